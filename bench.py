@@ -10,7 +10,11 @@ N > 1 (launched by torch.distributed.run, one rank per GPU): the batch axis is s
 filters its own map (weak scaling, no data-path collective); rank 0's filter parameters are broadcast
 once over RCCL before the timed region.
 
-Prints ONE JSON line on rank 0 (see the keys below).  `roofline` is for the whole chain launch
+Prints ONE JSON line on rank 0 (see the keys below).  A plain run reports the headline alone: `value` (cells/s of the K
+timed steps), `ms_per_step` and what describes the workload.  Everything else in this text needs `--full`.
+`--dump-outputs DIR` writes the layers the last timed step left for its caller (bench.dump_outputs).
+
+`roofline` is for the whole chain launch
 sequence: algorithmic bytes (20 B/cell chain, 24 B/cell with the footprint pass) divided
 by the chain's duration measured with HIP events on the stream the kernels run on (median of >= 100
 launches, one event pair per launch); `roofline.dominant_kernel` is the normals/slope/roughness pass timed
@@ -18,14 +22,15 @@ alone the same way (12 B/cell); `roofline_issue` prices the same launch against 
 issue rate, which is what bounds these kernels.
 `cpu_baseline` times the CPU oracle (our restatement of the reference; kind "port") on one host thread
 over a bounded crop of the same map; `cpu_baseline_all_cores` the same oracle with OpenMP over rows on every host core.
-`parity_check` (every run, rank 0): the layers the timed launches left on the device are compared with the oracle on EVERY
+`parity_check` (rank 0): the layers the timed launches left on the device are compared with the oracle on EVERY
 cell of the map (up to 4096^2; `--check-crops`: a corner crop and one full-width band); a mismatch fails the run (exit
 code 1) after the line is printed.
 `ranks`: how many ranks ran, over which backend, on which device each.  `--gpus N` without a launcher starts the N ranks
 itself (torch.distributed.run, one per GPU); a WORLD_SIZE that differs from --gpus is an error.
 
-Order of the run: upload -> event-timed samples of the launch (they also bring the GPU to its working clocks) -> W
-warm-up steps -> barrier + sync -> K timed steps -> sync + barrier -> parity check -> host path -> CPU baselines.
+Order of the run: upload -> event-timed samples of the launch (they also bring the GPU to its working clocks; a plain run
+makes as many launches untimed) -> W warm-up steps -> barrier + sync -> K timed steps -> sync + barrier -> --dump-outputs
+-> (--full: parity check -> host path -> CPU baselines).
 """
 import argparse
 import json
@@ -40,6 +45,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); measured copy ceiling 6290 GB/s
 N_SIMDS, CLOCK_HZ = 1024, 2.4e9
+DUMP_BYTES, DUMP_SEED = 48 << 20, 20240  # --dump-outputs: the data of all the .npy files together, and the seed of the cell sample
 FP64_LANE_OPS_PEAK = 39.3e12  # 78.6 TFLOP/s vector fp64 = 39.3e12 fused multiply-adds (lane operations) per second
 # double-precision lane operations per cell of one launch: the sliding moments of k_normals3 (6 per disc
 # column and edge + 1 per distinct run length: 118 at R = 9, scaled with 2R+1 for other radii) and its tail (31)
@@ -100,7 +106,34 @@ def parse():
                     help="cfg5: sync = te_upload_tile + te_run_chain_region + te_download_tile, one blocking call after the other (lowest latency "
                          "for small tiles); stream = the asynchronous pair on the copy streams (throughput for large tiles); auto: sync up to 512^2")
     ap.add_argument("--check", action="store_true", help="(default now; kept for old command lines)")
+    ap.add_argument("--full", action="store_true", help="also what the headline figure does not need: the event-timed launch samples "
+                    "(latency_ms_per_launch, roofline, roofline_issue; cfg5: the tick latency sample), the oracle parity check, the host "
+                    "path, the other cfg5 tick form and the CPU baselines (the --no-* / --check-crops / --cpu-* options shape these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed as DIR/<layer>.npy "
+                    "(float32; a layer larger than its share of %d MB is written as a fixed, seeded sample of its cells)" % (DUMP_BYTES >> 20))
     return ap.parse_args()
+
+
+def chain_outputs(with_fp, keep_normals=False):
+    """The layers a te_run_chain leaves for its caller."""
+    names = ["traversability_slope", "traversability_step", "traversability_roughness", "traversability"]
+    if with_fp:
+        names.append("traversability_footprint")
+    if keep_normals:
+        names += ["surface_normal_x", "surface_normal_y", "surface_normal_z"]
+    return names
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy in float32.  An array larger than its share of DUMP_BYTES is written as the
+    cells at DUMP_SEED's sorted random indices (flat), the same cells in every run: two builds compare value for value."""
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // 4 // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a, np.float32)
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=share, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def make_params(capi, synth, args):
@@ -390,7 +423,8 @@ def main():
 
         step = tick_sync if tick_mode == "sync" else tick_stream
 
-        # latency of ONE tick, host-timed (tile in, region run, tile out, wait), median of 48
+        # latency of ONE tick, host-timed (tile in, region run, tile out, wait), median of 48 (reported with --full; the 56 ticks
+        # run in every run: they settle the GPU before the warm-up, and the timed ticks start at the same tile in both forms)
         lat = []
         for _ in range(56):
             t0 = time.perf_counter()
@@ -406,15 +440,22 @@ def main():
         def step():
             ctx.run_chain(flags)
 
-        # kernel-only duration of the chain: HIP events on the context's own stream, one pair per launch, median of >= 100.
-        # Taken BEFORE the host-timed loop: the same launches, and they leave the GPU at its working clocks (the driver's
-        # 5 warm-up + 20 timed steps alone start on an idle device).
-        n_samples = max(100, args.steps)
-        chain_samples = ctx.time_chain_samples(flags, warmup=20, iters=n_samples)
-        ms_chain = float(np.median(chain_samples))
-        # the dominant kernel alone (normals/slope/roughness + its fix-up pass: TE_RUN_NORMALS_ONLY), the same way
-        normals_samples = ctx.time_chain_samples(capi.RUN_NORMALS_ONLY | (flags & capi.RUN_KEEP_NORMALS), warmup=5, iters=n_samples)
-        ms_normals = float(np.median(normals_samples))
+        ms_chain = ms_normals = None
+        if args.full:
+            # kernel-only duration of the chain: HIP events on the context's own stream, one pair per launch, median of >= 100.
+            # Taken BEFORE the host-timed loop: the same launches, and they leave the GPU at its working clocks (the driver's
+            # 5 warm-up + 20 timed steps alone start on an idle device).
+            n_samples = max(100, args.steps)
+            chain_samples = ctx.time_chain_samples(flags, warmup=20, iters=n_samples)
+            ms_chain = float(np.median(chain_samples))
+            # the dominant kernel alone (normals/slope/roughness + its fix-up pass: TE_RUN_NORMALS_ONLY), the same way
+            normals_samples = ctx.time_chain_samples(capi.RUN_NORMALS_ONLY | (flags & capi.RUN_KEEP_NORMALS), warmup=5, iters=n_samples)
+            ms_normals = float(np.median(normals_samples))
+        else:
+            # without the samples the GPU still has to reach its working clocks before the warm-up: as many launches as the
+            # two samples make at K <= 100 (a fixed number: the time outside the timed steps must not grow with K)
+            for _ in range(225):
+                ctx.run_chain(flags)
         ctx.run_chain(flags)  # (the normals-only launches overwrote two layers with the same values; keep the state simple)
         cells_timed = B * cells
 
@@ -432,9 +473,17 @@ def main():
     dt = time.perf_counter() - t0
     dt = tdist.max_over_ranks(dt)
 
+    # what a caller of the timed path received from its last step (rank 0: its own maps)
+    if rank == 0 and args.dump_outputs:
+        if tick is not None:  # one tick hands back the dirty tile's output layer
+            last = tick["last_out"] if tick_mode == "sync" else tiles_out[(tick["k"] - 1) % 8]
+            dump_outputs(args.dump_outputs, {out_layer + "_tile": last})
+        else:
+            dump_outputs(args.dump_outputs, {k: ctx.download(k).reshape(B, cols, rows) for k in chain_outputs(with_fp, flags & capi.RUN_KEEP_NORMALS)})
+
     # parity of what the timed launches left on the device (rank 0, map 0)
     check = None
-    if rank == 0 and not args.no_check:
+    if rank == 0 and args.full and not args.no_check:
         if tick is not None:
             # cfg5: the region runs must have left the resident layers as a whole-map run of the final elevation would:
             # windows around the last four tiles (each dilated by twice the parity margin), against the oracle
@@ -444,23 +493,22 @@ def main():
         else:
             check = parity_check(args, ctx, elevs[0], p, with_fp, rows, cols, whole=(not args.check_crops) and cells <= 4096 * 4096, pos=pos)
     if tick is not None:
-        other = tick_stream if tick_mode == "sync" else tick_sync  # the other form, 128 ticks, for the record
-        ctx.sync()
-        t0 = time.perf_counter()
-        for _ in range(128):
-            other()
-        ctx.sync()
-        tick["other_ms"] = (time.perf_counter() - t0) / 128 * 1e3
+        if args.full:
+            other = tick_stream if tick_mode == "sync" else tick_sync  # the other form, 128 ticks, for the record
+            ctx.sync()
+            t0 = time.perf_counter()
+            for _ in range(128):
+                other()
+            ctx.sync()
+            tick["other_ms"] = (time.perf_counter() - t0) / 128 * 1e3
         for buf in tiles_in + tiles_out:
             capi.unpin_host(buf)
 
     # plugin-shaped path: host buffers in, host buffers out (PCIe both ways); reported next to, never as, `value`
     host_path = None
-    if rank == 0 and world == 1 and not args.no_host_path and total_maps is None and args.config == "cfg3":  # N = 1 only: at N > 1 the other ranks would wait for it
+    if rank == 0 and world == 1 and args.full and not args.no_host_path and total_maps is None and args.config == "cfg3":  # N = 1 only: at N > 1 the other ranks would wait for it
         stack = np.stack(elevs)
-        names = ["traversability_slope", "traversability_step", "traversability_roughness", "traversability"]
-        if with_fp:
-            names.append("traversability_footprint")
+        names = chain_outputs(with_fp)
         best = None
         for _ in range(3):
             t0 = time.perf_counter()
@@ -561,9 +609,6 @@ def main():
 
     if rank == 0:
         cells_per_step = total_maps * cells if total_maps is not None else world * cells_timed
-        bytes_per_cell = 24 if with_fp else 20
-        achieved = cells_timed * bytes_per_cell / (ms_chain * 1e-3) / 1e9
-        is_cfg3 = args.config == "cfg3" and with_fp and n == 4096 and B == 1 and args.radius_cells == 9.0 and args.holes == 0.0 and not args.yaml
         what = {"cfg1": "the reference's bag map (TE/maps/elevation_map.bag), default robot_filter_parameter.yaml: ",
                 "cfg2": "", "cfg3": "", "cfg4": f"batch of {total_maps} maps cut over {world} rank(s), ",
                 "cfg5": f"8192x8192 resident map, one {args.tile}x{args.tile} dirty tile per step (tile H2D + region re-filter + tile D2H; "
@@ -577,10 +622,6 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3,
-            # latency of ONE launch (HIP events around a single te_run_chain, median) beside the loop's throughput figure above
-            "latency_ms_per_launch": ms_chain,
-            # what the host-timed loop carries on top of K event-timed launches (first-launch latency, the final sync)
-            "sync_overhead_ms": dt * 1e3 - args.steps * ms_chain,
             "higher_is_better": True,
             "scaling": "strong" if total_maps is not None else "weak",
             "vs_baseline": None,
@@ -594,94 +635,103 @@ def main():
                                    f"{' + traversability_footprint pass' if with_fp else ''}"
                                    + (f"; parameters from {os.path.basename(args.yaml)}" if args.yaml else ""),
                        "maps_per_gpu": B, "map_cells": cells, "radius_cells": args.radius_cells,
-                       "footprint": with_fp, "sharding": "batch axis, one map shard per rank, params broadcast over RCCL"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                         "kernel": "chain launch sequence (all kernels of one te_run_chain)",
-                         "ms_per_launch": ms_chain,
-                         "ms_per_launch_stat": (f"median of {n_samples} ticks, host-timed one at a time (tile H2D + region run + tile D2H + wait; " if tick is not None
-                                                else f"median of {n_samples} launches, one HIP event pair each (") +
-                                               f"p10 {np.percentile(chain_samples, 10):.4f}, p90 {np.percentile(chain_samples, 90):.4f})",
-                         "algorithmic_bytes_per_cell": bytes_per_cell},
+                       "footprint": with_fp, "sharding": "batch axis, one map shard per rank, params broadcast over RCCL"}
         }
-        if ms_normals is not None:
-            out["roofline"]["dominant_kernel"] = {
-                "name": "the normals / slope / roughness pass alone on the GPU (TE_RUN_NORMALS_ONLY: k_normals3s or k_normals3 + k_normals_fixup on the "
-                        "headline map -- rocprofv3 lists the two separately, profiles/ --, k_normals_small on discs of at most 13 cells)",
-                "ms": ms_normals, "algorithmic_bytes_per_cell": 12, "achieved": cells_timed * 12 / (ms_normals * 1e-3) / 1e9,
-                "frac": cells_timed * 12 / (ms_normals * 1e-3) / 1e9 / HBM_PEAK_GBS}
         if tick is not None:
             out["ticks_per_s"] = args.steps / dt
-            out["tick_latency_ms"] = ms_chain
             out["tick_mode"] = {"timed": tick_mode, "what": "sync: te_upload_tile + te_run_chain_region + te_download_tile, blocking; stream: "
-                                f"te_upload_tile_async / te_run_chain_region / te_download_tile_async on the copy streams, {args.in_flight} ticks in flight",
-                                ("stream" if tick_mode == "sync" else "sync") + "_ms_per_tick": tick["other_ms"]}
-            out["roofline"]["kernel"] = "one tick: tile H2D, region run of the chain (tile dilated by the reach), tile D2H -- latency-bound by construction"
-        # second roofline: what actually bounds these kernels is instruction issue, most of it double precision
-        ops = fp64_lane_ops_per_cell(args.radius_cells, with_fp) * cells_timed
-        out["roofline_issue"] = {"bound": "valu-f64", "achieved": ops / (ms_chain * 1e-3), "peak": FP64_LANE_OPS_PEAK,
-                                 "unit": "fp64 lane operations/s", "frac": ops / (ms_chain * 1e-3) / FP64_LANE_OPS_PEAK,
-                                 "lane_ops_per_cell": fp64_lane_ops_per_cell(args.radius_cells, with_fp),
-                                 "note": "algorithmic fp64 operations of the sliding moments, the tails and the footprint sum; "
-                                         "strip warm-up, staging and the float32 work are not counted"}
-        # HBM traffic of the same launch sequence: PMC counters need their own rocprofv3 passes (FETCH_SIZE and
-        # WRITE_SIZE do not fit one pass), so the number comes from the committed profile of this exact workload --
-        # and only if that profile was taken with the kernels of this tree (hash of csrc/)
-        import glob
-        tpaths = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_hbm_traffic.json")), reverse=True)  # newest round first
-        if tpaths and is_cfg3:
-            sha = kernel_sources_sha16()
-            hit = None
-            for tp in tpaths:
-                t = json.load(open(tp))
-                if t.get("kernel_sources_sha16") == sha:
-                    hit = (tp, t)
-                    break
-            if hit:
-                out["roofline"]["traffic"] = hit[1]["traffic_bytes"]
-                out["roofline"]["traffic_unit"] = f"bytes per launch (rocprofv3 FETCH_SIZE + WRITE_SIZE, profiles/{os.path.basename(hit[0])})"
-            else:
-                out["roofline"]["traffic_unit"] = f"not reported: profiles/{os.path.basename(tpaths[0])} was taken with other kernel sources"
-        # What this FORMULATION can reach at most: the launch is bound by vector-instruction issue, so
-        # the sum of the kernels' issue floors is a lower bound of its time, whatever the overlap.  Round 6 prices the
-        # executed VALU instructions BY CLASS (tools/valu_classes.py -> profiles/rNN_valu_classes.json: fp64 as counted by
-        # SQ_INSTS_VALU_*_F64 at 4.2 cycles per SIMD, the rest split by each kernel's loop mix into the 4.2-cycle class --
-        # 3-operand, min / max, compare, select, convert --, the 2.2-cycle class -- plain float32 / integer -- and float32
-        # transcendentals at 8.2); round 5 priced all of them at 4.2, which flattered the efficiency.  `frac` is to be read
-        # against this ceiling, not against 1.
-        vpaths = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_valu_classes.json")), reverse=True)
-        if vpaths and is_cfg3:
-            try:
-                vc = json.load(open(vpaths[0]))
-                if vc.get("kernel_sources_sha16") != kernel_sources_sha16():
-                    out["roofline"]["formulation_ceiling_error"] = f"profiles/{os.path.basename(vpaths[0])} was taken with other kernel sources"
+                                f"te_upload_tile_async / te_run_chain_region / te_download_tile_async on the copy streams, {args.in_flight} ticks in flight"}
+        if args.full:
+            bytes_per_cell = 24 if with_fp else 20
+            achieved = cells_timed * bytes_per_cell / (ms_chain * 1e-3) / 1e9
+            is_cfg3 = args.config == "cfg3" and with_fp and n == 4096 and B == 1 and args.radius_cells == 9.0 and args.holes == 0.0 and not args.yaml
+            # latency of ONE launch (HIP events around a single te_run_chain, median) beside the loop's throughput figure
+            out["latency_ms_per_launch"] = ms_chain
+            # what the host-timed loop carries on top of K event-timed launches (first-launch latency, the final sync)
+            out["sync_overhead_ms"] = dt * 1e3 - args.steps * ms_chain
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+                               "kernel": "chain launch sequence (all kernels of one te_run_chain)",
+                               "ms_per_launch": ms_chain,
+                               "ms_per_launch_stat": (f"median of {n_samples} ticks, host-timed one at a time (tile H2D + region run + tile D2H + wait; " if tick is not None
+                                                      else f"median of {n_samples} launches, one HIP event pair each (") +
+                                                     f"p10 {np.percentile(chain_samples, 10):.4f}, p90 {np.percentile(chain_samples, 90):.4f})",
+                               "algorithmic_bytes_per_cell": bytes_per_cell}
+            if ms_normals is not None:
+                out["roofline"]["dominant_kernel"] = {
+                    "name": "the normals / slope / roughness pass alone on the GPU (TE_RUN_NORMALS_ONLY: k_normals3s or k_normals3 + k_normals_fixup on the "
+                            "headline map -- rocprofv3 lists the two separately, profiles/ --, k_normals_small on discs of at most 13 cells)",
+                    "ms": ms_normals, "algorithmic_bytes_per_cell": 12, "achieved": cells_timed * 12 / (ms_normals * 1e-3) / 1e9,
+                    "frac": cells_timed * 12 / (ms_normals * 1e-3) / 1e9 / HBM_PEAK_GBS}
+            if tick is not None:
+                out["tick_latency_ms"] = ms_chain
+                out["tick_mode"][("stream" if tick_mode == "sync" else "sync") + "_ms_per_tick"] = tick["other_ms"]
+                out["roofline"]["kernel"] = "one tick: tile H2D, region run of the chain (tile dilated by the reach), tile D2H -- latency-bound by construction"
+            # second roofline: what actually bounds these kernels is instruction issue, most of it double precision
+            ops = fp64_lane_ops_per_cell(args.radius_cells, with_fp) * cells_timed
+            out["roofline_issue"] = {"bound": "valu-f64", "achieved": ops / (ms_chain * 1e-3), "peak": FP64_LANE_OPS_PEAK,
+                                     "unit": "fp64 lane operations/s", "frac": ops / (ms_chain * 1e-3) / FP64_LANE_OPS_PEAK,
+                                     "lane_ops_per_cell": fp64_lane_ops_per_cell(args.radius_cells, with_fp),
+                                     "note": "algorithmic fp64 operations of the sliding moments, the tails and the footprint sum; "
+                                             "strip warm-up, staging and the float32 work are not counted"}
+            # HBM traffic of the same launch sequence: PMC counters need their own rocprofv3 passes (FETCH_SIZE and
+            # WRITE_SIZE do not fit one pass), so the number comes from the committed profile of this exact workload --
+            # and only if that profile was taken with the kernels of this tree (hash of csrc/)
+            import glob
+            tpaths = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_hbm_traffic.json")), reverse=True)  # newest round first
+            if tpaths and is_cfg3:
+                sha = kernel_sources_sha16()
+                hit = None
+                for tp in tpaths:
+                    t = json.load(open(tp))
+                    if t.get("kernel_sources_sha16") == sha:
+                        hit = (tp, t)
+                        break
+                if hit:
+                    out["roofline"]["traffic"] = hit[1]["traffic_bytes"]
+                    out["roofline"]["traffic_unit"] = f"bytes per launch (rocprofv3 FETCH_SIZE + WRITE_SIZE, profiles/{os.path.basename(hit[0])})"
                 else:
-                    floor_cls, floor_all = vc["sum_issue_floor_us_by_class"], vc["sum_issue_floor_us_all_at_4.2"]
-                    ceiling = cells_timed * bytes_per_cell / (floor_cls * 1e-6) / 1e9 / HBM_PEAK_GBS
-                    out["roofline"]["formulation_ceiling"] = ceiling
-                    out["roofline"]["frac_of_ceiling"] = out["roofline"]["frac"] / ceiling
-                    out["roofline"]["formulation_ceiling_what"] = {
-                        "issue_floor_us_by_class": {k: v.get("issue_floor_us_by_class") for k, v in vc["kernels"].items()},
-                        "issue_floor_us_sum_by_class": floor_cls,
-                        "issue_floor_us_sum_all_at_4.2": floor_all,
-                        "formulation_ceiling_all_at_4.2 (round 5's model)": cells_timed * bytes_per_cell / (floor_all * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                        "model": "executed VALU instructions per launch (SQ counters) priced by class: fp64 / 3-operand / min-max / compare / select / convert "
-                                 f"4.2 cycles per SIMD, plain float32 and 2-operand integer 2.2, float32 transcendental 8.2 (profiles/r01_valu_rates.txt), "
-                                 f"/ ({N_SIMDS} SIMDs x {CLOCK_HZ / 1e9:.1f} GHz); the 2.2-cycle rate needs >= 4 waves per SIMD, so the floor is a lower bound "
-                                 "of the time and the ceiling an upper bound of the formulation's reach",
-                        "source": f"profiles/{os.path.basename(vpaths[0])} ({vc.get('counters')})",
-                        "note": "an fp64 sliding-disc formulation at R = 9 is bound by vector-instruction issue, not by HBM: "
-                                "the 50 % north-star presumes a bandwidth-bound stencil, which this is not (DESIGN.md 4)"}
-            except (OSError, ValueError, KeyError) as e:
-                out["roofline"]["formulation_ceiling_error"] = str(e)
-        if host_path is not None:
-            out["host_path"] = host_path
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
-            out["cpu_baseline"] = cpu_baseline(args, elevs[0], p, with_fp, pos=pos)
-            if not args.no_cpu_all_cores:  # single thread AND OpenMP over rows on all host cores
-                out["cpu_baseline_all_cores"] = cpu_baseline(args, elevs[0], p, with_fp, threads=0, pos=pos)  # (0: the fastest rung of a thread ladder)
-        if check is not None:
-            out["parity_check"] = check
+                    out["roofline"]["traffic_unit"] = f"not reported: profiles/{os.path.basename(tpaths[0])} was taken with other kernel sources"
+            # What this FORMULATION can reach at most: the launch is bound by vector-instruction issue, so
+            # the sum of the kernels' issue floors is a lower bound of its time, whatever the overlap.  Round 6 prices the
+            # executed VALU instructions BY CLASS (tools/valu_classes.py -> profiles/rNN_valu_classes.json: fp64 as counted by
+            # SQ_INSTS_VALU_*_F64 at 4.2 cycles per SIMD, the rest split by each kernel's loop mix into the 4.2-cycle class --
+            # 3-operand, min / max, compare, select, convert --, the 2.2-cycle class -- plain float32 / integer -- and float32
+            # transcendentals at 8.2); round 5 priced all of them at 4.2, which flattered the efficiency.  `frac` is to be read
+            # against this ceiling, not against 1.
+            vpaths = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_valu_classes.json")), reverse=True)
+            if vpaths and is_cfg3:
+                try:
+                    vc = json.load(open(vpaths[0]))
+                    if vc.get("kernel_sources_sha16") != kernel_sources_sha16():
+                        out["roofline"]["formulation_ceiling_error"] = f"profiles/{os.path.basename(vpaths[0])} was taken with other kernel sources"
+                    else:
+                        floor_cls, floor_all = vc["sum_issue_floor_us_by_class"], vc["sum_issue_floor_us_all_at_4.2"]
+                        ceiling = cells_timed * bytes_per_cell / (floor_cls * 1e-6) / 1e9 / HBM_PEAK_GBS
+                        out["roofline"]["formulation_ceiling"] = ceiling
+                        out["roofline"]["frac_of_ceiling"] = out["roofline"]["frac"] / ceiling
+                        out["roofline"]["formulation_ceiling_what"] = {
+                            "issue_floor_us_by_class": {k: v.get("issue_floor_us_by_class") for k, v in vc["kernels"].items()},
+                            "issue_floor_us_sum_by_class": floor_cls,
+                            "issue_floor_us_sum_all_at_4.2": floor_all,
+                            "formulation_ceiling_all_at_4.2 (round 5's model)": cells_timed * bytes_per_cell / (floor_all * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                            "model": "executed VALU instructions per launch (SQ counters) priced by class: fp64 / 3-operand / min-max / compare / select / convert "
+                                     f"4.2 cycles per SIMD, plain float32 and 2-operand integer 2.2, float32 transcendental 8.2 (profiles/r01_valu_rates.txt), "
+                                     f"/ ({N_SIMDS} SIMDs x {CLOCK_HZ / 1e9:.1f} GHz); the 2.2-cycle rate needs >= 4 waves per SIMD, so the floor is a lower bound "
+                                     "of the time and the ceiling an upper bound of the formulation's reach",
+                            "source": f"profiles/{os.path.basename(vpaths[0])} ({vc.get('counters')})",
+                            "note": "an fp64 sliding-disc formulation at R = 9 is bound by vector-instruction issue, not by HBM: "
+                                    "the 50 % north-star presumes a bandwidth-bound stencil, which this is not (DESIGN.md 4)"}
+                except (OSError, ValueError, KeyError) as e:
+                    out["roofline"]["formulation_ceiling_error"] = str(e)
+            if host_path is not None:
+                out["host_path"] = host_path
+            if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
+                out["cpu_baseline"] = cpu_baseline(args, elevs[0], p, with_fp, pos=pos)
+                if not args.no_cpu_all_cores:  # single thread AND OpenMP over rows on all host cores
+                    out["cpu_baseline_all_cores"] = cpu_baseline(args, elevs[0], p, with_fp, threads=0, pos=pos)  # (0: the fastest rung of a thread ladder)
+            if check is not None:
+                out["parity_check"] = check
         print(json.dumps(out), flush=True)
         if check is not None and not check["ok"]:
             print("parity check FAILED: " + json.dumps(check), file=sys.stderr)

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Decode the reference's only fixture (a rosbag holding one grid_map_msgs/GridMap) into a small
-.npz so that the known-answer test travels to the GPU box (``/root/reference`` does not).
+.npz so that the known-answer tests need no rosbag decoder.
 
-Source : /root/reference/traversability_estimation/maps/elevation_map.bag
+Source : tests/golden/elevation_map.bag, the reference's traversability_estimation/maps/elevation_map.bag unchanged
          (byte-identical copy: maps/traversability_map.bag) -- SURVEY.md F5/F6, Appendix A.
 Output : tests/golden/bag_map.npz  (geometry + elevation input + the reference's own golden outputs
          of the default filter chain, traversability_estimation/config/robot_filter_parameter.yaml).
 
-Run here (build container) only:  python tests/golden/make_golden.py
+Run:  python tests/golden/make_golden.py
 The decoder is dependency-free (no rosbag): ROSBAG V2.0 record walk + little-endian ROS
 serialisation of grid_map_msgs/GridMap.
 """
@@ -18,7 +18,7 @@ import sys
 
 import numpy as np
 
-BAG = "/root/reference/traversability_estimation/maps/elevation_map.bag"
+BAG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "elevation_map.bag")
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bag_map.npz")
 
 

@@ -181,7 +181,7 @@ def test_bench_gpus_2_without_a_launcher_runs_two_ranks(capi):
     rccl = capi.device_count() >= 2
     if not rccl:
         env["TE_DIST_BACKEND"] = "gloo"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--check-crops"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full", "--check-crops"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -207,7 +207,7 @@ def test_bench_under_the_drivers_launcher_over_rccl_with_one_rank(capi):
     env["TE_DIST_WORLD1_COLLECTIVES"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(tdist.free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
-           "--check-crops", "--no-cpu-baseline"]
+           "--full", "--check-crops", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -1,6 +1,6 @@
 """grid_map_msgs/GridMap messages and rosbag V2.0 images either side of the chain (C-ABI te_msg_* / te_bag_* /
 te_upload_msg / te_download_msg).  The host-side parsing and writing is checked on the CPU against an independent
-pure-Python decoder (tests/golden/make_golden.py) and, when the reference checkout is present, against its own bag."""
+pure-Python decoder (tests/golden/make_golden.py) and against the reference's own bag (tests/golden/elevation_map.bag)."""
 import hashlib
 import os
 import struct
@@ -168,9 +168,8 @@ def test_bag_with_several_messages_returns_the_last(capi):
     assert capi.bag_find_message(both, "grid_map") == m2
 
 
-@pytest.mark.skipif(not os.path.exists(REF_BAG), reason="the reference checkout is not on this machine")
 def test_reference_bag(capi, bag):
-    """The reference's own fixture (maps/elevation_map.bag) through te_bag_find_message + te_msg_parse."""
+    """The reference's own fixture (maps/elevation_map.bag, kept as tests/golden/elevation_map.bag) through te_bag_find_message + te_msg_parse."""
     raw = open(REF_BAG, "rb").read()
     assert hashlib.md5(raw).hexdigest() == bytes(bag["bag_md5"]).decode()
     msg = capi.bag_find_message(raw, "grid_map")

@@ -4,12 +4,14 @@ import os
 
 import pytest
 
+from tests.conftest import ROOT
 from traversability_estimation_amd import params_yaml as Y
 
-REF_CFG = "/root/reference/traversability_estimation/config"
+# the reference's traversability_estimation/config/*.yaml, unchanged
+REF_CFG = os.path.join(ROOT, "tests", "golden", "config")
 
 # the shipped chain, restated as data (robot_filter_parameter.yaml:1-37 holds the same keys and values; the test below
-# reads the reference's own file wherever /root/reference exists)
+# reads the reference's own file)
 SHIPPED = """
 traversability_map_filters:
   - {name: surfaceNormalsFilter, type: gridMapFilters/NormalVectorsFilter,
@@ -48,7 +50,6 @@ def test_shipped_values_reproduce_the_library_defaults(capi):
     assert _same(capi, p, capi.default_params()) and flags == 0
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="the reference tree is not on this box")
 def test_the_references_own_files_reproduce_the_library_defaults(capi):
     p, flags = Y.params_from_yaml(capi, os.path.join(REF_CFG, "robot_filter_parameter.yaml"),
                                   os.path.join(REF_CFG, "robot_footprint_parameter.yaml"), os.path.join(REF_CFG, "robot.yaml"))

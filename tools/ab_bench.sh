@@ -9,6 +9,7 @@
 #
 # Prints ms per step / per launch and the per-kernel averages (rocprofv3 --kernel-trace --stats) per variant.
 cd /tmp && export TMPDIR=/tmp
+AB_FLAGS="--full $AB_FLAGS"  # (the line's roofline.ms_per_launch, and the event-timed launches in the kernel averages)
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 for rep in 1 2; do for v in "$@"; do
   export TRAVGPU_LIB=$ROOT/traversability_estimation_amd/libtravgpu_$v.so

@@ -5,9 +5,9 @@ TAG=${1:-check}; shift
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}; O=$ROOT/gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp; cd /tmp
 (cd $ROOT && timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -15) > $O/pytest.log
-env "$@" python $ROOT/bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-host-path > $O/bench.json 2>$O/bench.err
+env "$@" python $ROOT/bench.py --steps 100 --warmup 20 --full --no-cpu-baseline --no-host-path > $O/bench.json 2>$O/bench.err
 for m in "" "--sequential"; do
-  env "$@" rocprofv3 --kernel-trace --stats -d $O/kt$m -o p --output-format csv -- python $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-host-path $m > $O/kt$m.log 2>&1
+  env "$@" rocprofv3 --kernel-trace --stats -d $O/kt$m -o p --output-format csv -- python $ROOT/bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-host-path $m > $O/kt$m.log 2>&1
 done
 python - <<PY
 import csv, glob, re

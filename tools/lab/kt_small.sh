@@ -1,7 +1,7 @@
 # the kernels of the small launches one by one (cfg1 = the bag map, cfg2 = 1024^2; chain + footprint, one stream)
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}; O=$ROOT/gpurun_out/r06h; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 for C in cfg1 cfg2; do
-  rocprofv3 --kernel-trace --stats -d $O/kt_$C -o d --output-format csv -- python $ROOT/bench.py --config $C --footprint --steps 200 --warmup 20 --sequential --no-cpu-baseline > $O/kt_$C.log 2>&1
+  rocprofv3 --kernel-trace --stats -d $O/kt_$C -o d --output-format csv -- python $ROOT/bench.py --config $C --footprint --steps 200 --warmup 20 --sequential --full --no-cpu-baseline > $O/kt_$C.log 2>&1
   echo "== $C"
   python - <<PY
 import csv, glob, re

@@ -11,7 +11,7 @@ timeout 900 python -m pytest tests -q -m gpu -n 4 > $OUT/pytest.log 2>&1
 echo "pytest rc=$?" >> $OUT/pytest.log
 tail -8 $OUT/pytest.log
 for k in 1 2 3; do
-  timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_$k.json 2> $OUT/bench_$k.err
+  timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $OUT/bench_$k.json 2> $OUT/bench_$k.err
   python - <<PY
 import json
 d = json.loads(open("$OUT/bench_$k.json").read().strip().splitlines()[-1])

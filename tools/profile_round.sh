@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python $ROOT/bench.py"
+BENCH="python $ROOT/bench.py --full"
 PROF_ARGS="--steps 5 --warmup 2 --no-cpu-baseline --no-host-path --no-check"  # (bench.py itself adds 2 x 100 event-timed launches)
 
 (cd $ROOT && timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -25) > $OUT/pytest.log

@@ -8,9 +8,9 @@ mkdir -p $O
 export TMPDIR=/tmp
 ulimit -c 0
 cd /tmp
-(cd $ROOT && timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench rc=$?")
+(cd $ROOT && timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench rc=$?")
 cut -c1-2400 $O/bench_driver.json
-(cd $ROOT && timeout 900 python bench.py --config cfg4 --gpus 1 > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "cfg4 rc=$?")
+(cd $ROOT && timeout 900 python bench.py --config cfg4 --gpus 1 --full > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "cfg4 rc=$?")
 cut -c1-1600 $O/bench_cfg4.json
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/kt_ovl -o p --output-format csv -- python $ROOT/tools/ab_chain.py --iters 30 > $O/kt_ovl.log 2>&1
 python - <<PY

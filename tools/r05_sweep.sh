@@ -10,5 +10,5 @@ echo "rc=$?" >> $O/pytest.log
 grep -E "^FAILED|passed|failed|rc=" $O/pytest.log | tail -12
 grep -E "mismatches=[1-9]" $O/pytest.log | sort | uniq -c | sort -rn | head -12
 export TMPDIR=/tmp
-(timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench rc=$?")
+(timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench rc=$?")
 cut -c1-600 $O/bench_driver.json

@@ -10,29 +10,29 @@ mkdir -p $O
 export TMPDIR=/tmp
 ulimit -c 0
 cd $ROOT
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench rc=$?"
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench rc=$?"
 cut -c1-1200 $O/bench_driver.json
 for cfg in cfg1 cfg2 cfg5; do
-  timeout 900 python bench.py --config $cfg > $O/bench_$cfg.json 2> $O/bench_$cfg.err; echo "$cfg rc=$?"
-  timeout 900 python bench.py --config $cfg --footprint --no-cpu-baseline > $O/bench_${cfg}_footprint.json 2> $O/bench_${cfg}_footprint.err; echo "$cfg+fp rc=$?"
+  timeout 900 python bench.py --config $cfg --full > $O/bench_$cfg.json 2> $O/bench_$cfg.err; echo "$cfg rc=$?"
+  timeout 900 python bench.py --config $cfg --footprint --full --no-cpu-baseline > $O/bench_${cfg}_footprint.json 2> $O/bench_${cfg}_footprint.err; echo "$cfg+fp rc=$?"
 done
-timeout 900 python bench.py --config cfg4 --gpus 1 > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "cfg4 rc=$?"
-TE_DIST_BACKEND=gloo timeout 900 python bench.py --gpus 2 --steps 20 --warmup 5 > $O/bench_gpus2_gloo.json 2> $O/bench_gpus2_gloo.err; echo "gpus2 rc=$?"
-TE_DIST_BACKEND=gloo timeout 900 python bench.py --config cfg4 --gpus 2 --steps 10 --warmup 2 > $O/bench_cfg4_gpus2_gloo.json 2> $O/bench_cfg4_gpus2_gloo.err; echo "cfg4 gpus2 rc=$?"
-python -c "from tests.test_params_yaml import SHIPPED, FOOTPRINT; open('/tmp/f.yaml','w').write(SHIPPED); open('/tmp/fp.yaml','w').write(FOOTPRINT)"
+timeout 900 python bench.py --config cfg4 --gpus 1 --full > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "cfg4 rc=$?"
+TE_DIST_BACKEND=gloo timeout 900 python bench.py --gpus 2 --steps 20 --warmup 5 --full > $O/bench_gpus2_gloo.json 2> $O/bench_gpus2_gloo.err; echo "gpus2 rc=$?"
+TE_DIST_BACKEND=gloo timeout 900 python bench.py --config cfg4 --gpus 2 --steps 10 --warmup 2 --full > $O/bench_cfg4_gpus2_gloo.json 2> $O/bench_cfg4_gpus2_gloo.err; echo "cfg4 gpus2 rc=$?"
+python -c "from tests.test_params_yaml import SHIPPED, FOOTPRINT; open('$O/f.yaml','w').write(SHIPPED); open('$O/fp.yaml','w').write(FOOTPRINT)"
 for n in 1024 4096; do
-  timeout 900 python bench.py --yaml /tmp/f.yaml --footprint-yaml /tmp/fp.yaml --size $n --steps 50 --warmup 10 --no-cpu-all-cores > $O/bench_yaml_$n.json 2> $O/bench_yaml_$n.err; echo "yaml $n rc=$?"
+  timeout 900 python bench.py --yaml $O/f.yaml --footprint-yaml $O/fp.yaml --size $n --steps 50 --warmup 10 --full --no-cpu-all-cores > $O/bench_yaml_$n.json 2> $O/bench_yaml_$n.err; echo "yaml $n rc=$?"
 done
 timeout 600 python tools/defaults_bench.py > $O/defaults.json 2> $O/defaults.err
 for h in 0.001 0.003 0.01 0.55 0.6 0.7; do
-  timeout 600 python bench.py --holes $h --steps 50 --warmup 10 --no-cpu-baseline --no-host-path > $O/holes_$h.json 2> $O/holes_$h.err; echo "holes $h rc=$?"
+  timeout 600 python bench.py --holes $h --steps 50 --warmup 10 --full --no-cpu-baseline --no-host-path > $O/holes_$h.json 2> $O/holes_$h.err; echo "holes $h rc=$?"
 done
 cd /tmp
-timeout 300 rocprofv3 --marker-trace --kernel-trace --stats -d $O/marker -o m --output-format csv -- python $ROOT/bench.py --config cfg2 --footprint --steps 5 --warmup 2 --no-cpu-baseline --no-check > $O/marker.log 2>&1
+timeout 300 rocprofv3 --marker-trace --kernel-trace --stats -d $O/marker -o m --output-format csv -- python $ROOT/bench.py --config cfg2 --footprint --steps 5 --warmup 2 --full --no-cpu-baseline --no-check > $O/marker.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/kt_ovl -o p --output-format csv -- python $ROOT/tools/ab_chain.py --iters 30 > $O/kt_ovl.log 2>&1
 TE_SIZES=4096 timeout 300 rocprofv3 --kernel-trace --stats -d $O/kt_defaults -o d --output-format csv -- python $ROOT/tools/defaults_bench.py profile > $O/kt_defaults.log 2>&1
 for c in cfg1 cfg2; do
-  timeout 300 rocprofv3 --kernel-trace --stats -d $O/kt_$c -o p --output-format csv -- python $ROOT/bench.py --config $c --footprint --steps 50 --warmup 5 --no-cpu-baseline --no-check > $O/kt_$c.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats -d $O/kt_$c -o p --output-format csv -- python $ROOT/bench.py --config $c --footprint --steps 50 --warmup 5 --full --no-cpu-baseline --no-check > $O/kt_$c.log 2>&1
 done
 python - <<PY
 import csv, glob, re

@@ -28,10 +28,10 @@ kt A TRAVGPU_LIB=$P/libtravgpu_A.so
 kt B TRAVGPU_LIB=$P/libtravgpu_B.so
 kt B_strip8 TRAVGPU_LIB=$P/libtravgpu_B.so TE_F3_MIN_STRIP=8 TE_FP_MIN_STRIP=8
 for v in A B; do
-  TRAVGPU_LIB=$P/libtravgpu_$v.so python $ROOT/bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-host-path > $O/bench_$v.json 2> $O/bench_$v.err
-  TRAVGPU_LIB=$P/libtravgpu_$v.so rocprofv3 --kernel-trace --stats -d $O/ktb_$v -o p --output-format csv -- python $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-host-path --sequential > $O/ktb_$v.log 2>&1
+  TRAVGPU_LIB=$P/libtravgpu_$v.so python $ROOT/bench.py --steps 50 --warmup 10 --full --no-cpu-baseline --no-host-path > $O/bench_$v.json 2> $O/bench_$v.err
+  TRAVGPU_LIB=$P/libtravgpu_$v.so rocprofv3 --kernel-trace --stats -d $O/ktb_$v -o p --output-format csv -- python $ROOT/bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-host-path --sequential > $O/ktb_$v.log 2>&1
   for h in 0.001 0.6; do
-    TRAVGPU_LIB=$P/libtravgpu_$v.so python $ROOT/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-host-path --holes $h > $O/bench_${v}_h$h.json 2> $O/bench_${v}_h$h.err
+    TRAVGPU_LIB=$P/libtravgpu_$v.so python $ROOT/bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-host-path --holes $h > $O/bench_${v}_h$h.json 2> $O/bench_${v}_h$h.err
     python - <<PY
 import json
 d = json.loads(open("$O/bench_${v}_h$h.json").read().strip().splitlines()[-1]); r = d["roofline"]
