@@ -70,7 +70,7 @@ typedef enum te_status {
   TE_ERR_NOT_READY = -3,   /* geometry/params/elevation missing, or chain not run before footprint */
   TE_ERR_HIP = -4,         /* HIP runtime error (message has hipGetErrorString) */
   TE_ERR_NO_DEVICE = -5,   /* no usable gfx950 device: the library never falls back to the CPU */
-  TE_ERR_UNSUPPORTED = -6  /* e.g. radius too large for the on-chip tile */
+  TE_ERR_UNSUPPORTED = -6  /* a filter radius above 32 cells (the on-chip tile); a circular footprint only when its tables do not fit in device memory */
 } te_status;
 
 /* Layers owned by a context (device-resident, [batch][cols][rows] float32). */
@@ -170,6 +170,7 @@ int te_get_params(te_ctx* ctx, te_params* p);
 #define TE_OPT_GRAPH_REPLAY 4             /* whole-map launches as a captured hipGraph: 0 by size (the default: from 2^22 cells), 1 always, 2 never */
 #define TE_OPT_POLYGON_PER_CELL 3         /* polygon footprint layers: 1 evaluates every cell of every bounding box instead of the offset table */
 #define TE_OPT_BCAST_RCCL 5               /* te_bcast_params, set on the ROOT context: 0 RCCL only between different devices (the default), 1 also when all contexts share one device (a communicator of one rank) */
+#define TE_OPT_FP_ANY_REACH 7             /* circular footprint pass: 0 (default) by reach -- up to 20 cells the shape-specialised sum kernels, above 20 the route of any reach; 1 the route of any reach for every footprint */
 #define TE_OPT_NORMALS_RANK_RULE 6        /* 1: NormalVectorsFilter as grid_map <= 1.6 had it (the filter that wrote TE/maps/elevation_map.bag): a disc whose scatter matrix is rank-deficient -- exactly planar -- gets UnitZ; runs the shape-generic kernels.  0 (default): the current area method */
 int te_set_option(te_ctx* ctx, int option, int value);
 /* rows = size(0), cols = size(1) of every map of the batch; (pos_x,pos_y) = map centre. */
@@ -230,7 +231,9 @@ int te_run_chain(te_ctx* ctx, unsigned flags);
  * A footprint shape none of the shape-specialised sum kernels takes (a tie radius that is not a whole number of cells,
  * a reach of 17..20 cells, a map narrower than 64 cells) is served by the general kernel, which recomputes the footprint
  * layer of the WHOLE map `map` (no other map of the batch): cost O(map), not O(region); cells outside the region are
- * recomputed from unchanged inputs and keep their values to within the fixed-point kernels' rounding (< 1e-6). */
+ * recomputed from unchanged inputs and keep their values to within the fixed-point kernels' rounding (< 1e-6).
+ * A reach above 20 cells (or TE_OPT_FP_ANY_REACH = 1): the route of any reach recomputes the column prefix sums of the
+ * whole map `map` (one streaming pass) and the footprint on the region grown by the reach only. */
 int te_run_chain_region(te_ctx* ctx, unsigned flags, int map, int row0, int col0, int h, int w);
 /* The h x w rectangle at (row0, col0) of a layer of map `map` into a packed column-major h x w host tile (the layout
  * te_upload_tile reads); returns when the tile is in host memory. */

@@ -67,6 +67,12 @@ struct te_ctx {
   int16_t* d_spiral = nullptr;
   int* clip_table = nullptr;
   int* fp_clip_table = nullptr;
+  // the circular footprint at any reach (te_footprint_any.hip): its tables and its prefix-sum scratch, allocated when the
+  // footprint tables are rebuilt for that route (never inside a launch: whole-map launches are captured into a hipGraph)
+  void* fpa_tab = nullptr;
+  size_t fpa_tab_bytes = 0;
+  void* fpa_prefix = nullptr;  // [batch][cols][rows + 1] doubles, then as many unsigned
+  size_t fpa_prefix_bytes = 0;
   bool combine_deferred = false;
   // the traversability layer was written from outside (upload, device pointer, a per-plugin combine of uploaded scores):
   // its values are then not bounded by the weights, and the fixed-point footprint kernel must not be used
@@ -76,7 +82,8 @@ struct te_ctx {
   // still assume the bound; te_run_footprint and region runs take the double kernel.  Reset with the layers.
   bool trav_ptr_out = false;
   // te_set_option: choices between kernels that give identical results (tests reach both; never read from the environment)
-  int opt_fb_walk = 0, opt_fb_blocks_per_cu = 0, opt_polygon_per_cell = 0, opt_graph = 0, opt_bcast_rccl = 0, opt_rank_rule = 0;
+  int opt_fb_walk = 0, opt_fb_blocks_per_cu = 0, opt_polygon_per_cell = 0, opt_graph = 0, opt_bcast_rccl = 0, opt_rank_rule = 0,
+      opt_fp_any = 0;
   // invalid cells of the elevation layer as of the last whole upload (-1: unknown -- tiles, device pointer): see sparse_holes()
   long long invalid_cells = -1;
   long long invalid_runs = -1;  // runs of invalid cells in memory order (k_count_invalid); meaningful with invalid_cells >= 0
@@ -84,8 +91,8 @@ struct te_ctx {
   char* hole_queue = nullptr;  // scratch of k_normals3's sparse-hole march (allocated when a launch first picks it)
   float* tie_scratch = nullptr;  // one float per cell: the step filter at a tie radius (allocated when a launch first needs it, freed with the layers)
   bool tables_ready = false;
-  // the circular-footprint tables are built separately: a footprint this build cannot handle (more than 20 cells) must
-  // not stop the filter chain or the per-plugin entry points, which never use them (the reference has no such coupling)
+  // the circular-footprint tables are built separately: a footprint whose tables do not fit in device memory must not
+  // stop the filter chain or the per-plugin entry points, which never use them (the reference has no such coupling)
   bool fp_tables_ready = false;
   int fp_tables_rc = TE_OK;
   char fp_tables_err[256] = "";

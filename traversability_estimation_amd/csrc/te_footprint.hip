@@ -1312,6 +1312,8 @@ hipError_t launch_footprint(const Geo& g, const FootprintParams& p, const Layers
   }
   TraceRange tr_sum("footprint: disc sums (+ blocked discs)");
   const Region* rfp = region ? &rf : nullptr;
+  // a reach above 20 cells (or TE_OPT_FP_ANY_REACH): the route of any reach; the kernels below serve reaches up to 20
+  if (p.any) return launch_footprint_any(g, p, L, rfp, stream);
   SpiralArgs a;
   const Disc& d = p.fp_disc;
   for (int k = 0; k <= kMaxRadiusCells; ++k) a.h[k] = (k <= d.R) ? d.hw[k] : -1;
@@ -1370,7 +1372,7 @@ hipError_t launch_footprint(const Geo& g, const FootprintParams& p, const Layers
     break;
     X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20)
 #undef X
-    default:
+    default:  // (unreachable: a reach above 20 cells takes the route of any reach, above)
       return hipErrorInvalidValue;
   }
   return hipGetLastError();

@@ -116,6 +116,15 @@ struct FootprintParams {
   double rmin, rmax, def, max_gap, crit_step;
   int check_rough;
   int n_spiral;      // entries of the ordered spiral table
+  // the route of any reach (te_footprint_any.hip): above 20 cells, or every reach with TE_OPT_FP_ANY_REACH = 1.  Its
+  // tables (te_fp_table.h, clipped to the map) and the prefix-sum scratch are device buffers of the context, allocated
+  // when the tables are rebuilt; fp_disc and the shape-specialised tables are not built for a reach above 20 cells.
+  int any;              // 1: this route serves the pass
+  const int* any_spiral;  // FpEntry [any_n_spiral]: {di, dj, ring, tie}
+  const int* any_ints;    // run half-widths [any_R + 1], inner-disc half-widths [any_inner_R + 1], ties [2 any_n_ties]
+  double* any_psum;       // [batch][cols][rows + 1]: column prefix sums of T'
+  unsigned* any_pcnt;     // [batch][cols][rows + 1]: column prefix counts of untraversable cells
+  int any_n_spiral, any_R, any_inner_R, any_n_ties, any_k_inner;
 };
 
 struct Layers {
@@ -303,6 +312,9 @@ hipError_t launch_chain(const Geo& g, const ChainParams& p, const Layers& L, con
 hipError_t launch_footprint(const Geo& g, const FootprintParams& p, const Layers& L, const int16_t* spiral_table,
                             const int* clip_table, bool write_memo, const ChainParams* combine, double trav_cap, hipStream_t stream,
                             const Region* region = nullptr);
+// te_footprint_any.hip: the sum of the circular footprint pass at any reach (the mask kernel has run); rf: the output
+// cells of map rf->map (nullptr: every cell of every map)
+hipError_t launch_footprint_any(const Geo& g, const FootprintParams& p, const Layers& L, const Region* rf, hipStream_t s);
 int chain_max_reach(const ChainParams& p);
 // the flag grid of Layers::untrav_flags: one byte per 64 x 4 cells of every map
 inline int untrav_flag_ntx(int rows) { return (rows + 63) / 64; }

@@ -3,6 +3,7 @@
 // Owns the device-resident elevation/output layers of a batch of maps and launches the HIP chain.
 // No CPU fallback of any kind: without a gfx950 device te_create() fails with TE_ERR_NO_DEVICE.
 #include "te_ctx.h"
+#include "te_fp_table.h"
 #include "te_hole_routing.h"
 
 using namespace te;
@@ -245,6 +246,81 @@ void drop_graph(te_ctx* c) {
   }
 }
 
+void release_fp_any(te_ctx* c) {
+  if (c->fpa_tab) (void)hipFree(c->fpa_tab);
+  if (c->fpa_prefix) (void)hipFree(c->fpa_prefix);
+  c->fpa_tab = c->fpa_prefix = nullptr;
+  c->fpa_tab_bytes = c->fpa_prefix_bytes = 0;
+  c->fp.any_spiral = nullptr;
+  c->fp.any_ints = nullptr;
+  c->fp.any_psum = nullptr;
+  c->fp.any_pcnt = nullptr;
+}
+
+// (device memory for the route of any reach: the only way its tables can fail)
+static int fp_any_alloc(te_ctx* c, void** buf, size_t* have, size_t bytes, const char* what) {
+  if (*buf && *have >= bytes) return TE_OK;
+  if (*buf) (void)hipFree(*buf);
+  *buf = nullptr;
+  *have = 0;
+  if (hipMalloc(buf, bytes) != hipSuccess) {
+    *buf = nullptr;
+    (void)hipGetLastError();
+    return fail(TE_ERR_UNSUPPORTED, "footprint radius %.3g m is %d cells: its %s (%zu bytes) do not fit in device memory", c->fp.rmax,
+                c->fp.reach, what, bytes);
+  }
+  *have = bytes;
+  return TE_OK;
+}
+
+// The tables of the route of any reach (te_footprint_any.hip) on the device: run half-widths, those of the inner disc (the
+// rings within radiusMin that the SpiralIterator takes whole, fast::footprint_inner_q), the tie offsets, the spiral; and
+// the prefix-sum scratch of the maps.  Allocated here and never inside a launch (whole-map launches are captured).
+int build_fp_any_tables(te_ctx* c, const FpTable& t) {
+  FootprintParams& f = c->fp;
+  const Geo& g = c->geo;
+  std::vector<int32_t> ints(t.hw.begin(), t.hw.end());
+  f.any_R = t.R;
+  f.any_inner_R = -1;
+  f.any_k_inner = 0;
+  const int inner_q = fast::footprint_inner_q(g.res, f.rmin, f.rmax);
+  if (inner_q >= 0) {  // cells with di^2 + dj^2 <= inner_q: rings 0 .. d with (d + 1)^2 = inner_q + 1
+    auto isqrt = [](long long v) {
+      long long r = (long long)sqrt((double)v);
+      while (r * r > v) --r;
+      while ((r + 1) * (r + 1) <= v) ++r;
+      return r;
+    };
+    const long long d = isqrt((long long)inner_q + 1) - 1;
+    for (long long b = 0; b <= isqrt(inner_q) && b < g.cols; ++b) {
+      const long long a = isqrt((long long)inner_q - b * b);
+      ints.push_back((int32_t)(a > g.rows - 1 ? g.rows - 1 : a));
+      f.any_inner_R = (int)b;
+    }
+    while (f.any_k_inner < (int)t.spiral.size() && t.spiral[f.any_k_inner].ring <= d) ++f.any_k_inner;
+    for (size_t k = f.any_k_inner; k < t.spiral.size(); ++k)
+      if (t.spiral[k].ring <= d) return fail(TE_ERR_UNSUPPORTED, "footprint: the inner rings are not a prefix of the spiral");
+  }
+  ints.insert(ints.end(), t.ties.begin(), t.ties.end());
+  f.any_n_ties = (int)t.ties.size() / 2;
+  f.any_n_spiral = (int)t.spiral.size();
+  while (ints.size() % 4) ints.push_back(0);  // (the spiral behind them 16-byte aligned)
+  const size_t ib = ints.size() * sizeof(int32_t), sb = t.spiral.size() * sizeof(FpEntry);
+  HIP_TRY(hipSetDevice(c->device));
+  int rc;
+  if ((rc = fp_any_alloc(c, &c->fpa_tab, &c->fpa_tab_bytes, ib + sb, "tables"))) return rc;
+  const size_t cells = (size_t)g.batch * g.cols * (size_t)(g.rows + 1);
+  if ((rc = fp_any_alloc(c, &c->fpa_prefix, &c->fpa_prefix_bytes, cells * (sizeof(double) + sizeof(unsigned)), "prefix sums"))) return rc;
+  HIP_TRY(hipMemcpyAsync(c->fpa_tab, ints.data(), ib, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync((char*)c->fpa_tab + ib, t.spiral.data(), sb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  f.any_ints = (const int*)c->fpa_tab;
+  f.any_spiral = (const int*)((const char*)c->fpa_tab + ib);
+  f.any_psum = (double*)c->fpa_prefix;
+  f.any_pcnt = (unsigned*)((char*)c->fpa_prefix + cells * sizeof(double));
+  return TE_OK;
+}
+
 // Discs of the three footprint checks, SpiralIterator order and clip table of the circular footprint pass.  A failure is
 // recorded (fp_tables_rc / fp_tables_err) and reported by the entry points that need the footprint, not by the chain.
 int rebuild_footprint_tables_impl(te_ctx* c) {
@@ -258,7 +334,6 @@ int rebuild_footprint_tables_impl(te_ctx* c) {
     if ((rc = build_disc(2.5 * res, res, &f.step_disc, "footprint step window"))) return rc;     // :798
     f.rmin = p.fp_radius;
     f.rmax = p.fp_radius + p.fp_offset;  // :312 isTraversable(center, radius + offset, ..., radius)
-    if ((rc = build_disc(f.rmax, res, &f.fp_disc, "footprint"))) return rc;
     f.def = p.fp_default;
     f.max_gap = p.fp_max_gap;
     f.crit_step = p.fp_critical_step;
@@ -268,6 +343,20 @@ int rebuild_footprint_tables_impl(te_ctx* c) {
       f.ncrit_slope = (int)floor(2 * wr * crit_len / pow(res, 2));    // :873
       f.ncrit_rough = (int)floor(1.5 * wr * crit_len / pow(res, 2));  // :901
     }
+    // the spiral of any reach, clipped to the map (te_fp_table.h): its reach picks the route.  Above 20 cells the route of
+    // any reach serves the pass, and fp_disc and the tables of the shape-specialised kernels are not built.
+    FpTable any;
+    build_fp_table(f.rmax, res, c->geo.rows, c->geo.cols, &any);
+    f.any = (c->opt_fp_any || any.reach > 20) ? 1 : 0;
+    if (any.reach > 20) {
+      memset(&f.fp_disc, 0, sizeof(f.fp_disc));
+      f.fp_disc.R = -1;
+      f.fp_disc.r2 = f.rmax * f.rmax;
+      f.reach = any.reach;
+      f.n_spiral = 0;
+      return build_fp_any_tables(c, any);
+    }
+    if ((rc = build_disc(f.rmax, res, &f.fp_disc, "footprint"))) return rc;
     // SpiralIterator order (grid_map_core): centre, then ring d = 1..nRings, each generated by a perimeter
     // walk from (d, 0) and consumed from the back; only the two outer rings are tested against the circle.
     const Disc& d = f.fp_disc;
@@ -323,8 +412,8 @@ int rebuild_footprint_tables_impl(te_ctx* c) {
     }
     f.n_spiral = (int)tab.size() / 4;
     f.reach = reach < 1 ? 1 : reach;
-    if (f.reach > 20 || f.n_spiral > kMaxSpiral)
-      return fail(TE_ERR_UNSUPPORTED, "footprint radius %.3g m is %d cells; this build supports up to 20", f.rmax, f.reach);
+    if (f.reach > 20 || f.n_spiral > kMaxSpiral)  // (a reach above 20 cells took the route of any reach above)
+      return fail(TE_ERR_UNSUPPORTED, "footprint radius %.3g m is %d cells: internal routing error", f.rmax, f.reach);
     std::vector<int> ctab((size_t)(2 * f.reach + 1) * (2 * f.reach + 1) * 6);
     fast::build_clip_table(d, f.reach, ctab.data());
     HIP_TRY(hipSetDevice(c->device));
@@ -358,6 +447,8 @@ int rebuild_footprint_tables_impl(te_ctx* c) {
     HIP_TRY(hipMemcpyAsync(c->d_spiral, tab.data(), tab.size() * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->fp_clip_table, ctab.data(), ctab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    if (f.any) return build_fp_any_tables(c, any);  // TE_OPT_FP_ANY_REACH
+    release_fp_any(c);
   }
   return TE_OK;
 }
@@ -448,6 +539,7 @@ void free_layers(te_ctx* c) {
   c->robot_slope = nullptr;
   if (c->tie_scratch) (void)hipFree(c->tie_scratch);
   c->tie_scratch = nullptr;
+  release_fp_any(c);  // (its prefix sums are sized by the geometry; rebuilt with the tables)
   c->have_robot_slope = false;
   memset(&c->L, 0, sizeof(c->L));
   c->layer_elems = 0;
@@ -763,6 +855,7 @@ int te_destroy(te_ctx* c) {
     if (c->hole_queue) (void)hipFree(c->hole_queue);
     if (c->clip_table) (void)hipFree(c->clip_table);
     if (c->fp_clip_table) (void)hipFree(c->fp_clip_table);
+    release_fp_any(c);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
@@ -828,6 +921,14 @@ int te_set_option(te_ctx* c, int option, int value) {
     case TE_OPT_BCAST_RCCL:
       c->opt_bcast_rccl = value != 0;
       return TE_OK;  // (no launch depends on it)
+    case TE_OPT_FP_ANY_REACH:
+      if (value < 0 || value > 1) return fail(TE_ERR_INVALID_ARG, "te_set_option: TE_OPT_FP_ANY_REACH takes 0 (by reach) or 1 (every reach)");
+      if (c->opt_fp_any != value) {
+        c->opt_fp_any = value;
+        c->footprint_done = false;
+        if (c->tables_ready) rebuild_footprint_tables(c);
+      }
+      break;
     case TE_OPT_NORMALS_RANK_RULE:
       c->opt_rank_rule = value != 0;
       c->chain_done = false;
