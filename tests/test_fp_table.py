@@ -1,7 +1,7 @@
 """te_fp_table.h on the CPU, from the header the route of any reach is built from (te_footprint_any.hip): for footprints of
 21 to 150 cells its spiral is the oracle's SpiralIterator (order, ring distances; the tie-flagged entries exactly the ones
 isInside decides per centre), its runs and ties are the same disc, and the clip to the map drops exactly the offsets no
-centre of the map can reach."""
+centre of the map can reach.  Up to a reach of 20 cells the kernels read the same spiral packed into one word per entry."""
 import math
 import os
 import subprocess
@@ -106,3 +106,18 @@ def test_clip_and_oracle_walk(exe, oracle, cells, what):
             want = list(zip(di.tolist(), dj.tolist(), rg.tolist()))
             mine = [e for e in clipped["spiral"] if 0 <= ci + e[0] < rows and 0 <= cj + e[1] < cols]
             walk_matches(mine, want, (what, res, rows, cols, ci, cj))
+
+
+# reach <= 20: the packed words the kernels of those reaches read (fp_pack); whole-cell and Pythagorean tie radii included
+PACKED = [0.5, 1.0, 1.5, 2.0, 2.9, 5.0, 6.3, 9.000009, 10.0, 12.5, 13.0, 15.0, 16.000016, 17.0, 18.5, 19.7, 20.0, 20.99]
+
+
+@pytest.mark.parametrize("cells", PACKED)
+def test_packed_spiral_round_trips(exe, cells):
+    for res in RES:
+        n, reach, bad = (int(v) for v in subprocess.run([exe, "pack", repr(cells * res), repr(res)], capture_output=True, text=True,
+                                                         timeout=120, check=True).stdout.split())
+        assert reach <= 20 and bad == 0, (cells, res, reach, bad)
+        assert n == table(exe, cells * res, res, 1, 1, clip=False)["n_full"]
+        if cells in (5.0, 10.0, 13.0, 15.0, 17.0, 20.0):  # ties with both parts non-zero: the tie flag round-trips too
+            assert sum(e[3] for e in table(exe, cells * res, res, 1, 1, clip=False)["spiral"]) == 12

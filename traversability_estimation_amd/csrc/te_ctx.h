@@ -64,7 +64,7 @@ struct te_ctx {
   te::Layers L;
   size_t layer_elems = 0;
   void* slab = nullptr;
-  int16_t* d_spiral = nullptr;
+  uint32_t* d_spiral = nullptr;  // [kMaxSpiral]: the footprint spiral of reach <= 20, packed (fp_pack)
   int* clip_table = nullptr;
   int* fp_clip_table = nullptr;
   // the circular footprint at any reach (te_footprint_any.hip): its tables and its prefix-sum scratch, allocated when the

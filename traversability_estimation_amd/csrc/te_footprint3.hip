@@ -34,7 +34,7 @@ struct F3Args {
   // the part of the map this launch covers: block columns [bx0, bx0 + nbx_l), output rows [j_lo, j_hi), map (< 0: blockIdx.z)
   int bx0, nbx_l, j_lo, j_hi, map;
   int n_spiral;
-  const int16_t* table;  // [n_spiral][4]: di, dj, ring (integer norm), tie flag (never set here: tie-free discs only)
+  const unsigned* ptab;  // [n_spiral]: di | dj << 8 | ring << 16 | tie << 24 (fp_pack; no tie flag here: tie-free discs only)
   const int* gtab;       // clip table of the disc: {n, ...} per (ky, kx)
   double rmin, rmax, def, res;
   int inner_q;  // see the tail, step (0)
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(kLanes) __attribute__((amdgpu_waves_per_eu(kF3Waves
   constexpr int NTAB = (int)(3.2 * (R + 1) * (R + 1) / kLanes) + 1;  // >= cells of a disc of radius R + 1
   unsigned tabreg[NTAB];
   {
-    const unsigned* __restrict__ ptab0 = reinterpret_cast<const unsigned*>(a.table + 4 * kMaxSpiral);
+    const unsigned* __restrict__ ptab0 = a.ptab;
 #pragma unroll
     for (int ch = 0; ch < NTAB; ++ch) tabreg[ch] = ch * kLanes + lane < a.n_spiral ? ptab0[ch * kLanes + lane] : 0u;
   }
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(kLanes) __attribute__((amdgpu_waves_per_eu(kF3Waves
       // walk the spiral until the first untraversable cell :687-717; logical row j+dj sits dj+R rows below the
       // oldest row of the ring, which is row u of the chunk vb[0] points to.
       const int slot0 = (int)((__builtin_amdgcn_readfirstlane(vb[0])) / RB) + u;
-      const unsigned* __restrict__ ptab = reinterpret_cast<const unsigned*>(a.table + 4 * kMaxSpiral);  // packed entries
+      const unsigned* __restrict__ ptab = a.ptab;  // packed entries
       auto slot_of = [&](int dj) __attribute__((always_inline)) {
         int sl = slot0 + dj + R;
         sl = sl >= NR ? sl - NR : sl;
@@ -362,31 +362,21 @@ void launch_f3(const F3Args& a0, int batch, hipStream_t s) {
 
 }  // namespace
 
-// Shapes: every disc shape up to radius 10 (te_march.h) except the single cell, and for radii 11 .. 16 (the default
-// footprint, 0.45 m, is 15 cells at 0.03 m) every sum of two squares up to 256.  Compiled in TE_PARTS parts like
-// te_normals3.hip (build.py): part k instantiates its list and exports one launcher, part 0 also holds footprint_slide3.
-#define TE_F3_P0(X) X(4) X(16) X(26) X(37) X(50) X(65) X(73) X(85) X(100) X(121) X(136) X(148) X(162) X(178) X(193) X(202) X(212) X(229) X(256)
-#define TE_F3_P1(X) X(10) X(13) X(25) X(36) X(49) X(64) X(82) X(98) X(109) X(117) X(130) X(146) X(160) X(173) X(185) X(200) X(226) X(241) X(250)
-#define TE_F3_P2(X) X(9) X(20) X(34) X(45) X(58) X(61) X(81) X(97) X(106) X(116) X(128) X(145) X(157) X(170) X(181) X(197) X(225) X(234) X(245)
-#define TE_F3_P3(X) X(2) X(8) X(18) X(32) X(41) X(53) X(72) X(80) X(90) X(104) X(113) X(125) X(144) X(153) X(169) X(196) X(208) X(221) X(233) X(244)
-#define TE_F3_P4(X) X(1) X(5) X(17) X(29) X(40) X(52) X(68) X(74) X(89) X(101) X(122) X(137) X(149) X(164) X(180) X(194) X(205) X(218) X(232) X(242)
-#if !defined(TE_PARTS) || defined(TE_F3_SHAPES)
-#undef TE_PARTS
-#undef TE_PART
+// Shapes: TE_F3_P0 .. TE_F3_P4 (te_fp_route.h), compiled in TE_PARTS parts like te_normals3.hip (build.py): part k
+// instantiates its list and exports one launcher, part 0 also holds footprint_slide3.
+#ifndef TE_PARTS
 #define TE_PARTS 1
 #define TE_PART 0
 #endif
 #if TE_PARTS != 1 && TE_PARTS != 5
 #error "te_footprint3.hip is cut into 1 or 5 parts"
 #endif
-#ifndef TE_F3_SHAPES
 #if TE_PARTS == 1
 #define TE_F3_SHAPES(X) TE_F3_P0(X) TE_F3_P1(X) TE_F3_P2(X) TE_F3_P3(X) TE_F3_P4(X)
 #else
 #define TE_F3_CAT2(a, b) a##b
 #define TE_F3_CAT(a, b) TE_F3_CAT2(a, b)
 #define TE_F3_SHAPES(X) TE_F3_CAT(TE_F3_P, TE_PART)(X)
-#endif
 #endif
 #define TE_F3_NAME2(k) f3_launch_part##k
 #define TE_F3_NAME(k) TE_F3_NAME2(k)
@@ -423,15 +413,11 @@ int footprint_inner_q(double res, double rmin, double rmax) {
   return d < 0 ? -1 : (d + 1) * (d + 1) - 1;
 }
 
-// The sliding-sum kernel of the footprint pass for a tie-free disc of an instantiated shape; false: not taken.
-bool footprint_slide3(const Geo& g, const FootprintParams& p, const Layers& L, const int16_t* spiral_table, const int* clip_table,
-                      hipStream_t s, const Region* region) {
+// The sliding-sum kernel of the footprint pass for a tie-free disc on its route (plan_fp_route); false: the shape is not
+// instantiated.
+bool footprint_slide3(const Geo& g, const FootprintParams& p, const Layers& L, const unsigned* ptab, const int* clip_table, hipStream_t s,
+                      const Region* region) {
   const Disc& d = p.fp_disc;
-  static const bool off = lab_flag("TE_NO_F3");
-  if (off || d.n_ties != 0 || d.Q < 1 || d.R < 1 || p.reach != d.R || g.rows < kLanes || g.rows < 2 * d.R + 1 || g.cols < 2 * d.R + 1)
-    return false;
-  if ((double)g.rows * (double)g.cols * 4.0 >= 4294967296.0) return false;
-  if (p.n_spiral > ((int)(3.2 * (d.R + 1) * (d.R + 1) / kLanes) + 1) * kLanes) return false;  // the kernel's table registers
   F3Args a;
   a.trav = L.trav;
   a.untrav = L.untrav;
@@ -448,7 +434,7 @@ bool footprint_slide3(const Geo& g, const FootprintParams& p, const Layers& L, c
   a.map = region ? region->map : -1;
   if (a.j_hi <= a.j_lo || a.nbx_l <= 0) return true;
   a.n_spiral = p.n_spiral;
-  a.table = spiral_table;
+  a.ptab = ptab;
   a.gtab = clip_table;
   a.rmin = p.rmin;
   a.rmax = p.rmax;

@@ -45,8 +45,6 @@ namespace fast {
 
 namespace {
 
-constexpr int kF4Waves = 4;
-
 struct F4Args {
   const float* trav;
   const uint8_t* untrav;
@@ -69,7 +67,7 @@ struct F4Args {
   unsigned* blocked_count;  // ... [0] how many entries are reserved, [1] how many hold a cell (k_fp_mask resets both: it runs
                             // before this kernel in every footprint pass), [3] see k_fp_blocked
   int chunk;                // entries a block reserves at a time: kF4Chunk, less for strips shorter than four rows
-  size_t list_cap;          // entries the list holds (host side: launch_f4 refuses a grid whose unfinished chunks might not fit)
+  size_t list_cap;          // entries the list holds (host side: plan_fp_route refuses a grid whose unfinished chunks might not fit)
 };
 
 constexpr int f4_chunk_rows(int NR) {
@@ -414,40 +412,11 @@ __global__ __launch_bounds__(kLanes) __attribute__((amdgpu_waves_per_eu(kF4Waves
 }
 
 template <int Q>
-bool launch_f4(const F4Args& a0, int batch, hipStream_t s) {
-  F4Args a = a0;
-  constexpr int R = Shape<Q>::R;
-  static_assert(R * R == Q, "instantiated for the shapes a tie radius can have: its circle passes through (R, 0)");
-  if (a.n_ties == 0) return false;  // (tie-free discs: k_fp_slide5, or the double kernel -- footprint_slide4 does not ask)
-  // the kernel knows the circle's cells from R (axis cells + one Pythagorean triple): the disc's own table must say the same
-  if (a.n_gen != tie_triple_cells(R) || a.n_ties != 4 + a.n_gen) return false;
-  constexpr int lds = (2 * R + 2) * (kLanes + 2 * R) * 4;
-  int per_cu = (160 * 1024) / (((lds + 2047) / 2048) * 2048);  // see te_normals3.hip (resident_blocks)
-  if (per_cu > kF4Waves * 4) per_cu = kF4Waves * 4;
-  static const int per_cu_env = lab_int("TE_F4_BLOCKS_PER_CU", 0);  // measurement aid
-  if (per_cu_env > 0 && per_cu_env < kF4Waves * 4) per_cu = per_cu_env;
-  const int capacity = per_cu * device_cus();
+void launch_f4(const F4Args& a, int batch, hipStream_t s) {
+  static_assert(Shape<Q>::R * Shape<Q>::R == Q, "instantiated for the shapes a tie radius can have: its circle passes through (R, 0)");
   const int nz = a.map >= 0 ? 1 : (batch > 0 ? batch : 1);
-  const int H = a.j_hi - a.j_lo;
-  const int per_row = a.nbx_l * nz;
-  int strips = capacity / per_row;
-  strips = strips < 1 ? 1 : strips;
-  int sr = (H + strips - 1) / strips;
-  // small maps cannot fill the wave slots: every resident block runs at once, so the launch takes one warm-up plus the
-  // rows of one strip -- the shortest strips win (the spiral walks of a row are serial within its wavefront)
-  static const int min_strip = lab_int("TE_F4_MIN_STRIP", 1);
-  sr = sr < min_strip ? min_strip : (sr > 512 ? 512 : sr);
-  sr = sr < 1 ? 1 : sr;
-  a.strip_rows = sr;
-  a.chunk = sr >= 4 ? kF4Chunk : (sr * kLanes >= kF4Chunk / 2 ? kF4Chunk / 2 : kLanes);  // (a strip of one row lists at most 64 cells)
-  const int nstrips = (H + sr - 1) / sr;
-  // every listed cell takes one entry and every block may leave one chunk unfinished (closed chunks are full): the list
-  // must hold both, whatever the grid (strips clamped to 512 rows on a very tall map or a small device: more blocks
-  // than one round of resident ones).  false: the double kernel serves.
-  if ((double)a.nbx_l * (double)nstrips * (double)nz * (double)a.chunk + (double)a.map_cells * (double)nz > (double)a.list_cap) return false;
-  const dim3 grid((unsigned)(a.nbx_l * nstrips), 1, (unsigned)nz);
-  hipLaunchKernelGGL((k_fp_slide4<Q, true>), grid, dim3(kLanes), 0, s, a);
-  return true;
+  const int nstrips = (a.j_hi - a.j_lo + a.strip_rows - 1) / a.strip_rows;
+  hipLaunchKernelGGL((k_fp_slide4<Q, true>), dim3((unsigned)(a.nbx_l * nstrips), 1, (unsigned)nz), dim3(kLanes), 0, s, a);
 }
 
 }  // namespace
@@ -455,33 +424,7 @@ bool launch_f4(const F4Args& a0, int batch, hipStream_t s) {
 // Shapes: the whole-cell radii 1 .. 16 (Q = R^2), TIES march only.  Until round 5 the kernel was also instantiated for
 // every tie-free shape up to radius 16 (97 shapes x 2, five translation units): k_fp_slide5 has served those since round 4
 // (bit-identical results, 51 against 61 us on the bench map), and the one tie-free radius it does not take -- 16 cells --
-// goes to the double kernel like every unbounded layer.
-#define TE_F4_SHAPES_ALL(X) X(1) X(4) X(9) X(16) X(25) X(36) X(49) X(64) X(81) X(100) X(121) X(144) X(169) X(196) X(225) X(256)
-#undef TE_PARTS
-#undef TE_PART
-#define TE_PARTS 1
-#define TE_PART 0
-#ifndef TE_F4_SHAPES
-#define TE_F4_SHAPES(X) TE_F4_SHAPES_ALL(X)
-#endif
-#define TE_F4_NAME2(k) f4_launch_part##k
-#define TE_F4_NAME(k) TE_F4_NAME2(k)
-
-// launches shape Q if it belongs to this part (args: the F4Args block of part 0 -- the same struct in every part)
-bool TE_F4_NAME(TE_PART)(int Q, const void* args, int batch, hipStream_t s) {
-  const F4Args& a = *static_cast<const F4Args*>(args);
-  switch (Q) {
-#define X(q) \
-  case q:    \
-    return launch_f4<q>(a, batch, s);
-    TE_F4_SHAPES(X)
-#undef X
-    default:
-      return false;
-  }
-}
-
-#if TE_PART == 0
+// goes to the double kernel like every unbounded layer.  The list: TE_F4_SHAPES_ALL (te_fp_route.h).
 
 namespace {
 
@@ -744,22 +687,8 @@ __global__ __launch_bounds__(kLanes) void k_fp_blocked(FBArgs a) {
 
 }  // namespace
 
-// Entries of the list beyond one per cell: every block of k_fp_slide4 may leave one chunk unfinished, and a launch has
-// at most (resident blocks + one row of blocks) of them -- or, when the strips are clamped to 512 rows (a very tall
-// map, a small device), one block per 512 rows of every block column (launch_f4 checks the actual grid against it).
-size_t f4_list_slack(int rows, int cols, int batch) {
-  const size_t nbx = (size_t)(rows + kLanes - 1) / kLanes, nb = (size_t)(batch > 0 ? batch : 1);
-  const size_t one_round = (size_t)32 * (size_t)device_cus() + 2 * nbx * nb;  // (up to 8 waves per SIMD: k_fp_slide5 runs at 5)
-  const size_t clamped = nbx * nb * ((size_t)(cols + 511) / 512 + 1);
-  // k_fp_slide5 reserves 64 entries per row of EVERY block column, the shifted last one included (launch_f5's capacity test):
-  // a map whose rows are not a multiple of 64 needs the columns that block shares with its neighbour once more -- without them
-  // rows = 65 or 4033 failed the test and fell to the double kernel for no other reason (advisor, round 5)
-  const size_t shared = (nbx * (size_t)kLanes - (size_t)rows) * (size_t)cols * nb;
-  return (size_t)kF4Chunk * (one_round > clamped ? one_round : clamped) + shared;
-}
-
 // The second half of a footprint pass that used k_fp_slide4: the listed cells (see the header).
-void footprint_blocked4(const Geo& g, const FootprintParams& p, const Layers& L, const int16_t* spiral_table, hipStream_t s) {
+void footprint_blocked4(const Geo& g, const FootprintParams& p, const Layers& L, const unsigned* ptab, hipStream_t s) {
   if (p.rmin == 0.0) return;  // k_fp_slide4 wrote those cells itself (0)
   FBArgs a;
   a.trav = L.trav;
@@ -767,7 +696,7 @@ void footprint_blocked4(const Geo& g, const FootprintParams& p, const Layers& L,
   a.footprint = L.footprint;
   a.list = L.fp_blocked;
   a.count = L.fp_blocked_count;
-  a.ptab = reinterpret_cast<const unsigned*>(spiral_table + 4 * kMaxSpiral);
+  a.ptab = ptab;
   a.n_spiral = p.n_spiral;
   a.rows = g.rows;
   a.cols = g.cols;
@@ -785,32 +714,12 @@ void footprint_blocked4(const Geo& g, const FootprintParams& p, const Layers& L,
   hipLaunchKernelGGL(k_fp_blocked, dim3((unsigned)(per_cu * device_cus())), dim3(kLanes), 0, s, a);
 }
 
-// The fixed-point sliding-sum kernel of the footprint pass for a tie-free disc of an instantiated shape; false: not
-// taken.  tcap: upper bound of the finite values of the traversability layer, as the host can prove it (the layer was
-// written by the chain: w_scale * (w_slope + w_step + w_rough) with non-negative weights); < 0: unknown.
-bool footprint_slide4(const Geo& g, const FootprintParams& p, const Layers& L, const int16_t* spiral_table, const int* clip_table,
-                      double tcap, hipStream_t s, const Region* region, bool finish) {
+// The fixed-point sliding-sum kernel of the footprint pass for a whole-cell tie radius on the route r (plan_fp_route);
+// false: the shape is not instantiated.  The caller owes footprint_blocked4 for the listed cells where r.blocked.
+bool footprint_slide4(const Geo& g, const FootprintParams& p, const Layers& L, const int* clip_table, const FpRoute& r, hipStream_t s,
+                      const Region* region) {
   const Disc& d = p.fp_disc;
-  static const bool off = lab_flag("TE_NO_F4");
-  static const bool no_ties = lab_flag("TE_F4_NO_TIES");  // measurement aid: tie radii to the general kernel as before
-  // The shape the kernel slides: the disc itself, or for a tie radius the disc with its circle (whole-cell radii only:
-  // every cell on the circle has the norm reach^2, and the runs plus the circle are the shape reach^2).
-  if (d.n_ties == 0) return false;  // tie-free discs: k_fp_slide5 (te_footprint5.hip), else the double kernel
-  const int R = p.reach, shape = R * R;
-  if (no_ties) return false;
-  for (int t = 0; t < d.n_ties; ++t)
-    if ((int)d.tie_di[t] * d.tie_di[t] + (int)d.tie_dj[t] * d.tie_dj[t] != shape) return false;
-  if (off || shape < 1 || R < 1 || p.reach != R || g.rows < kLanes || g.rows < 2 * R + 1 || g.cols < 2 * R + 1) return false;
-  if ((double)g.rows * (double)g.cols * 4.0 >= 4294967296.0) return false;
-  // 32-bit list entries, and room for every block's unfinished chunk
-  if (!L.fp_blocked || !L.fp_blocked_count || (double)g.rows * (double)g.cols * (double)g.batch > (double)L.fp_blocked_cap) return false;
-  // the fixed-point scale: (2R+1) cells of at most cap * 2^k + 1/2 each must stay below 2^24 (the packed edge sums), and
-  // the default value that replaces NaN has to fit as well
-  if (!(tcap >= 0.0) || !(p.def >= 0.0)) return false;
-  const double cap = (tcap > p.def ? tcap : p.def) * (1.0 + 1e-6) + 1e-12;
-  int k = 23;
-  while (k >= 0 && (double)(2 * R + 1) * (cap * ldexp(1.0, k) + 1.0) >= 16777216.0) --k;
-  if (k < 17) return false;  // rounding each value to 2^-17 could show at the 1e-5 level: the double kernel serves
+  const int k = r.k;
   F4Args a;
   a.trav = L.trav;
   a.untrav = L.untrav;
@@ -819,7 +728,7 @@ bool footprint_slide4(const Geo& g, const FootprintParams& p, const Layers& L, c
   a.cols = g.cols;
   a.map_cells = (long long)g.rows * g.cols;
   a.nbx = (g.rows + kLanes - 1) / kLanes;
-  a.strip_rows = 0;
+  a.strip_rows = r.strip_rows;
   a.bx0 = region ? region->i0 / kLanes : 0;
   a.nbx_l = region ? (region->i1 - 1) / kLanes - a.bx0 + 1 : a.nbx;
   a.j_lo = region ? region->j0 : 0;
@@ -841,12 +750,19 @@ bool footprint_slide4(const Geo& g, const FootprintParams& p, const Layers& L, c
   a.inv_scale = ldexp(1.0, -k);
   a.blocked_list = L.fp_blocked;
   a.blocked_count = L.fp_blocked_count;
+  a.chunk = r.chunk;
   a.list_cap = L.fp_blocked_cap;
-  const bool launched = f4_launch_part0(shape, &a, g.batch, s);
-  if (launched && finish) footprint_blocked4(g, p, L, spiral_table, s);
-  return launched;
+  switch (p.reach * p.reach) {
+#define X(q)                     \
+  case q:                        \
+    launch_f4<q>(a, g.batch, s); \
+    return true;
+    TE_F4_SHAPES_ALL(X)
+#undef X
+    default:
+      return false;
+  }
 }
-#endif  // TE_PART == 0
 
 }  // namespace fast
 }  // namespace te

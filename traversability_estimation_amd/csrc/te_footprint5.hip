@@ -28,9 +28,6 @@ namespace fast {
 
 namespace {
 
-constexpr int kF5Waves = 5;
-constexpr int kF5UBit = 27;
-
 struct F5Args {
   const float* trav;
   const uint8_t* untrav;
@@ -48,7 +45,7 @@ struct F5Args {
   unsigned* blocked_count;  // ... [0] entries of the list, [1] entries that hold a cell, [4] entries of the scratch reserved (k_fp_mask resets them)
   unsigned* scratch;        // where a block collects its cells until its strip is done (Layers::fp_scratch)
   int chunk;                // granule of the scratch reservations
-  size_t list_cap;          // (host side: the launcher refuses a grid whose unfinished chunks might not fit)
+  size_t list_cap;          // (host side: plan_fp_route refuses a grid whose unfinished chunks might not fit)
   // one byte per 64 x 4 cells, written by k_fp_mask: "holds an untraversable cell" (Layers::untrav_flags).  A strip whose
   // flags are all clear -- on terrain without obstacles every strip -- does not fetch its mask bytes: the byte loads stay
   // in the instruction stream, but their descriptor is given zero records, and a raw buffer load beyond its records
@@ -348,53 +345,29 @@ __global__ __launch_bounds__(kLanes) __attribute__((amdgpu_waves_per_eu(kF5Waves
 }
 
 template <int Q>
-bool launch_f5(const F5Args& a0, int batch, hipStream_t s) {
-  F5Args a = a0;
-  constexpr int R = Shape<Q>::R;
-  static_assert(2 * R + 1 <= 31, "a run sum of 2R+1 cells with the untraversable flag at bit 27 must fit 32 bits");
-  static const int waves_env = lab_int("TE_F5_WAVES", 0);  // measurement aid: strips sized for this many waves per SIMD
-  const int capacity = (waves_env > 0 ? waves_env : kF5Waves) * 4 * device_cus();
+void launch_f5(const F5Args& a, int batch, hipStream_t s) {
+  static_assert(2 * Shape<Q>::R + 1 <= 31, "a run sum of 2R+1 cells with the untraversable flag at bit 27 must fit 32 bits");
   const int nz = a.map >= 0 ? 1 : (batch > 0 ? batch : 1);
-  const int H = a.j_hi - a.j_lo;
-  static const int max_strip = lab_int("TE_F5_MAX_STRIP", 512);
-  a.strip_rows = plan_strip_rows(H, (long)a.nbx_l * nz, capacity, max_strip > 0 ? max_strip : 512);
-  const int sr = a.strip_rows;
-  a.chunk = sr >= 4 ? kF4Chunk : (sr * kLanes >= kF4Chunk / 2 ? kF4Chunk / 2 : kLanes);  // (a strip of one row lists at most 64 cells)
-  const int nstrips = (H + sr - 1) / sr;
-  // a block reserves at most its own cells rounded up to whole pages
-  // (64 entries per row of every block -- a shifted last block reserves for the columns it shares with its neighbour too)
-  if ((double)a.nbx_l * (double)nz * ((double)H * (double)kLanes + (double)nstrips * (double)a.chunk) > (double)a.list_cap) return false;
-  const dim3 grid((unsigned)(a.nbx_l * nstrips), 1, (unsigned)nz);
-  hipLaunchKernelGGL((k_fp_slide5<Q>), grid, dim3(kLanes), 0, s, a);
-  return true;
+  const int nstrips = (a.j_hi - a.j_lo + a.strip_rows - 1) / a.strip_rows;
+  hipLaunchKernelGGL((k_fp_slide5<Q>), dim3((unsigned)(a.nbx_l * nstrips), 1, (unsigned)nz), dim3(kLanes), 0, s, a);
 }
 
 }  // namespace
 
-// Shapes: every disc shape up to radius 10 (te_march.h) except the single cell, and for radii 11 .. 15 every sum of two
-// squares below 256.  Compiled in TE_PARTS parts like te_footprint4.hip (build.py).
-#define TE_F5_P0(X) X(4) X(16) X(26) X(37) X(50) X(65) X(73) X(85) X(100) X(121) X(136) X(148) X(162) X(178) X(193) X(202) X(212) X(229)
-#define TE_F5_P1(X) X(10) X(13) X(25) X(36) X(49) X(64) X(82) X(98) X(109) X(117) X(130) X(146) X(160) X(173) X(185) X(200) X(226) X(241) X(250)
-#define TE_F5_P2(X) X(9) X(20) X(34) X(45) X(58) X(61) X(81) X(97) X(106) X(116) X(128) X(145) X(157) X(170) X(181) X(197) X(225) X(234) X(245)
-#define TE_F5_P3(X) X(2) X(8) X(18) X(32) X(41) X(53) X(72) X(80) X(90) X(104) X(113) X(125) X(144) X(153) X(169) X(196) X(208) X(221) X(233) X(244)
-#define TE_F5_P4(X) X(1) X(5) X(17) X(29) X(40) X(52) X(68) X(74) X(89) X(101) X(122) X(137) X(149) X(164) X(180) X(194) X(205) X(218) X(232) X(242)
-#if !defined(TE_PARTS) || defined(TE_F5_SHAPES)
-#undef TE_PARTS
-#undef TE_PART
+// Shapes: TE_F5_P0 .. TE_F5_P4 (te_fp_route.h), compiled in TE_PARTS parts like te_footprint3.hip (build.py).
+#ifndef TE_PARTS
 #define TE_PARTS 1
 #define TE_PART 0
 #endif
 #if TE_PARTS != 1 && TE_PARTS != 5
 #error "te_footprint5.hip is cut into 1 or 5 parts"
 #endif
-#ifndef TE_F5_SHAPES
 #if TE_PARTS == 1
 #define TE_F5_SHAPES(X) TE_F5_P0(X) TE_F5_P1(X) TE_F5_P2(X) TE_F5_P3(X) TE_F5_P4(X)
 #else
 #define TE_F5_CAT2(a, b) a##b
 #define TE_F5_CAT(a, b) TE_F5_CAT2(a, b)
 #define TE_F5_SHAPES(X) TE_F5_CAT(TE_F5_P, TE_PART)(X)
-#endif
 #endif
 #define TE_F5_NAME2(k) f5_launch_part##k
 #define TE_F5_NAME(k) TE_F5_NAME2(k)
@@ -403,9 +376,10 @@ bool launch_f5(const F5Args& a0, int batch, hipStream_t s) {
 bool TE_F5_NAME(TE_PART)(int Q, const void* args, int batch, hipStream_t s) {
   const F5Args& a = *static_cast<const F5Args*>(args);
   switch (Q) {
-#define X(q) \
-  case q:    \
-    return launch_f5<q>(a, batch, s);
+#define X(q)                   \
+  case q:                      \
+    launch_f5<q>(a, batch, s); \
+    return true;
     TE_F5_SHAPES(X)
 #undef X
     default:
@@ -421,30 +395,12 @@ bool f5_launch_part3(int Q, const void* args, int batch, hipStream_t s);
 bool f5_launch_part4(int Q, const void* args, int batch, hipStream_t s);
 #endif
 
-// The scatter-form sum kernel of the footprint pass for a tie-free disc of an instantiated shape; false: not taken
-// (the caller tries k_fp_slide4, then the double kernel).  tcap: upper bound of the finite values of the traversability
-// layer, as the host can prove it (the layer was written by the chain: w_scale * (w_slope + w_step + w_rough) with
-// non-negative weights); < 0: unknown.  On success the caller still owes footprint_blocked4 (finish = false) for the
-// listed cells.
-bool footprint_slide5(const Geo& g, const FootprintParams& p, const Layers& L, const int* clip_table, double tcap, hipStream_t s,
-                      const Region* region, bool* needs_blocked) {
+// The scatter-form sum kernel of the footprint pass for a tie-free disc on the route r (plan_fp_route); false: the shape
+// is not instantiated.  The caller owes footprint_blocked4 for the listed cells where r.blocked.
+bool footprint_slide5(const Geo& g, const FootprintParams& p, const Layers& L, const int* clip_table, const FpRoute& r, hipStream_t s,
+                      const Region* region) {
   const Disc& d = p.fp_disc;
-  static const bool off = lab_flag("TE_NO_F5");  // measurement aid: k_fp_slide4 as in round 3
-  if (off || d.n_ties != 0) return false;
-  const int shape = d.Q, R = d.R;
-  if (shape < 1 || R < 1 || 2 * R + 1 > 31 || p.reach != R || g.rows < kLanes || g.rows < 2 * R + 1 || g.cols < 2 * R + 1) return false;
-  if ((double)g.rows * (double)g.cols * 4.0 >= 4294967296.0) return false;  // 32-bit list entries and byte offsets within a pass
-  if (!L.fp_blocked || !L.fp_scratch || !L.fp_blocked_count || (double)g.rows * (double)g.cols * (double)g.batch > (double)L.fp_blocked_cap) return false;
-  // the fixed-point scale: the T-sum of a whole disc (npoints cells of at most cap * 2^k + 1/2 each) must stay below
-  // 2^27 -- the untraversable flag's bit -- and the default value that replaces NaN has to fit as well
-  if (!(tcap >= 0.0) || !(p.def >= 0.0)) return false;
-  // (the march loads rows beyond the layers it is given, te_internal.h; the mask bytes are a quarter of a float layer's
-  // rows in bytes, so the float test of the mask's own rows is the stricter one)
-  if (!layer_has_guard_rows(L.trav, g, sizeof(float)) || !layer_has_guard_rows(L.untrav, g, sizeof(uint8_t))) return false;
-  const double cap = (tcap > p.def ? tcap : p.def) * (1.0 + 1e-6) + 1e-12;
-  int k = 23;
-  while (k >= 0 && (double)d.npoints * (cap * ldexp(1.0, k) + 1.0) >= (double)(1u << kF5UBit)) --k;
-  if (k < 17) return false;  // rounding each value to 2^-17 could show at the 1e-5 level: the double kernel serves
+  const int k = r.k, R = d.R;
   F5Args a;
   a.trav = L.trav;
   a.untrav = L.untrav;
@@ -452,14 +408,13 @@ bool footprint_slide5(const Geo& g, const FootprintParams& p, const Layers& L, c
   a.rows = g.rows;
   a.cols = g.cols;
   a.map_cells = (long long)g.rows * g.cols;
-  a.strip_rows = 0;
+  a.strip_rows = r.strip_rows;
   const int nbx = (g.rows + kLanes - 1) / kLanes;
   a.bx0 = region ? region->i0 / kLanes : 0;
   a.nbx_l = region ? (region->i1 - 1) / kLanes - a.bx0 + 1 : nbx;
   a.j_lo = region ? region->j0 : 0;
   a.j_hi = region ? region->j1 : g.cols;
   a.map = region ? region->map : -1;
-  *needs_blocked = false;
   if (a.j_hi <= a.j_lo || a.nbx_l <= 0) return true;
   a.gtab = clip_table;
   a.rmin = p.rmin;
@@ -494,17 +449,16 @@ bool footprint_slide5(const Geo& g, const FootprintParams& p, const Layers& L, c
   a.blocked_list = L.fp_blocked;
   a.blocked_count = L.fp_blocked_count;
   a.scratch = L.fp_scratch;
-  a.chunk = kF4Chunk;
+  a.chunk = r.chunk;
   a.list_cap = L.fp_blocked_cap;
   a.untrav_flags = L.untrav_flags;
   a.flag_ntx = untrav_flag_ntx(g.rows);
   a.flag_nfy = untrav_flag_nfy(g.cols);
-  bool launched = f5_launch_part0(shape, &a, g.batch, s);
+  bool launched = f5_launch_part0(d.Q, &a, g.batch, s);
 #if TE_PARTS > 1
-  launched = launched || f5_launch_part1(shape, &a, g.batch, s) || f5_launch_part2(shape, &a, g.batch, s) || f5_launch_part3(shape, &a, g.batch, s) ||
-             f5_launch_part4(shape, &a, g.batch, s);
+  launched = launched || f5_launch_part1(d.Q, &a, g.batch, s) || f5_launch_part2(d.Q, &a, g.batch, s) || f5_launch_part3(d.Q, &a, g.batch, s) ||
+             f5_launch_part4(d.Q, &a, g.batch, s);
 #endif
-  *needs_blocked = launched;
   return launched;
 }
 #endif  // TE_PART == 0

@@ -8,6 +8,7 @@
 
 #include <vector>
 
+#include "te_fp_route.h"
 #include "travgpu.h"
 
 namespace te {
@@ -148,7 +149,7 @@ struct Layers {
                                // in a listed disc, [4] entries of the scratch reserved (k_fp_mask resets [0], [1], [4])
   unsigned* fp_scratch;        // k_fp_slide5 collects a block's cells here (one reservation per block, sized for its whole strip) and copies
                                // them to the list when the strip is done: the list stays dense whatever the reservations
-  size_t fp_blocked_cap;       // entries the list holds (cells + fast::f4_list_slack)
+  size_t fp_blocked_cap;       // entries the list holds (cells + fast::fp_list_slack)
   int* block_flags;    // one flag per block of the shape-specialised normals kernel ("needs the fix-up pass")
   uint8_t* untrav_flags;  // one byte per 64 x 4 cells: "holds an untraversable cell" as of the mask kernel's last pass over them (1 until then);
                           // k_fp_slide5 does not fetch the mask bytes of a strip whose flags are all clear
@@ -305,11 +306,12 @@ hipError_t launch_filter(const Geo& g, const ChainParams& p, const Layers& L, in
                          hipStream_t stream);
 hipError_t launch_chain(const Geo& g, const ChainParams& p, const Layers& L, const Region& r, unsigned flags,
                         hipStream_t stream);
-// spiral_table: [n_spiral][4] int16 {di, dj, ring, tie}; clip_table: build_clip_table(fp_disc, reach)
-// trav_cap: upper bound of the finite traversability values if the layer was written by the chain (see footprint_slide4), else < 0
+// ptab: [n_spiral] packed spiral entries (fp_pack); clip_table: build_clip_table(fp_disc, reach)
+// trav_cap: upper bound of the finite traversability values if the layer was written by the chain, else < 0
 // region (nullptr: all maps, all cells): the cells whose scores changed; the mask is recomputed within 3 cells of them
-// and the footprint within the footprint's reach of those (a footprint shape only the general kernel serves: on every cell)
-hipError_t launch_footprint(const Geo& g, const FootprintParams& p, const Layers& L, const int16_t* spiral_table,
+// and the footprint within the footprint's reach of those (a footprint shape only the general kernel serves: on every cell).
+// The sum kernels are chosen by plan_fp_route (te_fp_route.h); a planned route without its instantiation is an error.
+hipError_t launch_footprint(const Geo& g, const FootprintParams& p, const Layers& L, const unsigned* ptab,
                             const int* clip_table, bool write_memo, const ChainParams* combine, double trav_cap, hipStream_t stream,
                             const Region* region = nullptr);
 // te_footprint_any.hip: the sum of the circular footprint pass at any reach (the mask kernel has run); rf: the output
@@ -364,28 +366,22 @@ bool normals_small(const Geo& g, const ChainParams& p, const Layers& L, bool kee
 bool chain_window(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, const Region& r, bool combine, hipStream_t s);
 int normals_fast_max_blocks(const Geo& g);
 size_t normals_hole_queue_bytes();  // te_normals3.hip: scratch of the sparse-hole march for one device (any map, any batch)
-// te_footprint3.hip: the sliding-sum kernel of the circular footprint pass (false: shape / map not taken)
-// region: the output cells to compute (whole block columns and the rows [j0, j1) of map `map`); nullptr: every map, every cell
-bool footprint_slide3(const Geo& g, const FootprintParams& p, const Layers& L, const int16_t* spiral_table, const int* clip_table,
-                      hipStream_t s, const Region* region = nullptr);
-// te_footprint4.hip: the same on 32-bit fixed point, when the values of the traversability layer are bounded by tcap
-// (tcap < 0: no bound known)
-bool footprint_slide4(const Geo& g, const FootprintParams& p, const Layers& L, const int16_t* spiral_table, const int* clip_table,
-                      double tcap, hipStream_t s, const Region* region = nullptr, bool finish = true);
-// te_footprint5.hip: the same sum in scatter form (tie-free discs up to 15 cells); *needs_blocked: the caller owes
-// footprint_blocked4 for the listed cells (after every launch of the pass)
-bool footprint_slide5(const Geo& g, const FootprintParams& p, const Layers& L, const int* clip_table, double tcap, hipStream_t s,
-                      const Region* region, bool* needs_blocked);
+// The sum kernels of the circular footprint pass, each on the route plan_fp_route chose for it (false: the shape is not
+// instantiated).  region: the output cells to compute (whole block columns and the rows [j0, j1) of map `map`); nullptr:
+// every map, every cell.  te_footprint5.hip: the scatter-form sum on fixed point (tie-free discs up to 15 cells);
+// te_footprint4.hip: the sliding sum on fixed point (whole-cell tie radii); te_footprint3.hip: the sliding sum in double.
+bool footprint_slide5(const Geo& g, const FootprintParams& p, const Layers& L, const int* clip_table, const FpRoute& r, hipStream_t s,
+                      const Region* region);
+bool footprint_slide4(const Geo& g, const FootprintParams& p, const Layers& L, const int* clip_table, const FpRoute& r, hipStream_t s,
+                      const Region* region);
+bool footprint_slide3(const Geo& g, const FootprintParams& p, const Layers& L, const unsigned* ptab, const int* clip_table, hipStream_t s,
+                      const Region* region);
 constexpr int kClipInts = 6 * (2 * kMaxRadiusCells + 1) * (2 * kMaxRadiusCells + 1);  // one clip table of the normals disc; for a tie radius the
                                                                                       // table of the disc with its circle follows, then the packed offsets
 constexpr int kFpClipInts = 6 * 41 * 41;  // one clip table of the footprint disc (reach <= 20); a second one follows it for a tie
                                            // radius: the disc with the cells on its circle (k_fp_slide4<Q, true>)
-constexpr int kF4Chunk = 256;              // entries of the list a block reserves at a time
-constexpr unsigned kF4NoCell = 0xffffffffu;  // an unused entry
-size_t f4_list_slack(int rows, int cols, int batch);
-// ... its second half: the cells whose disc holds an untraversable cell (finish = false above: the caller runs it, after
-// every k_fp_slide4 launch of the pass has completed)
-void footprint_blocked4(const Geo& g, const FootprintParams& p, const Layers& L, const int16_t* spiral_table, hipStream_t s);
+// the second half of a fixed-point pass (FpRoute::blocked): the listed cells, after every launch of the pass
+void footprint_blocked4(const Geo& g, const FootprintParams& p, const Layers& L, const unsigned* ptab, hipStream_t s);
 void build_clip_table(const Disc& d, int Rk, int* out);  // (2*Rk+1)^2 * 6 ints, clip codes relative to radius Rk
 }  // namespace fast
 

@@ -21,6 +21,7 @@
 // The kernel-specific part is a policy K (see te_step5.hip, te_footprint5.hip).
 #pragma once
 #include "te_march.h"
+#include "te_strips.h"
 
 namespace te {
 namespace fast {
@@ -166,17 +167,6 @@ __device__ __forceinline__ void march5(K& k, const int js, const int jend) {
   // those paths arrives there as v_readfirstlane of an UNDEFINED vector register -- the allocator picks one with a load
   // in flight, and every other pass waits for that load)
   asm volatile("" ::"s"(r));
-}
-
-// Rows per strip such that (column blocks x maps x strips) fills `slots` resident waves in one round (at least 1 row;
-// more than max_rows per strip gains nothing and keeps short maps from waiting on one long strip)
-inline int plan_strip_rows(int rows, long columns, long slots, int max_rows = 512) {
-  long strips = slots / (columns > 0 ? columns : 1);
-  if (strips < 1) strips = 1;
-  long per = (rows + strips - 1) / strips;
-  if (per > max_rows) per = max_rows;
-  if (per < 1) per = 1;
-  return (int)per;
 }
 
 __device__ __forceinline__ float canon_nan(float x) {  // finite x -> x (exactly), +-inf / NaN -> NaN

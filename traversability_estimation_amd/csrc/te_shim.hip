@@ -357,74 +357,22 @@ int rebuild_footprint_tables_impl(te_ctx* c) {
       return build_fp_any_tables(c, any);
     }
     if ((rc = build_disc(f.rmax, res, &f.fp_disc, "footprint"))) return rc;
-    // SpiralIterator order (grid_map_core): centre, then ring d = 1..nRings, each generated by a perimeter
-    // walk from (d, 0) and consumed from the back; only the two outer rings are tested against the circle.
     const Disc& d = f.fp_disc;
-    const unsigned nrings = (unsigned)ceil(f.rmax / res);
-    std::vector<int16_t> tab;
-    auto tie_of = [&](int di, int dj) {
-      for (int t = 0; t < d.n_ties; ++t)
-        if (d.tie_di[t] == di && d.tie_dj[t] == dj) return true;
-      return false;
-    };
-    auto in_runs = [&](int di, int dj) {
-      const int ai = di < 0 ? -di : di, aj = dj < 0 ? -dj : dj;
-      return aj <= d.R && d.R >= 0 && d.hw[aj] >= 0 && ai <= d.hw[aj];
-    };
-    auto push = [&](int di, int dj, bool tie) {
-      tab.push_back((int16_t)di);
-      tab.push_back((int16_t)dj);
-      tab.push_back((int16_t)(int)sqrt((double)(di * di + dj * dj)));  // getCurrentRadius(): integer norm
-      tab.push_back((int16_t)(tie ? 1 : 0));
-    };
-    push(0, 0, false);
-    int reach = 0;
-    for (unsigned dist = 1; dist <= nrings && dist <= (unsigned)kMaxRadiusCells + 1; ++dist) {
-      std::vector<int> ring;
-      int px = (int)dist, py = 0;
-      do {
-        bool keep = true, tie = false;
-        if (dist == nrings || dist + 1 == nrings) {
-          tie = tie_of(px, py);
-          keep = tie || in_runs(px, py);
-        }
-        if (keep) {
-          ring.push_back(px);
-          ring.push_back(py);
-          ring.push_back(tie ? 1 : 0);
-        }
-        const int nx = -((py > 0) - (py < 0)), ny = (px > 0) - (px < 0);
-        if (nx != 0 && (unsigned)sqrt((double)(px + nx) * (px + nx) + (double)py * py) == dist)
-          px += nx;
-        else if (ny != 0 && (unsigned)sqrt((double)px * px + (double)(py + ny) * (py + ny)) == dist)
-          py += ny;
-        else {
-          px += nx;
-          py += ny;
-        }
-      } while ((unsigned)px != dist || py != 0);
-      for (int k = (int)ring.size() / 3 - 1; k >= 0; --k) {
-        push(ring[3 * k], ring[3 * k + 1], ring[3 * k + 2] != 0);
-        const int ax = abs(ring[3 * k]), ay = abs(ring[3 * k + 1]);
-        reach = ax > reach ? ax : reach;
-        reach = ay > reach ? ay : reach;
-      }
-    }
-    f.n_spiral = (int)tab.size() / 4;
-    f.reach = reach < 1 ? 1 : reach;
+    // the same spiral unclipped (the kernels clip it per centre), one packed word per entry: the kernels' spiral walks read
+    // it with scalar loads, eight entries at a time
+    FpTable sp;
+    build_fp_table(f.rmax, res, c->geo.rows, c->geo.cols, &sp, false);
+    f.n_spiral = (int)sp.spiral.size();
+    f.reach = sp.reach;
     if (f.reach > 20 || f.n_spiral > kMaxSpiral)  // (a reach above 20 cells took the route of any reach above)
       return fail(TE_ERR_UNSUPPORTED, "footprint radius %.3g m is %d cells: internal routing error", f.rmax, f.reach);
+    std::vector<uint32_t> packed(f.n_spiral);
+    for (int k = 0; k < f.n_spiral; ++k) packed[k] = fp_pack(sp.spiral[k]);
     std::vector<int> ctab((size_t)(2 * f.reach + 1) * (2 * f.reach + 1) * 6);
     fast::build_clip_table(d, f.reach, ctab.data());
     HIP_TRY(hipSetDevice(c->device));
-    // the int16 table, followed by the same entries packed into one word each (di | dj << 8 | ring << 16 | tie << 24):
-    // the kernels' spiral walk reads those with scalar loads, eight entries at a time
-    if (!c->d_spiral) HIP_TRY(hipMalloc((void**)&c->d_spiral, sizeof(int16_t) * 4 * kMaxSpiral + sizeof(uint32_t) * kMaxSpiral));
-    std::vector<uint32_t> packed(f.n_spiral);
-    for (int k = 0; k < f.n_spiral; ++k)
-      packed[k] = ((uint32_t)tab[4 * k] & 0xffu) | (((uint32_t)tab[4 * k + 1] & 0xffu) << 8) | (((uint32_t)tab[4 * k + 2] & 0xffu) << 16) |
-                  (((uint32_t)tab[4 * k + 3] & 0xffu) << 24);
-    HIP_TRY(hipMemcpyAsync(c->d_spiral + 4 * kMaxSpiral, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (!c->d_spiral) HIP_TRY(hipMalloc((void**)&c->d_spiral, sizeof(uint32_t) * kMaxSpiral));
+    HIP_TRY(hipMemcpyAsync(c->d_spiral, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     if (!c->fp_clip_table) HIP_TRY(hipMalloc((void**)&c->fp_clip_table, sizeof(int) * (2 * fast::kFpClipInts + kMaxTies)));
     std::vector<int> ctab_full;
     int gen_tab[kMaxTies];
@@ -444,7 +392,6 @@ int rebuild_footprint_tables_impl(te_ctx* c) {
         if (d.tie_di[t] != 0 && d.tie_dj[t] != 0) gen_tab[n_gen++] = ((int)d.tie_di[t] & 0xff) | (((int)d.tie_dj[t] & 0xff) << 8);
       if (n_gen) HIP_TRY(hipMemcpyAsync(c->fp_clip_table + 2 * fast::kFpClipInts, gen_tab, n_gen * sizeof(int), hipMemcpyHostToDevice, c->stream));
     }
-    HIP_TRY(hipMemcpyAsync(c->d_spiral, tab.data(), tab.size() * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->fp_clip_table, ctab.data(), ctab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (f.any) return build_fp_any_tables(c, any);  // TE_OPT_FP_ANY_REACH
@@ -972,7 +919,7 @@ int te_set_geometry(te_ctx* c, int rows, int cols, int batch, double res, double
     const size_t fb = ((size_t)fast::normals_fast_max_blocks(gtmp) * sizeof(int) + 255) & ~(size_t)255;
     // (+ the footprint pass's list of cells with an untraversable cell in their disc: one 32-bit entry per cell at
     // most, and its counter)
-    const size_t list_cap = elems + fast::f4_list_slack(rows, cols, batch);
+    const size_t list_cap = elems + fast::fp_list_slack(rows, cols, batch, device_cus());
     const size_t qb = (list_cap * sizeof(unsigned) + 255) & ~(size_t)255;
     // (guard: kSlabGuardRows rows of slack before the first and behind the last layer -- te_internal.h)
     const size_t guard = ((size_t)kSlabGuardRows * (size_t)rows * sizeof(float) + 255) & ~(size_t)255;
