@@ -70,7 +70,8 @@ typedef enum te_status {
   TE_ERR_NOT_READY = -3,   /* geometry/params/elevation missing, or chain not run before footprint */
   TE_ERR_HIP = -4,         /* HIP runtime error (message has hipGetErrorString) */
   TE_ERR_NO_DEVICE = -5,   /* no usable gfx950 device: the library never falls back to the CPU */
-  TE_ERR_UNSUPPORTED = -6  /* a filter radius above 32 cells (the on-chip tile); a circular footprint only when its tables do not fit in device memory */
+  TE_ERR_UNSUPPORTED = -6  /* a filter disc above 32 cells or with more than 32 offsets on its circle, under TE_OPT_FILTER_ANY_RADIUS = 0 (the
+                              default); under 1 or 2, and for a circular footprint, only tables that do not fit in device memory */
 } te_status;
 
 /* Layers owned by a context (device-resident, [batch][cols][rows] float32). */
@@ -172,6 +173,14 @@ int te_get_params(te_ctx* ctx, te_params* p);
 #define TE_OPT_BCAST_RCCL 5               /* te_bcast_params, set on the ROOT context: 0 RCCL only between different devices (the default), 1 also when all contexts share one device (a communicator of one rank) */
 #define TE_OPT_FP_ANY_REACH 7             /* circular footprint pass: 0 (default) by reach -- up to 20 cells the shape-specialised sum kernels, above 20 the route of any reach; 1 the route of any reach for every footprint */
 #define TE_OPT_NORMALS_RANK_RULE 6        /* 1: NormalVectorsFilter as grid_map <= 1.6 had it (the filter that wrote TE/maps/elevation_map.bag): a disc whose scatter matrix is rank-deficient -- exactly planar -- gets UnitZ; runs the shape-generic kernels.  0 (default): the current area method */
+/* Filter discs (normals, roughness, step windows) of any radius, per context:
+ *   0 (default) a disc above 32 cells, or with more than 32 offsets on its circle, is refused with TE_ERR_UNSUPPORTED;
+ *   1 any radius: the discs the shape kernels hold keep their routes bit for bit, larger ones take te_filter_any.hip;
+ *   2 that route for every filter disc (tests and A/B timing).
+ * Takes effect at once when parameters and geometry are held (the discs are rebuilt); if they cannot be -- going back to 0
+ * while a 40-cell radius is held -- TE_ERR_UNSUPPORTED, and the option and the discs stay as they were.  te_bcast_params
+ * carries parameters only: each receiving context needs the option set as well.  The C++ plugins set 1. */
+#define TE_OPT_FILTER_ANY_RADIUS 8
 int te_set_option(te_ctx* ctx, int option, int value);
 /* rows = size(0), cols = size(1) of every map of the batch; (pos_x,pos_y) = map centre. */
 int te_set_geometry(te_ctx* ctx, int rows, int cols, int batch, double resolution, double pos_x, double pos_y);

@@ -28,6 +28,7 @@ RUN_SEQUENTIAL = 0x10
 RUN_NORMALS_ONLY = 0x20
 OPT_FP_BLOCKED_WALK, OPT_FP_BLOCKED_BLOCKS_PER_CU, OPT_POLYGON_PER_CELL, OPT_GRAPH_REPLAY, OPT_BCAST_RCCL, OPT_NORMALS_RANK_RULE = 1, 2, 3, 4, 5, 6
 OPT_FP_ANY_REACH = 7  # circular footprint: 0 routes by reach (above 20 cells: the route of any reach), 1 that route always
+OPT_FILTER_ANY_RADIUS = 8  # filter discs: 0 up to 32 cells (TE_ERR_UNSUPPORTED above), 1 any radius, 2 the route of any radius for every disc
 
 # every symbol include/travgpu.h declares (tests/test_cabi.py checks the library exports them all)
 SYMBOLS = ["te_params_default", "te_params_validate", "te_device_count", "te_create", "te_destroy",

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include <cstdlib>
+#include "te_disc_table.h"
 #include "te_internal.h"
 #include "te_msg.h"
 
@@ -84,6 +85,13 @@ struct te_ctx {
   // te_set_option: choices between kernels that give identical results (tests reach both; never read from the environment)
   int opt_fb_walk = 0, opt_fb_blocks_per_cu = 0, opt_polygon_per_cell = 0, opt_graph = 0, opt_bcast_rccl = 0, opt_rank_rule = 0,
       opt_fp_any = 0;
+  // TE_OPT_FILTER_ANY_RADIUS (0: discs above 32 cells refused, 1: those take te_filter_any.hip, 2: every disc does), the host
+  // tables of the filter discs that route takes (normals, roughness, step windows 1 and 2) and their device copy, uploaded
+  // by rebuild_tables (never inside a launch: whole-map launches are captured)
+  int opt_filter_any = 0;
+  te::DiscTable fa_host[4];
+  void* fa_tab = nullptr;
+  size_t fa_tab_bytes = 0;
   // invalid cells of the elevation layer as of the last whole upload (-1: unknown -- tiles, device pointer): see sparse_holes()
   long long invalid_cells = -1;
   long long invalid_runs = -1;  // runs of invalid cells in memory order (k_count_invalid); meaningful with invalid_cells >= 0

@@ -274,6 +274,7 @@ bool step_height_ties(const Disc& d, const Geo& g, const float* elev, float* sh,
   TieArgs t;
   SmallWin w;
   static const bool no_small = lab_flag("TE_STEP_NO_SMALL");
+  if (d.any) return false;  // (te_filter_any.hip)
   if (!off && !no_small && d.n_ties != 0 && small_window(-1, &d, &w)) {  // a tie radius of one or two cells
     hipLaunchKernelGGL(k_step_small<false>, small_grid(g, r), dim3(kLanes, 4), 0, s, g, w, 0.0, 0.0f, 1, elev, sh, r);
     return true;
@@ -302,6 +303,7 @@ bool step_score_ties(const Disc& d, const Geo& g, double crit, int ncrit, const 
   TieArgs t;
   SmallWin w;
   static const bool no_small = lab_flag("TE_STEP_NO_SMALL");
+  if (d.any) return false;
   if (!off && !no_small && d.n_ties != 0 && small_window(-1, &d, &w)) {
     hipLaunchKernelGGL(k_step_small<true>, small_grid(g, r), dim3(kLanes, 4), 0, s, g, w, crit, largest_float_below(crit), ncrit, sh, out, r);
     return true;

@@ -71,6 +71,12 @@ struct Disc {
   int reach;                     // max(R, max |tie offset|)
   int npoints;                   // number of cells in the runs (full disc, away from borders)
   int Q;                         // tie-free discs: largest a^2+b^2 <= (radius/res)^2 (names the shape); -1 with ties
+  // TE_OPT_FILTER_ANY_RADIUS: a disc the fixed arrays above do not hold (or every disc under option 2) takes the kernels of
+  // te_filter_any.hip.  Its runs and ties are in the device table `tab` (te_disc_table.h: hw[0 .. R], then n_ties (di, dj)
+  // int32 pairs); hw[] holds -1 and Q is -1, and every other kernel's route refuses the disc.
+  int any;
+  int any_hw0;                   // (host copy of tab[0]: the widest run)
+  const int* tab;
 };
 
 struct ChainParams {
@@ -330,6 +336,22 @@ hipError_t launch_check_circular_paths(const Geo& g, const float* footprint, dou
 // batched checkInclination(start, end): segment k = start_end_xy[4k .. 4k+4)
 hipError_t launch_check_inclination(const Geo& g, const float* robot_slope, int n, const double* start_end_xy,
                                     unsigned char* ok, int* status, hipStream_t stream);
+
+// te_filter_any.hip: the filters for the discs marked Disc::any (the other disc of a normals stage may be either kind)
+namespace any {
+struct NormalsJob {  // k_normals' arguments
+  Disc dn, dr;
+  int same_disc, axis, rank_rule;
+  int combine;        // also write the traversability layer (reads the step layer)
+  int given_normals;  // RoughnessFilter alone: surface_normal_{x,y,z} are input layers
+  double slope_crit, rough_crit;
+  float w_scale, w_slope, w_step, w_rough;
+};
+hipError_t step_height(const Geo& g, const Disc& d, const float* elev, float* sh, const Region& r, hipStream_t s);
+hipError_t step_score(const Geo& g, const Disc& d, double crit, int ncrit, const float* sh, float* out, const Region& r, hipStream_t s);
+// nx, ny, nz: the normals to keep (nullptr: none); with given_normals the input normals
+hipError_t normals(const Geo& g, const NormalsJob& a, const Layers& L, float* nx, float* ny, float* nz, const Region& r, hipStream_t s);
+}  // namespace any
 
 // shape-specialised kernels (te_fast_*.hip); return false when the shape Q is not instantiated
 namespace fast {

@@ -501,6 +501,25 @@ inline dim3 tile_grid(const Geo& g, const Region& r) {
 
 inline size_t tile_bytes(int K) { return (size_t)(TX + 2 * K) * (TY + 2 * K) * sizeof(float); }
 
+// a normals stage with a disc marked Disc::any: te_filter_any.hip, whatever the flags
+inline any::NormalsJob any_job(const NormalsArgs& na) {
+  any::NormalsJob j;
+  j.dn = na.dn;
+  j.dr = na.dr;
+  j.same_disc = na.same_disc;
+  j.axis = na.axis;
+  j.rank_rule = na.rank_rule;
+  j.combine = na.combine;
+  j.given_normals = na.given_normals;
+  j.slope_crit = na.slope_crit;
+  j.rough_crit = na.rough_crit;
+  j.w_scale = na.w_scale;
+  j.w_slope = na.w_slope;
+  j.w_step = na.w_step;
+  j.w_rough = na.w_rough;
+  return j;
+}
+
 }  // namespace
 
 int chain_max_reach(const ChainParams& p) {
@@ -522,11 +541,16 @@ hipError_t launch_filter(const Geo& g, const ChainParams& p, const Layers& L, in
     hipLaunchKernelGGL(k_slope_from_nz, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, g, p.slope_crit, L.nz,
                        L.slope);
   } else if (filter == TE_FILTER_STEP) {
-    if (!(use_fast && (fast::step_height_fast(p.step1.Q, g, L.elev, L.step_height, r, stream) ||
-                       fast::step_height_ties(p.step1, g, L.elev, L.step_height, L.tie_scratch, r, stream))))
+    hipError_t e;
+    if (p.step1.any) {
+      if ((e = any::step_height(g, p.step1, L.elev, L.step_height, r, stream)) != hipSuccess) return e;
+    } else if (!(use_fast && (fast::step_height_fast(p.step1.Q, g, L.elev, L.step_height, r, stream) ||
+                              fast::step_height_ties(p.step1, g, L.elev, L.step_height, L.tie_scratch, r, stream))))
       hipLaunchKernelGGL(k_step_height, tile_grid(g, r), blk, tile_bytes(p.step1.reach), stream, g, p.step1, L.elev,
                          L.step_height, r);
-    if (!(use_fast && (fast::step_score_fast(p.step2.Q, g, p.step_crit, p.step_ncrit, L.step_height, L.step, r, stream) ||
+    if (p.step2.any) {
+      if ((e = any::step_score(g, p.step2, p.step_crit, p.step_ncrit, L.step_height, L.step, r, stream)) != hipSuccess) return e;
+    } else if (!(use_fast && (fast::step_score_fast(p.step2.Q, g, p.step_crit, p.step_ncrit, L.step_height, L.step, r, stream) ||
                        fast::step_score_ties(p.step2, g, p.step_crit, p.step_ncrit, L.step_height, L.step, L.tie_scratch, r, stream))))
       hipLaunchKernelGGL(k_step_score, tile_grid(g, r), blk, tile_bytes(p.step2.reach), stream, g, p.step2, p.step_crit,
                          p.step_ncrit, L.step_height, L.step, r);
@@ -547,6 +571,7 @@ hipError_t launch_filter(const Geo& g, const ChainParams& p, const Layers& L, in
     // tie-free discs: the sliding kernel with the layers' normals (interior, hole-free discs in closed form from the
     // moments), the fix-up pass for the frame and the holes; otherwise the generic kernel on every cell
     FastGrid fg;
+    if (p.rough.any) return any::normals(g, any_job(na), L, L.nx, L.ny, L.nz, r, stream);
     if (use_fast && fast::roughness_given_fast(g, p, L, r, L.block_flags, &fg, stream))
       hipLaunchKernelGGL(k_normals_fixup, dim3((unsigned)fix_groups(fg.ntx * fg.nty * fg.nbz)), blk, tile_bytes(p.rough.reach), stream, g, na,
                          L.elev, L.step, L.slope, L.rough, L.trav, L.nx, L.ny, L.nz, L.block_flags, fg, r);
@@ -590,12 +615,15 @@ hipError_t launch_chain(const Geo& g, const ChainParams& p, const Layers& L, con
   // that kernel writes the step layer and the weighted sum as well: the whole chain is ONE kernel
   // (4096^2, default parameters at res 0.05: 0.34 -> 0.24 ms; 256^2: 17 -> 5 us).  Whole-map runs only: a region run
   // re-filters dilated regions stage by stage as before.
-  if (whole && use_fast && !normals_only && p.same_rough_disc && p.axis == 2) {  // a small launch: the whole chain in one kernel
+  // (a disc marked Disc::any takes te_filter_any.hip for its own stage: none of the one-kernel chains)
+  const bool any_normals = p.normals.any || p.rough.any;
+  const bool any_disc = any_normals || p.step1.any || p.step2.any;
+  if (whole && use_fast && !any_disc && !normals_only && p.same_rough_disc && p.axis == 2) {  // a small launch: the whole chain in one kernel
     TraceRange tr("chain: one kernel (k_chain_window)");
     if (fast::chain_window(g, p, L, (flags & TE_RUN_KEEP_NORMALS) != 0, r, !(flags & kDeferCombine), stream)) return hipGetLastError();
   }
-  if (whole && use_fast && !normals_only && p.same_rough_disc && p.axis == 2 && p.step1.n_ties == 0 && p.step1.Q == 0 && p.step2.n_ties == 0 &&
-      p.step2.Q == 0) {
+  if (whole && use_fast && !any_disc && !normals_only && p.same_rough_disc && p.axis == 2 && p.step1.n_ties == 0 && p.step1.Q == 0 &&
+      p.step2.n_ties == 0 && p.step2.Q == 0) {
     const bool comb = !(flags & kDeferCombine);
     FastGrid fg;
     TraceRange tr("chain: normals + slope + roughness + single-cell step windows + combine (one kernel)");
@@ -611,11 +639,16 @@ hipError_t launch_chain(const Geo& g, const ChainParams& p, const Layers& L, con
   }
   if (!normals_only) {
     TraceRange tr("chain: step filter (height, score)");
-    if (!(use_fast && (fast::step_height_fast(p.step1.Q, g, L.elev, L.step_height, r1, ss) ||
-                       fast::step_height_ties(p.step1, g, L.elev, L.step_height, L.tie_scratch, r1, ss))))
+    hipError_t e;
+    if (p.step1.any) {
+      if ((e = any::step_height(g, p.step1, L.elev, L.step_height, r1, ss)) != hipSuccess) return e;
+    } else if (!(use_fast && (fast::step_height_fast(p.step1.Q, g, L.elev, L.step_height, r1, ss) ||
+                              fast::step_height_ties(p.step1, g, L.elev, L.step_height, L.tie_scratch, r1, ss))))
       hipLaunchKernelGGL(k_step_height, tile_grid(g, r1), blk, tile_bytes(p.step1.reach), ss, g, p.step1, L.elev,
                          L.step_height, r1);
-    if (!(use_fast && (fast::step_score_fast(p.step2.Q, g, p.step_crit, p.step_ncrit, L.step_height, L.step, r2, ss) ||
+    if (p.step2.any) {
+      if ((e = any::step_score(g, p.step2, p.step_crit, p.step_ncrit, L.step_height, L.step, r2, ss)) != hipSuccess) return e;
+    } else if (!(use_fast && (fast::step_score_fast(p.step2.Q, g, p.step_crit, p.step_ncrit, L.step_height, L.step, r2, ss) ||
                        fast::step_score_ties(p.step2, g, p.step_crit, p.step_ncrit, L.step_height, L.step, L.tie_scratch, r2, ss))))
       hipLaunchKernelGGL(k_step_score, tile_grid(g, r2), blk, tile_bytes(p.step2.reach), ss, g, p.step2, p.step_crit,
                          p.step_ncrit, L.step_height, L.step, r2);
@@ -648,7 +681,11 @@ hipError_t launch_chain(const Geo& g, const ChainParams& p, const Layers& L, con
   FastGrid fg;
   bool combined = false;
   TraceRange tr_normals("chain: normals + slope + roughness (+ fix-up)");
-  if (use_fast && p.same_rough_disc && p.axis == 2 &&
+  if (any_normals) {
+    combined = na.combine != 0;
+    const hipError_t e = any::normals(g, any_job(na), L, knx, kny, knz, rn, stream);
+    if (e != hipSuccess) return e;
+  } else if (use_fast && p.same_rough_disc && p.axis == 2 &&
       fast::normals_fast(g, p, L, keep, fused_combine, rn, L.block_flags, L.clip_table, &fg, stream, &combined)) {
     na.combine = combined ? 1 : 0;
     if (fg.frame >= 0)  // (k_normals_small settles every cell itself)

@@ -1349,6 +1349,7 @@ bool normals_fast3(const Geo& g, const ChainParams& p, const Layers& L, bool kee
                    FastGrid* fgp, hipStream_t s) {
   FastGrid& fg = *fgp;
   const Disc& d = p.normals;
+  if (d.any || p.rough.any) return false;  // (te_filter_any.hip)
   // The shape the kernel slides: the disc, or for a tie radius the disc with its circle (whole-cell radii: every cell
   // on the circle has the norm reach^2, the runs plus the circle are the shape reach^2)
   int shape = d.Q, R = d.R;

@@ -426,7 +426,7 @@ bool normals_small(const Geo& g, const ChainParams& p, const Layers& L, bool kee
   static const bool off = lab_flag("TE_NO_SMALL");  // measurement aid
   static const int max_cells_env = lab_int("TE_SMALL_MAX_CELLS", 0);
   (void)flags;  // (no cell is left to the fix-up pass)
-  if (off || d.reach < 1 || d.reach > 2) return false;
+  if (off || d.any || p.rough.any || d.reach < 1 || d.reach > 2) return false;
   if ((double)g.rows * (double)g.cols * 4.0 >= 4294967296.0) return false;
   const long long cells = (long long)(r.i1 - r.i0) * (r.j1 - r.j0) * (r.map >= 0 ? 1 : g.batch);
   const long long small_launch = max_cells_env > 0 ? max_cells_env : (1ll << 18);
@@ -486,6 +486,7 @@ bool normals_small(const Geo& g, const ChainParams& p, const Layers& L, bool kee
 bool chain_window(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, const Region& r, bool combine, hipStream_t s) {
   static const bool off = lab_flag("TE_NO_CHAIN_WINDOW");  // measurement aid
   const Disc& d = p.normals;
+  if (off || d.any || p.rough.any || p.step1.any || p.step2.any) return false;  // (te_filter_any.hip)
   if (off || d.reach < 1 || d.reach > 2 || p.step1.n_ties != 0 || p.step2.n_ties != 0 || p.step1.Q < 0 || p.step1.Q > 2 || p.step2.Q < 0 || p.step2.Q > 2) return false;
   const long long cells = (long long)(r.i1 - r.i0) * (r.j1 - r.j0) * (r.map >= 0 ? 1 : g.batch);
   if (cells > (1ll << 18) || (double)g.rows * (double)g.cols * 4.0 >= 4294967296.0) return false;

@@ -83,6 +83,65 @@ int build_disc(double radius, double res, Disc* d, const char* what) {
   return TE_OK;
 }
 
+// A filter disc: build_disc's fixed arrays, or under TE_OPT_FILTER_ANY_RADIUS the table of any radius (te_disc_table.h) --
+// option 1 for the discs build_disc refuses, option 2 for every disc.  The device table is set by upload_any_discs.
+int filter_disc(te_ctx* c, double radius, Disc* d, DiscTable* t, const char* what) {
+  *t = DiscTable();
+  if (c->opt_filter_any != 2) {
+    char before[sizeof(g_err)];
+    memcpy(before, g_err, sizeof(before));
+    const int rc = build_disc(radius, c->geo.res, d, what);
+    if (rc == TE_OK || c->opt_filter_any == 0) return rc;
+    memcpy(g_err, before, sizeof(before));  // (the refusal is not an error under option 1)
+  }
+  build_disc_table(radius, c->geo.res, t);
+  memset(d, 0, sizeof(*d));
+  d->R = t->R;
+  for (int b = 0; b <= kMaxRadiusCells; ++b) d->hw[b] = -1;
+  d->n_ties = t->n_ties();
+  d->r2 = t->r2;
+  d->reach = t->reach;
+  d->npoints = t->npoints < 0x7fffffff ? (int)t->npoints : 0x7fffffff;
+  d->Q = -1;
+  d->any = 1;
+  d->any_hw0 = t->R >= 0 ? t->hw[0] : -1;
+  d->tab = nullptr;
+  return TE_OK;
+}
+
+// the tables of the discs marked Disc::any on the device, in one buffer (grown when a larger one is needed)
+int upload_any_discs(te_ctx* c) {
+  Disc* ds[4] = {&c->cp.normals, &c->cp.rough, &c->cp.step1, &c->cp.step2};
+  std::vector<int32_t> ints;
+  size_t off[4] = {0, 0, 0, 0};
+  for (int k = 0; k < 4; ++k) {
+    if (!ds[k]->any) continue;
+    off[k] = ints.size();
+    ints.insert(ints.end(), c->fa_host[k].hw.begin(), c->fa_host[k].hw.end());
+    ints.insert(ints.end(), c->fa_host[k].ties.begin(), c->fa_host[k].ties.end());
+    ints.push_back(0);  // (an empty disc still gets an address of its own)
+  }
+  if (ints.empty()) return TE_OK;
+  const size_t bytes = ints.size() * sizeof(int32_t);
+  HIP_TRY(hipSetDevice(c->device));
+  if (bytes > c->fa_tab_bytes) {
+    if (c->fa_tab) (void)hipFree(c->fa_tab);
+    c->fa_tab = nullptr;
+    c->fa_tab_bytes = 0;
+    if (hipMalloc(&c->fa_tab, bytes) != hipSuccess) {
+      c->fa_tab = nullptr;
+      (void)hipGetLastError();
+      return fail(TE_ERR_UNSUPPORTED, "filter discs of any radius: their tables (%zu bytes) do not fit in device memory", bytes);
+    }
+    c->fa_tab_bytes = bytes;
+  }
+  HIP_TRY(hipMemcpyAsync(c->fa_tab, ints.data(), bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < 4; ++k)
+    if (ds[k]->any) ds[k]->tab = (const int*)c->fa_tab + off[k];
+  return TE_OK;
+}
+
 bool same_disc(const Disc& a, const Disc& b) {
   if (a.R != b.R || a.n_ties != b.n_ties) return false;
   for (int k = 0; k <= kMaxRadiusCells; ++k)
@@ -229,7 +288,7 @@ bool ensure_hole_queue(te_ctx* c) {
 // the step filter's scratch layer at a tie radius (te_fast_step.hip); without it the generic kernels serve
 void ensure_tie_scratch(te_ctx* c) {
   if (c->tie_scratch || !c->tables_ready || c->layer_elems == 0) return;
-  if (c->cp.step1.n_ties == 0 && c->cp.step2.n_ties == 0) return;
+  if ((c->cp.step1.n_ties == 0 || c->cp.step1.any) && (c->cp.step2.n_ties == 0 || c->cp.step2.any)) return;
   if (hipSetDevice(c->device) != hipSuccess) return;
   void* p = nullptr;
   if (hipMalloc(&p, c->layer_elems * sizeof(float)) != hipSuccess) {
@@ -237,6 +296,15 @@ void ensure_tie_scratch(te_ctx* c) {
     return;
   }
   c->tie_scratch = (float*)p;
+}
+
+// TE_OPT_NORMALS_RANK_RULE decides on the rank of an exactly planar disc; on a normals disc above 32 cells the moment form's
+// pivot test and the oracle's (centred points, 3 eps) disagree on rounding noise, so the combination is refused
+int refuse_rank_rule(te_ctx* c) {
+  if (c->opt_rank_rule && c->cp.normals.any)
+    return fail(TE_ERR_UNSUPPORTED, "TE_OPT_NORMALS_RANK_RULE is not supported with a normals disc of the route of any radius (%d cells)",
+                c->cp.normals.R);
+  return TE_OK;
 }
 
 void drop_graph(te_ctx* c) {
@@ -420,11 +488,15 @@ int rebuild_tables(te_ctx* c) {
   const te_params& p = c->params;
   const double res = c->geo.res;
   int rc;
-  if ((rc = build_disc(p.normals_radius, res, &c->cp.normals, "normals"))) return rc;
-  if ((rc = build_disc(p.rough_radius, res, &c->cp.rough, "roughness estimation"))) return rc;
-  if ((rc = build_disc(p.step_radius1, res, &c->cp.step1, "step first window"))) return rc;
-  if ((rc = build_disc(p.step_radius2, res, &c->cp.step2, "step second window"))) return rc;
-  c->cp.same_rough_disc = same_disc(c->cp.normals, c->cp.rough) ? 1 : 0;
+  if ((rc = filter_disc(c, p.normals_radius, &c->cp.normals, &c->fa_host[0], "normals"))) return rc;
+  if ((rc = filter_disc(c, p.rough_radius, &c->cp.rough, &c->fa_host[1], "roughness estimation"))) return rc;
+  if ((rc = filter_disc(c, p.step_radius1, &c->cp.step1, &c->fa_host[2], "step first window"))) return rc;
+  if ((rc = filter_disc(c, p.step_radius2, &c->cp.step2, &c->fa_host[3], "step second window"))) return rc;
+  if ((rc = upload_any_discs(c))) return rc;
+  if (c->cp.normals.any || c->cp.rough.any)
+    c->cp.same_rough_disc = c->cp.normals.any && c->cp.rough.any && same_disc_table(c->fa_host[0], c->fa_host[1]) ? 1 : 0;
+  else
+    c->cp.same_rough_disc = same_disc(c->cp.normals, c->cp.rough) ? 1 : 0;
   c->cp.axis = p.normals_axis;
   c->cp.slope_crit = p.slope_critical;
   c->cp.step_crit = p.step_critical;
@@ -437,7 +509,8 @@ int rebuild_tables(te_ctx* c) {
   // x/y moments of the normals disc clipped by the map border, for the sliding-disc kernel
   // (a tie radius: the table of the disc WITH the cells on its circle behind it, then the circle's offsets with both
   // parts non-zero -- te_normals3.hip, TIES march)
-  if (c->cp.normals.R >= 1 || c->cp.normals.n_ties != 0) {
+  // (a disc of te_filter_any.hip has no clip table)
+  if (!c->cp.normals.any && (c->cp.normals.R >= 1 || c->cp.normals.n_ties != 0)) {
     const Disc& dn = c->cp.normals;
     HIP_TRY(hipSetDevice(c->device));
     if (!c->clip_table) HIP_TRY(hipMalloc((void**)&c->clip_table, sizeof(int) * (2 * fast::kClipInts + kMaxTies)));
@@ -539,6 +612,7 @@ int run_chain_locked(te_ctx* c, unsigned flags, const Region& r) {
     if (rc) return rc;
   }
   if (!c->have_elev) return fail(TE_ERR_NOT_READY, "te_run_chain: no elevation uploaded");
+  if (int rc = refuse_rank_rule(c)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   // Two streams (step filter || normals kernel) pay from about 2^21 cells: below that the launch is a handful of
   // short kernels and the fork / join events cost more than the overlap gains -- one stream, the combine fused into the
@@ -609,6 +683,7 @@ int run_whole_locked(te_ctx* c, unsigned flags) {
       int rc = rebuild_tables(c);
       if (rc) return rc;
     }
+    if (int rc = refuse_rank_rule(c)) return rc;  // (before a capture: a failed one would end graph replay for good)
     HIP_TRY(hipSetDevice(c->device));
     int slot = -1;
     // (the captured launches bake in which k_normals3 variant runs: the hint is part of the key)
@@ -803,6 +878,7 @@ int te_destroy(te_ctx* c) {
     if (c->clip_table) (void)hipFree(c->clip_table);
     if (c->fp_clip_table) (void)hipFree(c->fp_clip_table);
     release_fp_any(c);
+    if (c->fa_tab) (void)hipFree(c->fa_tab);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
@@ -874,6 +950,24 @@ int te_set_option(te_ctx* c, int option, int value) {
         c->opt_fp_any = value;
         c->footprint_done = false;
         if (c->tables_ready) rebuild_footprint_tables(c);
+      }
+      break;
+    case TE_OPT_FILTER_ANY_RADIUS:
+      if (value < 0 || value > 2)
+        return fail(TE_ERR_INVALID_ARG, "te_set_option: TE_OPT_FILTER_ANY_RADIUS takes 0 (up to 32 cells), 1 (any radius), 2 (the route of any radius for every disc)");
+      if (c->opt_filter_any != value) {
+        const int old = c->opt_filter_any;
+        c->opt_filter_any = value;
+        if (c->have_params && c->have_geo) {  // the discs of the parameters held; a failure leaves the option and the tables as they were
+          const int rc = rebuild_tables(c);
+          if (rc) {
+            c->opt_filter_any = old;
+            (void)rebuild_tables(c);
+            return rc;
+          }
+        }
+        c->chain_done = false;
+        c->footprint_done = false;
       }
       break;
     case TE_OPT_NORMALS_RANK_RULE:
@@ -984,6 +1078,8 @@ int te_run_filter(te_ctx* c, int filter, unsigned flags) {
   if (filter < TE_FILTER_SLOPE || filter > TE_FILTER_NORMALS) return fail(TE_ERR_INVALID_ARG, "te_run_filter: bad filter %d", filter);
   if ((filter == TE_FILTER_STEP || filter == TE_FILTER_ROUGHNESS || filter == TE_FILTER_NORMALS) && !c->have_elev)
     return fail(TE_ERR_NOT_READY, "te_run_filter: no elevation uploaded");
+  if (filter == TE_FILTER_NORMALS)
+    if (int rc = refuse_rank_rule(c)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   ensure_tie_scratch(c);
   c->L.tie_scratch = c->tie_scratch;

@@ -529,6 +529,7 @@ void launch_r(const Geo& g, SlideArgs a, const Layers& L, bool keep, const Regio
 bool normals_fast(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, bool combine,
                   const Region& r, int* flags, const int* gtab, FastGrid* fg, hipStream_t s, bool* combined) {
   const Disc& d = p.normals;
+  if (d.any || p.rough.any) return false;  // (te_filter_any.hip)
   if (normals_small(g, p, L, keep_normals, r, flags, fg, s)) {  // discs of at most 13 cells: one cell per thread
     *combined = false;
     return true;
@@ -617,7 +618,7 @@ bool normals_fast(const Geo& g, const ChainParams& p, const Layers& L, bool keep
 // RoughnessFilter alone on the roughness disc with the normals of the layers (SlideArgs::given).  False: not taken.
 bool roughness_given_fast(const Geo& g, const ChainParams& p, const Layers& L, const Region& r, int* flags, FastGrid* fg, hipStream_t s) {
   const Disc& d = p.rough;
-  if (d.n_ties != 0 || d.R < 1 || d.R > 16 || d.npoints < 3 || !flags) return false;
+  if (d.any || d.n_ties != 0 || d.R < 1 || d.R > 16 || d.npoints < 3 || !flags) return false;
   if (g.rows < 2 * d.R + 1 || g.cols < 2 * d.R + 1) return false;
   SlideArgs a;
   int sii = 0;

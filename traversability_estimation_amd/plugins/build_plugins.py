@@ -8,6 +8,7 @@ PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
 LIB = os.path.join(HERE, "libtraversability_estimation_filters.so")
 TEST = os.path.join(HERE, "plugin_chain_test")
+RADIUS_TEST = os.path.join(HERE, "plugin_radius_test")
 SRCS = ["src/DeviceMap.cpp", "src/SlopeFilter.cpp", "src/StepFilter.cpp", "src/RoughnessFilter.cpp",
         "src/FusedChainFilter.cpp", "src/SurfaceNormalsFilter.cpp", "src/TraversabilityMap.cpp", "stubs/pluginlib/registry.cpp"]
 
@@ -24,6 +25,12 @@ def build(verbose=False):
                     "-L" + HERE, "-ltraversability_estimation_filters", "-L" + os.path.join(ROOT, "oracle"), "-lte_oracle",
                     "-Wl,-rpath," + HERE, "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-Wl,-rpath," + PKG,
                     "-Wl,--no-as-needed", "-o", TEST]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    # the Step and Roughness plugins at radii above 32 cells (tests/test_plugins_radius.py)
+    cmd = cmd[:cmd.index(TEST)] + [RADIUS_TEST]
+    cmd[cmd.index(os.path.join(HERE, "test", "plugin_chain_test.cpp"))] = os.path.join(HERE, "test", "plugin_radius_test.cpp")
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

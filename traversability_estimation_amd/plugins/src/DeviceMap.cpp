@@ -67,6 +67,15 @@ uint64_t hash_layer(const float* d, size_t n, bool sampled) {
   }
   return mix64(mix64(mix64(h0, h1), h2), h3) ^ (uint64_t)n;
 }
+// the reference's filters take any radius: so does the context of the plugins (TE_OPT_FILTER_ANY_RADIUS = 1)
+int create_context(te_ctx** ctx) {
+  int rc = te_create(0, ctx);
+  if (rc == TE_OK && (rc = te_set_option(*ctx, TE_OPT_FILTER_ANY_RADIUS, 1)) != TE_OK) {
+    te_destroy(*ctx);  // (no context without the option)
+    *ctx = nullptr;
+  }
+  return rc;
+}
 bool hash_sampled() {
   static const bool v = getenv("TRAVGPU_PLUGIN_HASH") && !strcmp(getenv("TRAVGPU_PLUGIN_HASH"), "sampled");
   return v;
@@ -84,7 +93,7 @@ bool DeviceMap::check(int rc) {
 }
 
 bool DeviceMap::prepare(const grid_map::GridMap& map) {
-  if (!ctx_ && !check(te_create(0, &ctx_))) return false;
+  if (!ctx_ && !check(create_context(&ctx_))) return false;
   // a moved map is a circular buffer; the copies to and from the device undo / redo the rotation
   start_row_ = map.getStartIndex()(0);
   start_col_ = map.getStartIndex()(1);
@@ -99,17 +108,17 @@ bool DeviceMap::prepare(const grid_map::GridMap& map) {
 }
 
 bool DeviceMap::params(te_params& p) {
-  if (!ctx_ && !check(te_create(0, &ctx_))) return false;
+  if (!ctx_ && !check(create_context(&ctx_))) return false;
   return check(te_get_params(ctx_, &p));
 }
 
 bool DeviceMap::setParams(const te_params& p) {
-  if (!ctx_ && !check(te_create(0, &ctx_))) return false;
+  if (!ctx_ && !check(create_context(&ctx_))) return false;
   return check(te_set_params(ctx_, &p));
 }
 
 bool DeviceMap::setOption(int option, int value) {
-  if (!ctx_ && !check(te_create(0, &ctx_))) return false;
+  if (!ctx_ && !check(create_context(&ctx_))) return false;
   return check(te_set_option(ctx_, option, value));
 }
 

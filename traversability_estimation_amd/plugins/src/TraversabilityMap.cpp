@@ -19,7 +19,15 @@ TraversabilityMap::TraversabilityMap(int device)
       footprintOffset_(-1.0),
       circularFootprintOffset_(0.15) {
   te_params_default(&params_);
-  if (check(te_create(device, &ctx_))) check(te_set_params(ctx_, &params_));
+  // (the reference's filters take any radius: TE_OPT_FILTER_ANY_RADIUS = 1)
+  if (check(te_create(device, &ctx_))) {
+    if (check(te_set_option(ctx_, TE_OPT_FILTER_ANY_RADIUS, 1))) {
+      check(te_set_params(ctx_, &params_));
+    } else {
+      te_destroy(ctx_);  // (no context without the option)
+      ctx_ = nullptr;
+    }
+  }
 }
 
 TraversabilityMap::~TraversabilityMap() {
