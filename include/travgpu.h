@@ -30,7 +30,7 @@
  *                           isTraversableForFilters :774-792, checkFor{Slope,Step,Roughness} :794-921)
  *   te_download_layer    <- mapOut.add(type_) / mapOut.at(type_, index) results of each plugin
  *                           (SlopeFilter.cpp:63,77-80 etc.)
- *   te_check_footprint_paths, te_check_polygon_footprint_paths
+ *   te_check_footprint_paths, te_check_footprint_paths_radius, te_check_polygon_footprint_paths
  *                        <- TraversabilityMap::checkFootprintPath, TraversabilityMap.cpp:320-342
  *                           (checkCircularFootprintPath :344-462, checkPolygonalFootprintPath :464-584)
  *   te_check_inclination, te_set_check_robot_inclination
@@ -272,6 +272,35 @@ int te_run_footprint(te_ctx* ctx);
  * the same with and without it.  Host buffers; synchronous. */
 int te_check_footprint_paths(te_ctx* ctx, int map, int n_paths, const int* pose_offset, const double* pose_xy,
                              unsigned char* is_safe, double* traversability, int* status);
+/* The same check with every path at its OWN radius (FootprintPath.radius, TraversabilityMap.cpp:347-348) and without a
+ * footprint layer: the value at a visited centre is isTraversable(centre, radius[k] + offset, radius[k]) evaluated on demand
+ * (:681-735 with computeUntraversablePolygon = false, the radiusMin == 0 branch and the static_cast<float> of the memo store
+ * included), at the centres the paths visit and nowhere else -- what the reference does on the all-NaN footprint layer
+ * computeTraversability leaves behind.  A request that mixes k radii costs one call, not k whole-map footprint passes.
+ *   precondition: the chain has run on the map (te_run_chain / te_run_chain_region): TE_ERR_NOT_READY otherwise.  The
+ *     footprint pass need not have run; TE_LAYER_FOOTPRINT is neither read nor written, and the call changes neither the
+ *     three memo layers nor the parameters te_get_params returns.
+ *   radius[n_paths], offset (0.15 in the reference, :348): negative or non-finite values give TE_ERR_INVALID_ARG for the
+ *     whole call.  At most 65536 distinct radii per call.
+ *   outputs, status codes, check_robot_inclination, traversabilityDefault_ (fp_default) for a centre outside the map, the
+ *     nSkip = 3 walk and the length-weighted mean: those of te_check_footprint_paths.
+ *   memo: lives for this one call, keyed by (centre cell, radius, offset).  The reference keeps ONE memo layer for all
+ *     radii, so there a value computed for one radius answers a later query at another radius; that accident of its state
+ *     is deliberately not reproduced.  The reference also stops a path at its first unsafe centre; the batch evaluates
+ *     every visited centre, the results are the same.
+ *   stats (may be NULL): n_visits centres visited by all paths (a one-pose path outside the map visits none; a path stops
+ *     at a segment with an end outside the map), n_discs distinct (cell, radius) discs evaluated, n_radius_classes
+ *     distinct radii.
+ * The untraversable-cell mask the discs read does not depend on the radius: it is built on the first call after the
+ * scores changed and kept until they, fp_max_gap, fp_critical_step or fp_check_roughness change.  Scratch memory follows
+ * the number of visits, not the map.  Not covered: publishPolygons, and the untraversable polygon of the on-demand branch
+ * (the convex hull at :729).  Host buffers; synchronous. */
+typedef struct te_path_check_stats {
+  int n_visits, n_discs, n_radius_classes;
+} te_path_check_stats;
+int te_check_footprint_paths_radius(te_ctx* ctx, int map, int n_paths, const int* pose_offset, const double* pose_xy,
+                                    const double* radius, double offset, unsigned char* is_safe, double* traversability,
+                                    int* status, te_path_check_stats* stats);
 /* footprint/check_robot_inclination (TraversabilityMap.cpp:114, default false): when set, te_check_footprint_paths and
  * te_check_polygon_footprint_paths run checkInclination before every isTraversable, reading TE_LAYER_ROBOT_SLOPE (the
  * reference's layer "robot_slope", written by whoever estimates the robot's inclination); TE_ERR_NOT_READY from the

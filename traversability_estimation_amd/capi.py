@@ -34,7 +34,7 @@ OPT_FILTER_ANY_RADIUS = 8  # filter discs: 0 up to 32 cells (TE_ERR_UNSUPPORTED 
 SYMBOLS = ["te_params_default", "te_params_validate", "te_device_count", "te_create", "te_destroy",
            "te_set_params", "te_get_params", "te_set_option", "te_set_geometry", "te_upload_elevation", "te_upload_tile", "te_download_tile",
            "te_upload_tile_async", "te_download_tile_async",
-           "te_device_ptr", "te_set_layer_present", "te_upload_layer", "te_prefetch_layers", "te_wait_prefetch", "te_upload_layer_circular", "te_download_layer_circular", "te_run_filter", "te_run_chain", "te_run_chain_region", "te_run_footprint", "te_check_footprint_paths",
+           "te_device_ptr", "te_set_layer_present", "te_upload_layer", "te_prefetch_layers", "te_wait_prefetch", "te_upload_layer_circular", "te_download_layer_circular", "te_run_filter", "te_run_chain", "te_run_chain_region", "te_run_footprint", "te_check_footprint_paths", "te_check_footprint_paths_radius",
            "te_sync",
            "te_download_layer", "te_time_chain", "te_time_chain_samples", "te_last_error", "te_version",
            "te_msg_parse", "te_msg_layer", "te_msg_write", "te_upload_msg", "te_download_msg", "te_bag_find_message",
@@ -87,6 +87,11 @@ class TeMsgInfo(C.Structure):
                 ("pose", C.c_double * 7),
                 ("rows", C.c_int32), ("cols", C.c_int32), ("start_row", C.c_int32), ("start_col", C.c_int32),
                 ("n_layers", C.c_int32), ("n_basic_layers", C.c_int32)]
+
+
+class TePathCheckStats(C.Structure):
+    """te_path_check_stats: centres visited, distinct (cell, radius) discs evaluated, distinct radii."""
+    _fields_ = [("n_visits", C.c_int), ("n_discs", C.c_int), ("n_radius_classes", C.c_int)]
 
 
 class TeParams(C.Structure):
@@ -153,6 +158,9 @@ def load():
         L.te_check_inclination.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_ubyte), C.POINTER(C.c_int)]
         L.te_check_footprint_paths.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double),
                                                C.POINTER(C.c_ubyte), C.POINTER(C.c_double), C.POINTER(C.c_int)]
+        L.te_check_footprint_paths_radius.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                                      C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_ubyte),
+                                                      C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(TePathCheckStats)]
         L.te_run_polygon_footprint.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.c_double]
         L.te_polygons_traversable.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double),
                                               C.POINTER(C.c_ubyte), C.POINTER(C.c_double)]
@@ -475,6 +483,33 @@ class Context:
                                                trav.ctypes.data_as(C.POINTER(C.c_double)),
                                                st.ctypes.data_as(C.POINTER(C.c_int))))
         return safe[:n].astype(bool), trav[:n], st[:n]
+
+    def check_footprint_paths_radius(self, paths, radii, offset=0.15, map_index=0, want_stats=False):
+        """checkFootprintPath for circular footprints with every path at its own radius (FootprintPath.radius), evaluated on
+        demand at the centres the paths visit: no footprint layer is needed, read or written (te_check_footprint_paths_radius).
+        radii: a scalar, or one value per path.  Returns (is_safe, traversability, status), and with want_stats a dict
+        n_visits / n_discs / n_radius_classes as the fourth element."""
+        off, xy = pack_paths(paths)
+        n = len(off) - 1
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radii, dtype=np.float64), (n,)) if np.ndim(radii) == 0
+                                 else np.asarray(radii, dtype=np.float64).reshape(-1))
+        if len(r) != n:
+            raise ValueError(f"{len(r)} radii for {n} paths")
+        if n == 0:
+            r = np.zeros(1, np.float64)
+        safe = np.zeros(max(n, 1), np.uint8)
+        trav = np.zeros(max(n, 1), np.float64)
+        st = np.zeros(max(n, 1), np.int32)
+        stats = TePathCheckStats()
+        dp = C.POINTER(C.c_double)
+        _check(load().te_check_footprint_paths_radius(self._h, int(map_index), n, off.ctypes.data_as(C.POINTER(C.c_int)),
+                                                      xy.ctypes.data_as(dp), r.ctypes.data_as(dp), float(offset),
+                                                      safe.ctypes.data_as(C.POINTER(C.c_ubyte)), trav.ctypes.data_as(dp),
+                                                      st.ctypes.data_as(C.POINTER(C.c_int)), C.byref(stats)))
+        out = (safe[:n].astype(bool), trav[:n], st[:n])
+        if want_stats:
+            out += ({"n_visits": stats.n_visits, "n_discs": stats.n_discs, "n_radius_classes": stats.n_radius_classes},)
+        return out
 
     def polygon_untraversable_hull(self, polygon, map_index=0, cap=4096):
         """isTraversable(polygon, computeUntraversablePolygon=True): (is_traversable, traversability, hull (k, 2))."""

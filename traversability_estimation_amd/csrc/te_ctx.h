@@ -74,6 +74,26 @@ struct te_ctx {
   size_t fpa_tab_bytes = 0;
   void* fpa_prefix = nullptr;  // [batch][cols][rows + 1] doubles, then as many unsigned
   size_t fpa_prefix_bytes = 0;
+  // mask_done: the untraversable mask (L.untrav) is complete for the scores and the three parameters it reads (fp_max_gap,
+  // fp_critical_step, fp_check_roughness).  Set by every footprint pass and by te_check_footprint_paths_radius, which builds
+  // the mask on its own when it is not; cleared wherever footprint_done is cleared -- except that te_set_params keeps it
+  // when nothing the mask reads changed -- and by an upload of a score layer (which leaves footprint_done as it was).
+  // te_check_footprint_paths_radius (te_path_discs.hip) -- pd_tables: the spiral tables of the radius classes on the device,
+  // by (radius, offset, resolution, map size), at most kPdTables of them, the least recently used one replaced; dropped
+  // with the layers.  pd_scratch: the call's staging buffers and memo, grown to the largest request so far.
+  bool mask_done = false;
+  struct PdTable {
+    double radius = 0.0, offset = 0.0, res = 0.0;
+    int rows = 0, cols = 0;  // (the clip)
+    void* dev = nullptr;     // FpEntry [n_spiral]
+    int n_spiral = 0;
+    unsigned long long used = 0;  // pd_clock at its last use
+  };
+  static constexpr int kPdTables = 16;
+  PdTable pd_tables[kPdTables];
+  unsigned long long pd_clock = 0;
+  void* pd_scratch = nullptr;
+  size_t pd_scratch_bytes = 0;
   bool combine_deferred = false;
   // the traversability layer was written from outside (upload, device pointer, a per-plugin combine of uploaded scores):
   // its values are then not bounded by the weights, and the fixed-point footprint kernel must not be used
@@ -163,5 +183,6 @@ int rebuild_tables(te_ctx* c);
 void rebuild_footprint_tables(te_ctx* c);
 int sync_tiles(te_ctx* c);  // waits for the copy streams of the streaming-tile calls
 int run_whole_locked(te_ctx* c, unsigned flags);
+void release_path_discs(te_ctx* c);  // te_paths_api.hip: the spiral tables and the scratch of te_check_footprint_paths_radius
 }  // namespace shim
 }  // namespace te

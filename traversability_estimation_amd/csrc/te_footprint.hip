@@ -1244,11 +1244,10 @@ bool footprint_slide_general(const Geo& g, const FootprintParams& p, const Layer
   }
 }
 
-}  // namespace
-
-hipError_t launch_footprint(const Geo& g, const FootprintParams& p, const Layers& L, const unsigned* ptab,
-                            const int* clip_table, bool write_memo, const ChainParams* combine, double trav_cap, hipStream_t stream,
-                            const Region* region) {
+// The mask pass of launch_footprint / launch_footprint_mask: k_fp_mask on the cells whose mask the scores of `region` can
+// change (nullptr: every cell of every map).  *rf_out: the cells whose footprint can change with them.
+void launch_mask_pass(const Geo& g, const FootprintParams& p, const Layers& L, bool write_memo, const ChainParams* combine,
+                      hipStream_t stream, const Region* region, Region* rf_out) {
   MaskArgs m;
   m.slope_disc = p.slope_disc;
   m.step_disc = p.step_disc;
@@ -1323,6 +1322,22 @@ hipError_t launch_footprint(const Geo& g, const FootprintParams& p, const Layers
     TraceRange tr(combine ? "footprint: isTraversableForFilters mask + weighted combine" : "footprint: isTraversableForFilters mask");
     launch_mask(t_lo, t_hi, stream);
   }
+  *rf_out = rf;
+}
+
+}  // namespace
+
+hipError_t launch_footprint_mask(const Geo& g, const FootprintParams& p, const Layers& L, const ChainParams* combine, hipStream_t stream) {
+  Region rf;
+  launch_mask_pass(g, p, L, false, combine, stream, nullptr, &rf);
+  return hipGetLastError();
+}
+
+hipError_t launch_footprint(const Geo& g, const FootprintParams& p, const Layers& L, const unsigned* ptab,
+                            const int* clip_table, bool write_memo, const ChainParams* combine, double trav_cap, hipStream_t stream,
+                            const Region* region) {
+  Region rf;
+  launch_mask_pass(g, p, L, write_memo, combine, stream, region, &rf);
   TraceRange tr_sum("footprint: disc sums (+ blocked discs)");
   const Region* rfp = region ? &rf : nullptr;
   const Disc& d = p.fp_disc;

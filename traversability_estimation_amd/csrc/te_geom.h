@@ -1,5 +1,8 @@
 // te_geom.h -- grid_map_core geometry on the device: cell centres, checkIfPositionWithinMap,
 // getIndexFromPosition and the Bresenham LineIterator, in the reference's own double arithmetic.
+// (te_path_visit.h holds a plain C++ copy of pos_inside, pos_to_index and LineIt -- pv::Geom, for the host driver's sizing and
+// the CPU check of the visit plan: a change here is a change there.  te_check_footprint_paths_radius compares the two walks'
+// visit counts on every call.)
 #pragma once
 #include "te_internal.h"
 

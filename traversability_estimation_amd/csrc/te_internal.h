@@ -337,6 +337,29 @@ hipError_t launch_check_circular_paths(const Geo& g, const float* footprint, dou
 hipError_t launch_check_inclination(const Geo& g, const float* robot_slope, int n, const double* start_end_xy,
                                     unsigned char* ok, int* status, hipStream_t stream);
 
+// te_path_discs.hip: circular path checks at each path's own radius, evaluated on demand at the visited centres
+struct PathDiscClass {  // one radius class of a request
+  const int4* spiral;   // FpEntry [n_spiral] of circle(radius + offset), SpiralIterator order, clipped to the map (te_fp_table.h)
+  int n_spiral, pad;
+  double rmin, rmax, r2;  // radius, radius + offset, (radius + offset)^2
+};
+enum { kPdDiscs = 0, kPdOverflow = 1, kPdVisits = 2, kPdCounters = 4 };
+struct PathDiscScratch {  // the memo of one call: sized by its number of visits (te_path_visit.h: table_entries)
+  uint64_t* keys;      // [mask + 1] open-addressing table of pack_key(class, cell); kEmptyKey: free
+  float* vals;         // [mask + 1] the disc's value beside its key
+  unsigned* list;      // [list_cap] slots in the order of their first insertion: the discs to evaluate
+  unsigned* counters;  // [kPdCounters]: discs listed, "table or list full", centres visited
+  uint64_t mask;
+  unsigned list_cap;
+};
+// the three phases (visit, discs, paths) on `stream`; trav / untrav / robot_slope: the layers of the map the paths are on
+hipError_t launch_path_discs(const Geo& g, const PathDiscScratch& s, const PathDiscClass* classes, const float* trav, const uint8_t* untrav,
+                             double fp_default, const float* robot_slope, int n_paths, const int* pose_offset, const double* pose_xy,
+                             const int* path_class, unsigned char* is_safe, double* traversability, int* status, hipStream_t stream);
+// te_footprint.hip: the isTraversableForFilters mask of every cell of every map (Layers::untrav, untrav_flags) and nothing
+// else: no memo layers, no footprint layer; combine: also the weighted sum a whole-map chain left to the mask kernel
+hipError_t launch_footprint_mask(const Geo& g, const FootprintParams& p, const Layers& L, const ChainParams* combine, hipStream_t stream);
+
 // te_filter_any.hip: the filters for the discs marked Disc::any (the other disc of a normals stage may be either kind)
 namespace any {
 struct NormalsJob {  // k_normals' arguments

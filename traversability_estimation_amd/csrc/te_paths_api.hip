@@ -2,11 +2,212 @@
 // TraversabilityMap.cpp:320-645), checkInclination (:748-762), the polygon footprint layers (:239-305).  Kernels:
 // te_paths.hip, te_polygon.hip.  The context and the helpers shared with the other parts: te_ctx.h.
 #include "te_ctx.h"
+#include "te_fp_table.h"
+#include "te_path_visit.h"
 
 using namespace te;
 using namespace te::shim;
 
+namespace te {
+namespace shim {
+void release_path_discs(te_ctx* c) {
+  for (te_ctx::PdTable& t : c->pd_tables) {
+    if (t.dev) (void)hipFree(t.dev);
+    t = te_ctx::PdTable();
+  }
+  if (c->pd_scratch) (void)hipFree(c->pd_scratch);
+  c->pd_scratch = nullptr;
+  c->pd_scratch_bytes = 0;
+}
+}  // namespace shim
+}  // namespace te
+
+namespace {
+// The spiral table of circle(radius + offset) on the device, from the context's cache or built now (te_fp_table.h: the
+// table of the footprint pass at any reach).  A request with more classes than the cache holds keeps the rest in `temps`
+// for the call.  first_clock: pd_clock when the call began (entries used since then serve this call and stay).
+int path_disc_table(te_ctx* c, double radius, double offset, unsigned long long first_clock, std::vector<void*>& temps,
+                    PathDiscClass* out) {
+  const Geo& g = c->geo;
+  out->rmin = radius;
+  out->rmax = radius + offset;
+  out->r2 = out->rmax * out->rmax;
+  out->pad = 0;
+  te_ctx::PdTable* victim = nullptr;
+  for (te_ctx::PdTable& t : c->pd_tables) {
+    if (t.dev && t.radius == radius && t.offset == offset && t.res == g.res && t.rows == g.rows && t.cols == g.cols) {
+      t.used = ++c->pd_clock;
+      out->spiral = (const int4*)t.dev;
+      out->n_spiral = t.n_spiral;
+      return TE_OK;
+    }
+    if ((!t.dev || t.used <= first_clock) && (!victim || (victim->dev && (!t.dev || t.used < victim->used)))) victim = &t;
+  }
+  FpTable tab;
+  build_fp_table(out->rmax, g.res, g.rows, g.cols, &tab);
+  const size_t bytes = tab.spiral.size() * sizeof(FpEntry);
+  if (tab.spiral.size() > (size_t)0x7fffffff) return fail(TE_ERR_UNSUPPORTED, "te_check_footprint_paths_radius: a spiral of %zu entries", tab.spiral.size());
+  void* dev = nullptr;
+  hipError_t e = hipMalloc(&dev, bytes);
+  if (e == hipSuccess) e = hipMemcpyAsync(dev, tab.spiral.data(), bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (tab goes out of scope)
+  if (e != hipSuccess) {
+    if (dev) (void)hipFree(dev);
+    (void)hipGetLastError();
+    return fail(TE_ERR_HIP, "te_check_footprint_paths_radius: the spiral table of radius %g m (%zu bytes): %s", radius, bytes, hipGetErrorString(e));
+  }
+  out->spiral = (const int4*)dev;
+  out->n_spiral = (int)tab.spiral.size();
+  if (victim) {
+    if (victim->dev) (void)hipFree(victim->dev);  // (no launch is in flight: every call ends with a stream synchronize)
+    victim->radius = radius;
+    victim->offset = offset;
+    victim->res = g.res;
+    victim->rows = g.rows;
+    victim->cols = g.cols;
+    victim->dev = dev;
+    victim->n_spiral = out->n_spiral;
+    victim->used = ++c->pd_clock;
+  } else {
+    temps.push_back(dev);
+  }
+  return TE_OK;
+}
+}  // namespace
+
 extern "C" {
+
+int te_check_footprint_paths_radius(te_ctx* c, int map, int n_paths, const int* pose_offset, const double* pose_xy, const double* radius,
+                                    double offset, unsigned char* is_safe, double* traversability, int* status,
+                                    te_path_check_stats* stats) {
+  if (!c || n_paths < 0 || (n_paths > 0 && (!pose_offset || !pose_xy || !radius || !is_safe || !traversability || !status)))
+    return fail(TE_ERR_INVALID_ARG, "te_check_footprint_paths_radius: NULL argument");
+  if (!isfinite(offset) || offset < 0.0) return fail(TE_ERR_INVALID_ARG, "te_check_footprint_paths_radius: offset %g", offset);
+  for (int k = 0; k < n_paths; ++k)
+    if (!isfinite(radius[k]) || radius[k] < 0.0)
+      return fail(TE_ERR_INVALID_ARG, "te_check_footprint_paths_radius: radius[%d] = %g (a footprint radius is finite and not negative)", k, radius[k]);
+  CtxLock lk(c);
+  if (!c->have_geo || !c->chain_done || !c->tables_ready)
+    return fail(TE_ERR_NOT_READY, "te_check_footprint_paths_radius: run the filter chain first (it produces the layers the discs read)");
+  if (map < 0 || map >= c->geo.batch) return fail(TE_ERR_INVALID_ARG, "te_check_footprint_paths_radius: map %d of %d", map, c->geo.batch);
+  if (c->check_inclination && !c->have_robot_slope)
+    return fail(TE_ERR_NOT_READY, "te_check_footprint_paths_radius: check_robot_inclination is set but the layer robot_slope was never uploaded");
+  if (stats) stats->n_visits = stats->n_discs = stats->n_radius_classes = 0;
+  if (n_paths == 0) return TE_OK;
+  const int n_poses = pose_offset[n_paths];
+  if (pose_offset[0] != 0 || n_poses < 0) return fail(TE_ERR_INVALID_ARG, "te_check_footprint_paths_radius: bad pose offsets");
+  for (int k = 0; k < n_paths; ++k)
+    if (pose_offset[k + 1] < pose_offset[k]) return fail(TE_ERR_INVALID_ARG, "te_check_footprint_paths_radius: bad pose offsets");
+  // (the mask kernel takes the discs of its three checks from the footprint tables; they do not depend on fp_radius)
+  if (!c->fp_tables_ready) return fail(c->fp_tables_rc ? c->fp_tables_rc : TE_ERR_NOT_READY, "%s", c->fp_tables_err);
+  const Geo& g = c->geo;
+  // the plan (te_path_visit.h): radius classes, and the number of visits, which sizes the memo
+  std::vector<double> uniq;
+  std::vector<int> cls;
+  pv::class_radii(n_paths, radius, &uniq, &cls);
+  if (uniq.size() > (size_t)pv::kMaxClasses)
+    return fail(TE_ERR_UNSUPPORTED, "te_check_footprint_paths_radius: %zu distinct radii in one call (at most %d)", uniq.size(), pv::kMaxClasses);
+  const pv::Geom hg = {g.rows, g.cols, g.res, g.len_x, g.len_y, g.pos_x, g.pos_y};
+  unsigned long long n_visits = 0;
+  for (int k = 0; k < n_paths; ++k)
+    n_visits += (unsigned long long)pv::count_path_visits(hg, pose_offset[k + 1] - pose_offset[k], pose_xy + 2 * (size_t)pose_offset[k]);
+  const uint64_t entries = pv::table_entries(n_visits);
+  if (entries > ((uint64_t)1 << 31)) return fail(TE_ERR_UNSUPPORTED, "te_check_footprint_paths_radius: %llu centres in one call", n_visits);
+  HIP_TRY(hipSetDevice(c->device));
+  const unsigned long long first_clock = c->pd_clock;
+  std::vector<PathDiscClass> classes(uniq.size());
+  std::vector<void*> temps;
+  auto drop_temps = [&]() {
+    for (void* t : temps) (void)hipFree(t);
+  };
+  for (size_t q = 0; q < uniq.size(); ++q)
+    if (const int rc = path_disc_table(c, uniq[q], offset, first_clock, temps, &classes[q])) {
+      drop_temps();
+      return rc;
+    }
+  // one scratch buffer: the staged request and its results, the class array, the memo (keys, values, work list, counters)
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t list_cap = n_visits > 0 ? (size_t)n_visits : 1;
+  const size_t b_off = (size_t)(n_paths + 1) * sizeof(int), b_xy = (size_t)2 * (n_poses > 0 ? n_poses : 1) * sizeof(double);
+  const size_t b_cls = (size_t)n_paths * sizeof(int), b_trav = (size_t)n_paths * sizeof(double), b_st = (size_t)n_paths * sizeof(int);
+  const size_t b_safe = (size_t)n_paths, b_classes = classes.size() * sizeof(PathDiscClass);
+  const size_t b_keys = (size_t)entries * sizeof(uint64_t), b_vals = (size_t)entries * sizeof(float), b_list = list_cap * sizeof(unsigned);
+  const size_t b_cnt = kPdCounters * sizeof(unsigned);
+  const size_t sizes[11] = {b_keys, b_xy, b_trav, b_classes, b_off, b_cls, b_st, b_vals, b_list, b_cnt, b_safe};
+  size_t at[12];
+  at[0] = 0;
+  for (int k = 0; k < 11; ++k) at[k + 1] = at[k] + up(sizes[k]);
+  if (at[11] > c->pd_scratch_bytes) {
+    if (c->pd_scratch) (void)hipFree(c->pd_scratch);
+    c->pd_scratch = nullptr;
+    c->pd_scratch_bytes = 0;
+    const hipError_t e = hipMalloc(&c->pd_scratch, at[11]);
+    if (e != hipSuccess) {
+      c->pd_scratch = nullptr;
+      (void)hipGetLastError();
+      drop_temps();
+      return fail(TE_ERR_HIP, "te_check_footprint_paths_radius: hipMalloc(%zu bytes) for %llu centres: %s", at[11], n_visits, hipGetErrorString(e));
+    }
+    c->pd_scratch_bytes = at[11];
+  }
+  char* d = (char*)c->pd_scratch;
+  PathDiscScratch s;
+  s.keys = (uint64_t*)(d + at[0]);
+  double* d_xy = (double*)(d + at[1]);
+  double* d_trav = (double*)(d + at[2]);
+  PathDiscClass* d_classes = (PathDiscClass*)(d + at[3]);
+  int* d_off = (int*)(d + at[4]);
+  int* d_cls = (int*)(d + at[5]);
+  int* d_st = (int*)(d + at[6]);
+  s.vals = (float*)(d + at[7]);
+  s.list = (unsigned*)(d + at[8]);
+  s.counters = (unsigned*)(d + at[9]);
+  unsigned char* d_safe = (unsigned char*)(d + at[10]);
+  s.mask = entries - 1;
+  s.list_cap = (unsigned)list_cap;
+  unsigned counters[kPdCounters] = {0, 0, 0, 0};
+  hipError_t e = hipMemcpyAsync(d_off, pose_offset, b_off, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && n_poses > 0) e = hipMemcpyAsync(d_xy, pose_xy, (size_t)2 * n_poses * sizeof(double), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_cls, cls.data(), b_cls, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_classes, classes.data(), b_classes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(s.keys, 0xFF, b_keys, c->stream);  // pv::kEmptyKey
+  if (e == hipSuccess) e = hipMemsetAsync(s.counters, 0, b_cnt, c->stream);
+  // the untraversable mask: built on the first call after the scores (or one of the three parameters it reads) changed
+  if (e == hipSuccess && !c->mask_done) {
+    e = launch_footprint_mask(g, c->fp, c->L, c->combine_deferred ? &c->cp : nullptr, c->stream);
+    if (e == hipSuccess) {
+      c->combine_deferred = false;
+      c->mask_done = true;
+    }
+  }
+  const size_t per = (size_t)g.rows * g.cols;
+  if (e == hipSuccess)
+    e = launch_path_discs(g, s, d_classes, c->L.trav + per * map, c->L.untrav + per * map, c->params.fp_default,
+                          c->check_inclination ? c->robot_slope + per * map : nullptr, n_paths, d_off, d_xy, d_cls, d_safe, d_trav, d_st,
+                          c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(is_safe, d_safe, b_safe, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(traversability, d_trav, b_trav, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(status, d_st, b_st, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(counters, s.counters, b_cnt, hipMemcpyDeviceToHost, c->stream);
+  const hipError_t e_sync = hipStreamSynchronize(c->stream);  // (also before the tables of this call alone are freed)
+  if (e == hipSuccess) e = e_sync;
+  drop_temps();
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(TE_ERR_HIP, "te_check_footprint_paths_radius: %s", hipGetErrorString(e));
+  }
+  // (internal errors -- no HIP call failed: the plan of te_path_visit.h and the kernels' walk disagree; the outputs are not valid)
+  if (counters[kPdOverflow])
+    return fail(TE_ERR_UNSUPPORTED, "te_check_footprint_paths_radius: internal error: the memo of %llu entries (work list %zu) overflowed", (unsigned long long)entries, list_cap);
+  if (counters[kPdVisits] != n_visits)
+    return fail(TE_ERR_UNSUPPORTED, "te_check_footprint_paths_radius: internal error: the kernels visited %u centres, the plan counted %llu", counters[kPdVisits], n_visits);
+  if (stats) {
+    stats->n_visits = (int)counters[kPdVisits];
+    stats->n_discs = (int)counters[kPdDiscs];
+    stats->n_radius_classes = (int)uniq.size();
+  }
+  return TE_OK;
+}
 
 int te_check_footprint_paths(te_ctx* c, int map, int n_paths, const int* pose_offset, const double* pose_xy,
                              unsigned char* is_safe, double* traversability, int* status) {

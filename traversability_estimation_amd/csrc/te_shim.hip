@@ -193,6 +193,7 @@ void finish_prefetch_locked(te_ctx* c) {
     // whatever was computed from the previous elevation no longer describes the layer, arrived or torn
     c->chain_done = false;
     c->footprint_done = false;
+    c->mask_done = false;
     c->invalid_cells = -1;
     c->invalid_runs = -1;
     if (ok) {
@@ -211,6 +212,7 @@ void finish_prefetch_locked(te_ctx* c) {
     if (mask & (1u << TE_LAYER_ROBOT_SLOPE)) c->have_robot_slope = true;
     if (mask & (1u << TE_LAYER_TRAVERSABILITY)) c->trav_external = c->trav_ptr_out = true;
   }
+  if (mask & (bit(TE_LAYER_SLOPE) | bit(TE_LAYER_STEP) | bit(TE_LAYER_ROUGHNESS))) c->mask_done = false;
 }
 // layers TE_FILTER_* reads and writes (travgpu.h: TE_FILTER_* table)
 unsigned filter_layers(int filter) {
@@ -560,6 +562,7 @@ void free_layers(te_ctx* c) {
   if (c->tie_scratch) (void)hipFree(c->tie_scratch);
   c->tie_scratch = nullptr;
   release_fp_any(c);  // (its prefix sums are sized by the geometry; rebuilt with the tables)
+  release_path_discs(c);  // (its spiral tables are clipped to the map)
   c->have_robot_slope = false;
   memset(&c->L, 0, sizeof(c->L));
   c->layer_elems = 0;
@@ -567,6 +570,7 @@ void free_layers(te_ctx* c) {
   c->have_elev = false;
   c->chain_done = false;
   c->footprint_done = false;
+  c->mask_done = false;
 }
 
 float* layer_ptr(te_ctx* c, int layer) {
@@ -644,6 +648,7 @@ int run_chain_locked(te_ctx* c, unsigned flags, const Region& r) {
   HIP_TRY(launch_chain(c->geo, c->cp, c->L, r, flags, c->stream));
   c->chain_done = true;
   c->footprint_done = false;  // the layers the footprint pass reads have changed
+  c->mask_done = false;
   if (r.map < 0) c->trav_external = false;  // every cell of the combined layer now comes from the chain
   return TE_OK;
 }
@@ -662,6 +667,7 @@ int run_footprint_locked(te_ctx* c, unsigned flags, bool fresh = false) {
                            c->combine_deferred ? &c->cp : nullptr, trav_cap, c->stream));
   c->combine_deferred = false;
   c->footprint_done = true;
+  c->mask_done = true;
   return TE_OK;
 }
 
@@ -721,6 +727,7 @@ int run_whole_locked(te_ctx* c, unsigned flags) {
       c->trav_external = false;  // (as run_chain_locked: every cell of the combined layer now comes from the chain)
       c->chain_done = true;
       c->footprint_done = (flags & TE_RUN_FOOTPRINT) != 0;
+      c->mask_done = c->footprint_done;
       c->combine_deferred = false;
       return TE_OK;
     }
@@ -918,6 +925,9 @@ int te_set_params(te_ctx* c, const te_params* p) {
   // the filter layers stay valid when only the footprint part (fp_*, the tail of the struct) changed:
   // traversabilityFootprint(radius, offset) is called with a new radius on an unchanged map
   if (memcmp(&old, p, offsetof(te_params, fp_radius)) != 0) c->chain_done = false;
+  // ... and the untraversable mask with them, unless one of the three parameters it reads changed (te_ctx.h: mask_done)
+  c->mask_done = c->mask_done && c->chain_done && old.fp_max_gap == p->fp_max_gap &&
+                      old.fp_critical_step == p->fp_critical_step && old.fp_check_roughness == p->fp_check_roughness;
   c->footprint_done = false;
   return TE_OK;
 }
@@ -968,12 +978,14 @@ int te_set_option(te_ctx* c, int option, int value) {
         }
         c->chain_done = false;
         c->footprint_done = false;
+        c->mask_done = false;
       }
       break;
     case TE_OPT_NORMALS_RANK_RULE:
       c->opt_rank_rule = value != 0;
       c->chain_done = false;
       c->footprint_done = false;
+      c->mask_done = false;
       break;
     default:
       return fail(TE_ERR_INVALID_ARG, "te_set_option: unknown option %d", option);
@@ -1061,6 +1073,7 @@ int te_set_geometry(te_ctx* c, int rows, int cols, int batch, double res, double
   c->have_geo = true;
   c->chain_done = false;
   c->footprint_done = false;
+  c->mask_done = false;
   return rebuild_tables(c);
 }
 
@@ -1097,6 +1110,7 @@ int te_run_filter(te_ctx* c, int filter, unsigned flags) {
   // footprint pass and the path checks must not build on them.
   c->chain_done = false;
   c->footprint_done = false;
+  c->mask_done = false;
   c->trav_external = true;
   return TE_OK;
 }
@@ -1120,7 +1134,7 @@ int te_run_chain_region(te_ctx* c, unsigned flags, int map, int row0, int col0, 
   if (!c->chain_done) return fail(TE_ERR_NOT_READY, "te_run_chain_region: run the full chain once first");
   const Region r = {map, row0, col0, row0 + h, col0 + w};
   const bool want_fp = (flags & (TE_RUN_FOOTPRINT | TE_RUN_FOOTPRINT_MEMO)) != 0;
-  const bool fp_was_done = c->footprint_done;
+  const bool fp_was_done = c->footprint_done, mask_was_done = c->mask_done;
   if (want_fp && !fp_was_done)
     return fail(TE_ERR_NOT_READY, "te_run_chain_region: the footprint flag refreshes a complete traversability_footprint layer; run the "
                                   "whole-map footprint pass once first (te_run_chain with TE_RUN_FOOTPRINT, or te_run_footprint)");
@@ -1145,6 +1159,7 @@ int te_run_chain_region(te_ctx* c, unsigned flags, int map, int row0, int col0, 
   HIP_TRY(launch_footprint(c->geo, c->fp, c->L, c->d_spiral, c->fp_clip_table, (flags & TE_RUN_FOOTPRINT_MEMO) != 0, nullptr, trav_cap,
                            c->stream, &changed));
   c->footprint_done = true;  // complete before, refreshed where it could change
+  c->mask_done = mask_was_done;  // (likewise the mask -- unless a score layer was uploaded since it was built)
   return TE_OK;
 }
 

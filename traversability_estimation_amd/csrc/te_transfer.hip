@@ -22,6 +22,7 @@ int te_upload_elevation(te_ctx* c, const float* host, int map0, int nmaps) {
   c->have_elev = true;
   c->chain_done = false;
   c->footprint_done = false;
+  c->mask_done = false;
   return TE_OK;
 }
 
@@ -157,11 +158,13 @@ int te_device_ptr(te_ctx* c, int layer, void** dptr, size_t* bytes) {
   *dptr = p;
   if (bytes) *bytes = c->layer_elems * sizeof(float);
   if (layer == TE_LAYER_TRAVERSABILITY) c->trav_external = c->trav_ptr_out = true;
+  if (layer == TE_LAYER_SLOPE || layer == TE_LAYER_STEP || layer == TE_LAYER_ROUGHNESS) c->mask_done = false;  // (the mask reads them)
   if (layer == TE_LAYER_ELEVATION) {  // caller fills the elevation in place (zero-copy producer)
     c->invalid_cells = -1;
     c->have_elev = true;
     c->chain_done = false;
     c->footprint_done = false;
+    c->mask_done = false;
   }
   return TE_OK;
 }
@@ -191,6 +194,7 @@ int te_upload_layer(te_ctx* c, int layer, const float* host, int map0, int nmaps
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (layer == TE_LAYER_ROBOT_SLOPE) c->have_robot_slope = true;
   if (layer == TE_LAYER_TRAVERSABILITY) c->trav_external = c->trav_ptr_out = true;
+  if (layer == TE_LAYER_SLOPE || layer == TE_LAYER_STEP || layer == TE_LAYER_ROUGHNESS) c->mask_done = false;  // (the mask reads them)
   return TE_OK;
 }
 
@@ -251,9 +255,11 @@ static int upload_layer_circular_checked(te_ctx* c, int layer, const float* host
     c->have_elev = true;
     c->chain_done = false;
     c->footprint_done = false;
+    c->mask_done = false;
   }
   if (layer == TE_LAYER_ROBOT_SLOPE) c->have_robot_slope = true;
   if (layer == TE_LAYER_TRAVERSABILITY) c->trav_external = c->trav_ptr_out = true;
+  if (layer == TE_LAYER_SLOPE || layer == TE_LAYER_STEP || layer == TE_LAYER_ROUGHNESS) c->mask_done = false;  // (the mask reads them)
   return TE_OK;
 }
 

@@ -9,6 +9,7 @@ ROOT = os.path.dirname(PKG)
 LIB = os.path.join(HERE, "libtraversability_estimation_filters.so")
 TEST = os.path.join(HERE, "plugin_chain_test")
 RADIUS_TEST = os.path.join(HERE, "plugin_radius_test")
+PATHS_TEST = os.path.join(HERE, "plugin_paths_test")
 SRCS = ["src/DeviceMap.cpp", "src/SlopeFilter.cpp", "src/StepFilter.cpp", "src/RoughnessFilter.cpp",
         "src/FusedChainFilter.cpp", "src/SurfaceNormalsFilter.cpp", "src/TraversabilityMap.cpp", "stubs/pluginlib/registry.cpp"]
 
@@ -31,6 +32,12 @@ def build(verbose=False):
     # the Step and Roughness plugins at radii above 32 cells (tests/test_plugins_radius.py)
     cmd = cmd[:cmd.index(TEST)] + [RADIUS_TEST]
     cmd[cmd.index(os.path.join(HERE, "test", "plugin_chain_test.cpp"))] = os.path.join(HERE, "test", "plugin_radius_test.cpp")
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    # TraversabilityMap::setPathCheckOnDemand (tests/test_plugins_paths_radius.py)
+    cmd = cmd[:cmd.index(RADIUS_TEST)] + [PATHS_TEST]
+    cmd[cmd.index(os.path.join(HERE, "test", "plugin_radius_test.cpp"))] = os.path.join(HERE, "test", "plugin_paths_test.cpp")
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

@@ -53,6 +53,16 @@ class TraversabilityMap {
    *  one device launch per footprint kind.  Returns false if any path has no poses (its result stays unsafe). */
   bool checkFootprintPaths(const std::vector<traversability_msgs::FootprintPath>& paths,
                            std::vector<traversability_msgs::TraversabilityResult>& results);
+  /*! How circular paths are checked.  Off (the default): per distinct radius of the request a whole-map footprint pass at
+   *  that radius, then the path kernel on the layer -- traversability_footprint and the footprint radius of the parameters
+   *  then belong to the last path check.  On: every circular path of the request goes through ONE call with its own
+   *  path.radius, evaluated on demand at the centres it visits (te_check_footprint_paths_radius), as the reference does
+   *  (:345-462 with isTraversable's on-demand branch); the layer a traversabilityFootprint(radius, offset) call computed and
+   *  the parameters stay as they are. */
+  void setPathCheckOnDemand(bool enabled) {
+    std::lock_guard<std::mutex> lock(mutex_);
+    pathCheckOnDemand_ = enabled;
+  }
   /*! The elevation map's geometry with the layers computed so far (getTraversabilityMap :196-199). */
   grid_map::GridMap getTraversabilityMap();
   bool traversabilityMapInitialized() const { return traversabilityMapInitialized_; }
@@ -68,6 +78,7 @@ class TraversabilityMap {
   grid_map::GridMap geometry_;  // geometry and start index of the last elevation map (no layers)
   bool elevationMapInitialized_, traversabilityMapInitialized_, footprintLayer_, polygonLayers_;
   bool checkRobotInclination_, robotSlopeLayer_;
+  bool pathCheckOnDemand_ = false;
   double footprintRadius_, footprintOffset_;
   double circularFootprintOffset_;  // :348 "TODO: get this with FootprintPath msg" = 0.15
   std::string error_;

@@ -242,6 +242,35 @@ bool TraversabilityMap::checkFootprintPaths(const std::vector<traversability_msg
       results[group[m]].area = area[m];
     }
   }
+  if (pathCheckOnDemand_ && !circular.empty()) {
+    // every circular path of the request in one call, each at its own path.radius, evaluated on demand at the centres it
+    // visits: no footprint pass, and footprintLayer_, footprintRadius_ and params_ stay as they are
+    std::vector<size_t> group;
+    for (size_t k = 0; k < n; ++k)
+      if (paths[k].footprint.polygon.points.empty()) group.push_back(k);
+    std::vector<int> offset(1, 0);
+    std::vector<double> xy, radius;
+    for (size_t k : group) {
+      for (const geometry_msgs::Pose& pose : paths[k].poses.poses) {
+        xy.push_back(pose.position.x);
+        xy.push_back(pose.position.y);
+      }
+      offset.push_back((int)(xy.size() / 2));
+      radius.push_back(paths[k].radius);
+    }
+    std::vector<unsigned char> safe(group.size());
+    std::vector<double> trav(group.size());
+    std::vector<int> status(group.size());
+    if (!check(te_check_footprint_paths_radius(ctx_, 0, (int)group.size(), offset.data(), xy.data(), radius.data(),
+                                               circularFootprintOffset_, safe.data(), trav.data(), status.data(), nullptr)))
+      return false;
+    for (size_t m = 0; m < group.size(); ++m) {
+      results[group[m]].is_safe = safe[m];
+      results[group[m]].traversability = trav[m];
+      results[group[m]].area = 0.0;  // :355: never set for circular footprints
+    }
+    return complete;
+  }
   for (const auto& entry : circular) {
     if (!ensureCircularFootprint(entry.first)) return false;
     const std::vector<size_t>& group = entry.second;
