@@ -41,6 +41,11 @@
  *   te_upload_msg / te_download_msg / te_msg_* / te_bag_*
  *                        <- GridMapRosConverter::fromMessage / toMessage / loadFromBag / saveToBag as called in
  *                           TraversabilityMap.cpp:135-154 and TraversabilityEstimation.cpp:125-152, 248-270, 318-329
+ *   te_image_parse / te_upload_image / te_upload_image_msg
+ *                        <- TraversabilityEstimation::imageCallback, TraversabilityEstimation.cpp:154-168
+ *                           (GridMapRosConverter::initializeFromImage, then addLayerFromImage(image, "elevation", map,
+ *                           min_height, max_height)): the image's own 1 .. 8 bytes per cell cross PCIe, the conversion
+ *                           to float32 and the transposition into the column-major layer run on the device
  *
  * Data contract (identical to grid_map::Matrix = Eigen::MatrixXf): float32, COLUMN-major,
  * element (row i, col j) of map m at ptr[m*rows*cols + j*rows + i]; invalid cell = non-finite.
@@ -442,6 +447,58 @@ int te_bag_find_message(const void* bag, size_t len, const char* topic, size_t* 
 /* saveToBag: a one-message bag (stamp 0.0 is written as ros::TIME_MIN like the reference).  Sizing call as above. */
 int te_bag_write(const void* msg, size_t msg_len, const char* topic, uint32_t stamp_sec, uint32_t stamp_nsec, void* out,
                  size_t cap, size_t* written);
+
+/* ---- sensor_msgs/Image as an input: the reference's image_elevation topic (TraversabilityEstimation.cpp:154-168) ----
+ * Accepted encodings (those of grid_map_ros's switch on the cv type): mono8 / 8UC1, mono16 / 16UC1, rgb8 / bgr8 / 8UC3,
+ * rgba8 / bgra8 / 8UC4, rgb16 / bgr16 / 16UC3, rgba16 / bgra16 / 16UC4.
+ *
+ * Semantics = GridMapCvConverter::addLayerFromImage<Type, N> (restated here: grid_map is not vendored):
+ *   - Cell (row i, col j) of the layer takes image pixel (row i, column j).  The layer ends up in logical order, start
+ *     index 0.  T is uint8 or uint16.  16-bit samples are byte-swapped when is_bigendian differs from the host.
+ *   - maxv = (float)numeric_limits<T>::max().
+ *   - thr = (T)(alpha_threshold * maxv), truncated.  This gives 127 or 32767 at the default 0.5.
+ *   - With 4 channels, a pixel whose last channel is < thr leaves the cell NaN.  (The reference's add(layer) fills NaN
+ *     first.)
+ *   - Otherwise the float32 operations below run without contraction (the build's -ffp-contract=off):
+ *         v = lower + (upper - lower) * ((float)g / maxv)
+ *   - g is the sample itself for 1 channel.
+ *   - For 3 or 4 channels it is the integer grey value
+ *         g = (c0*3735 + c1*19235 + c2*9798 + 16384) >> 15
+ *     c0, c1, c2 are the first three channels IN MEMORY ORDER, WHATEVER THE ENCODING SAYS: grid_map calls
+ *     cvtColor(..., BGR2GRAY) for rgb and bgr alike.  That quirk is reproduced.
+ * The three weights and the shift are OpenCV 4's fixed-point BGR2GRAY as remembered.  Neither OpenCV nor grid_map is part
+ * of this project's build, so the colour branch has no reference-held vector (like the footprint half):
+ * the formula above is a stated contract that nothing here can pin.  The mono and alpha branches have no such doubt.
+ *
+ * Rejected with TE_ERR_INVALID_ARG and a message: any other encoding, a truncated message, step below the row's bytes, a
+ * data length other than step * height, sizes whose product overflows, a NULL pointer, alpha_threshold outside [0, 1],
+ * non-finite lower or upper, and a geometry that is set but whose rows or cols differ from height or width
+ * (addLayerFromImage's "Image size does not correspond to grid map size").  te_upload_image without a geometry:
+ * TE_ERR_NOT_READY.
+ *
+ * After an image went into TE_LAYER_ELEVATION the context is exactly what te_upload_elevation of the same floats leaves
+ * (invalid cells counted -- alpha holes are holes --, elevation present, chain / footprint / mask results dropped); any
+ * other layer follows te_upload_layer.  Both upload calls are synchronous: the host buffer is free on return. */
+typedef struct te_image_info {
+  uint32_t seq, stamp_sec, stamp_nsec; /* header */
+  char frame_id[TE_MSG_MAX_NAME];      /* NUL-terminated */
+  int32_t height, width, step;         /* step = bytes per image row, >= width * channels * bytes_per_channel */
+  int32_t channels, bytes_per_channel; /* 1|3|4, 1|2 */
+  int32_t is_bigendian;
+  char encoding[TE_MSG_MAX_NAME];
+} te_image_info;
+
+/* ROS1 serialisation of sensor_msgs/Image: header, height, width, encoding, is_bigendian, step, data[].  *data_offset =
+ * byte offset of the step * height pixel bytes inside the message. */
+int te_image_parse(const void* msg, size_t len, te_image_info* info, size_t* data_offset);
+/* addLayerFromImage: pixels (height x width, row pitch `step`, any alignment) -> layer `layer` of map `map`.  Reads only
+ * height, width, step, channels, bytes_per_channel and is_bigendian of `info`: a caller with a raw buffer fills those six. */
+int te_upload_image(te_ctx* ctx, const te_image_info* info, const void* pixels, int layer, int map, float lower, float upper,
+                    double alpha_threshold);
+/* imageCallback in one step: parse, (re)set the geometry like initializeFromImage when it differs (batch 1, rows = height,
+ * cols = width, resolution, position), then te_upload_image into map 0.  `info` (may be NULL) receives the description. */
+int te_upload_image_msg(te_ctx* ctx, const void* msg, size_t len, int layer, float lower, float upper, double alpha_threshold,
+                        double resolution, double pos_x, double pos_y, te_image_info* info);
 
 const char* te_last_error(void);
 const char* te_version(void);

@@ -5,6 +5,8 @@ shared library is missing this module raises, and without a gfx950 device te_cre
 """
 import ctypes as C
 import os
+import struct
+import sys
 
 import numpy as np
 
@@ -41,7 +43,8 @@ SYMBOLS = ["te_params_default", "te_params_validate", "te_device_count", "te_cre
            "te_bag_write", "te_run_polygon_footprint", "te_polygons_traversable",
            "te_check_polygon_footprint_paths", "te_pin_host", "te_unpin_host", "te_path_polygons",
            "te_shard_range", "te_bcast_params", "te_run_chain_multi", "te_sync_multi",
-           "te_set_check_robot_inclination", "te_check_inclination", "te_polygon_untraversable_hull"]
+           "te_set_check_robot_inclination", "te_check_inclination", "te_polygon_untraversable_hull",
+           "te_image_parse", "te_upload_image", "te_upload_image_msg"]
 MSG_MAX_NAME = 64
 
 
@@ -87,6 +90,21 @@ class TeMsgInfo(C.Structure):
                 ("pose", C.c_double * 7),
                 ("rows", C.c_int32), ("cols", C.c_int32), ("start_row", C.c_int32), ("start_col", C.c_int32),
                 ("n_layers", C.c_int32), ("n_basic_layers", C.c_int32)]
+
+
+class TeImageInfo(C.Structure):
+    """te_image_info: a sensor_msgs/Image without its pixels."""
+    _fields_ = [("seq", C.c_uint32), ("stamp_sec", C.c_uint32), ("stamp_nsec", C.c_uint32),
+                ("frame_id", C.c_char * MSG_MAX_NAME),
+                ("height", C.c_int32), ("width", C.c_int32), ("step", C.c_int32),
+                ("channels", C.c_int32), ("bytes_per_channel", C.c_int32), ("is_bigendian", C.c_int32),
+                ("encoding", C.c_char * MSG_MAX_NAME)]
+
+
+# encoding name -> (channels, bytes per channel): the encodings te_image_parse accepts
+IMAGE_ENCODINGS = {"mono8": (1, 1), "8UC1": (1, 1), "mono16": (1, 2), "16UC1": (1, 2),
+                   "rgb8": (3, 1), "bgr8": (3, 1), "8UC3": (3, 1), "rgba8": (4, 1), "bgra8": (4, 1), "8UC4": (4, 1),
+                   "rgb16": (3, 2), "bgr16": (3, 2), "16UC3": (3, 2), "rgba16": (4, 2), "bgra16": (4, 2), "16UC4": (4, 2)}
 
 
 class TePathCheckStats(C.Structure):
@@ -189,6 +207,10 @@ def load():
                                       C.c_size_t, szp]
         L.te_bag_find_message.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, szp, szp]
         L.te_bag_write.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_uint32, C.c_uint32, vp, C.c_size_t, szp]
+        L.te_image_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(TeImageInfo), szp]
+        L.te_upload_image.argtypes = [vp, C.POINTER(TeImageInfo), vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_double]
+        L.te_upload_image_msg.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double,
+                                          C.c_double, C.c_double, C.POINTER(TeImageInfo)]
         L.te_last_error.restype = C.c_char_p
         L.te_version.restype = C.c_char_p
         _lib = L
@@ -283,6 +305,36 @@ def bag_write(msg, topic, stamp=(0, 0)):
     out = C.create_string_buffer(max(need.value, 1))
     _check(L.te_bag_write(msg, len(msg), topic.encode(), int(stamp[0]), int(stamp[1]), out, need.value, C.byref(need)))
     return out.raw[:need.value]
+
+
+def image_parse(msg):
+    """Validate a serialised sensor_msgs/Image; returns (TeImageInfo, byte offset of its step * height pixel bytes)."""
+    info, off = TeImageInfo(), C.c_size_t()
+    _check(load().te_image_parse(msg, len(msg), C.byref(info), C.byref(off)))
+    return info, off.value
+
+
+def _image_array(array):
+    a = np.asarray(array)
+    if a.dtype not in (np.uint8, np.uint16) or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3, 4)):
+        raise ValueError(f"image: H x W or H x W x (1|3|4) of uint8 / uint16, not {a.dtype} {a.shape}")
+    return a
+
+
+def image_msg(array, encoding, step=None, is_bigendian=0, frame_id="map", seq=0, stamp=(0, 0), pad=0xA5):
+    """The ROS1 serialisation of a sensor_msgs/Image (pure Python): `array` is H x W or H x W x C of uint8 / uint16 sample
+    values, written in the byte order `is_bigendian` names, rows `step` bytes apart (default: packed; the bytes between
+    rows are `pad`).  `encoding` is written as given -- also one the parser refuses."""
+    a = _image_array(array)
+    h, w = a.shape[:2]
+    rows = np.ascontiguousarray(a.astype(a.dtype.newbyteorder(">" if is_bigendian else "<"))).view(np.uint8).reshape(h, -1)
+    step = rows.shape[1] if step is None else int(step)
+    data = np.full((h, max(step, rows.shape[1])), pad, np.uint8)
+    data[:, :rows.shape[1]] = rows
+    data = data[:, :step].tobytes() if step < rows.shape[1] else data.tobytes()  # (a step below the row: for the parser to refuse)
+    f, e = frame_id.encode(), encoding.encode()
+    return (struct.pack("<IIII", seq, stamp[0], stamp[1], len(f)) + f + struct.pack("<III", h, w, len(e)) + e +
+            struct.pack("<BII", 1 if is_bigendian else 0, step, len(data)) + data)
 
 
 def pin_host(array):
@@ -541,6 +593,32 @@ class Context:
         _check(load().te_upload_msg(self._h, msg, len(msg), layer_name.encode(),
                                     LAYERS[layer] if isinstance(layer, str) else int(layer), C.byref(info)))
         self.rows, self.cols, self.batch = info.rows, info.cols, 1
+        return info
+
+    def upload_image(self, array, encoding=None, lower=0.0, upper=1.0, alpha_threshold=0.5, layer="elevation", map_index=0):
+        """addLayerFromImage on the device: an H x W or H x W x C array of uint8 / uint16 (host byte order) into `layer`.
+        The array's own row stride is the image's step when its pixels are packed within a row; the encoding defaults from
+        dtype and channel count and only decides the layout (the grey value takes the channels in memory order)."""
+        a = _image_array(array)
+        ch = 1 if a.ndim == 2 else a.shape[2]
+        if encoding is not None and IMAGE_ENCODINGS.get(encoding) != (ch, a.itemsize):
+            raise ValueError(f"encoding {encoding!r} does not describe {ch} channels of {a.itemsize} bytes")
+        packed = a.strides[1:] == ((ch * a.itemsize, a.itemsize) if a.ndim == 3 else (a.itemsize,))
+        if not packed or a.strides[0] < a.shape[1] * ch * a.itemsize or a.strides[0] >= 2 ** 31 or a.shape[0] == 1:
+            a = np.ascontiguousarray(a)
+        info = TeImageInfo(height=a.shape[0], width=a.shape[1], step=a.strides[0], channels=ch, bytes_per_channel=a.itemsize,
+                           is_bigendian=1 if sys.byteorder == "big" else 0)
+        _check(load().te_upload_image(self._h, C.byref(info), C.c_void_p(a.ctypes.data),
+                                      LAYERS[layer] if isinstance(layer, str) else int(layer), int(map_index), float(lower),
+                                      float(upper), float(alpha_threshold)))
+
+    def upload_image_msg(self, msg, resolution, position=(0.0, 0.0), lower=0.0, upper=1.0, alpha_threshold=0.5, layer="elevation"):
+        """imageCallback: the geometry from the image's size, `resolution` and `position`, its pixels into `layer`."""
+        info = TeImageInfo()
+        _check(load().te_upload_image_msg(self._h, msg, len(msg), LAYERS[layer] if isinstance(layer, str) else int(layer),
+                                          float(lower), float(upper), float(alpha_threshold), float(resolution),
+                                          float(position[0]), float(position[1]), C.byref(info)))
+        self.rows, self.cols, self.batch = info.height, info.width, 1
         return info
 
     def download_msg(self, info, layers, basic_layers=()):

@@ -142,6 +142,10 @@ struct te_ctx {
   int in_next = 0, out_next = 0;
   bool tiles_pending = false;  // te_sync has copy streams to wait for
   te::HostStager stager;           // whole-layer transfers through pageable host buffers (te_stage.hip)
+  // te_upload_image: the raw image bytes on the device (te_image.hip converts and transposes them into a layer); grown to
+  // the largest image so far, freed with the layers
+  void* img_stage = nullptr;
+  size_t img_stage_bytes = 0;
   // te_prefetch_layers: whole-layer uploads on a thread of their own, through a second staging ring and the second copy
   // pool, beside whatever the caller does meanwhile (a filter on other layers, the download of its output)
   te::HostStager prefetcher;

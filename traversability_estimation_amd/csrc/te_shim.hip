@@ -561,6 +561,9 @@ void free_layers(te_ctx* c) {
   c->robot_slope = nullptr;
   if (c->tie_scratch) (void)hipFree(c->tie_scratch);
   c->tie_scratch = nullptr;
+  if (c->img_stage) (void)hipFree(c->img_stage);
+  c->img_stage = nullptr;
+  c->img_stage_bytes = 0;
   release_fp_any(c);  // (its prefix sums are sized by the geometry; rebuilt with the tables)
   release_path_discs(c);  // (its spiral tables are clipped to the map)
   c->have_robot_slope = false;

@@ -1,7 +1,9 @@
 // te_transfer.hip -- C-ABI of libtravgpu.so, the transfers (include/travgpu.h): whole layers, tiles (synchronous and on the
 // copy streams), GridMap's circular-buffer order, grid_map_msgs/GridMap messages and bags, whole-layer prefetches beside
-// the caller's own work, page-locking.  The context and the helpers shared with the other parts: te_ctx.h.
+// the caller's own work, page-locking, sensor_msgs/Image (parser and kernel: te_image.hip).  The context and the helpers
+// shared with the other parts: te_ctx.h.
 #include "te_ctx.h"
+#include "te_image.h"
 
 using namespace te;
 using namespace te::shim;
@@ -348,6 +350,100 @@ int te_upload_msg(te_ctx* c, const void* m, size_t len, const char* layer_name, 
   // the payload may be unaligned: it is only ever handed to the copy engine
   return upload_layer_circular_checked(c, layer, reinterpret_cast<const float*>((const uint8_t*)m + l->data_off), 0, mi.start_row,
                                        mi.start_col, mi.rows, mi.cols);
+}
+
+int te_image_parse(const void* m, size_t len, te_image_info* info, size_t* data_offset) {
+  if (!m || !info || !data_offset) return fail(TE_ERR_INVALID_ARG, "te_image_parse: NULL");
+  std::string err;
+  te_image_info mi;
+  size_t off = 0;
+  if (!img::parse((const uint8_t*)m, len, mi, off, err)) return fail(TE_ERR_INVALID_ARG, "te_image_parse: %s", err.c_str());
+  *info = mi;
+  *data_offset = off;
+  return TE_OK;
+}
+
+// what te_upload_image and te_upload_image_msg check before they touch the context
+static int check_image_args(const char* who, const te_image_info* info, float lower, float upper, double alpha_threshold) {
+  std::string err;
+  if (!img::check_layout(*info, err)) return fail(TE_ERR_INVALID_ARG, "%s: %s", who, err.c_str());
+  if (!isfinite(lower) || !isfinite(upper)) return fail(TE_ERR_INVALID_ARG, "%s: lower = %g, upper = %g", who, (double)lower, (double)upper);
+  if (!(alpha_threshold >= 0.0 && alpha_threshold <= 1.0)) return fail(TE_ERR_INVALID_ARG, "%s: alpha_threshold %g outside [0, 1]", who, alpha_threshold);
+  return TE_OK;
+}
+
+static int upload_image_checked(const char* who, te_ctx* c, const te_image_info* info, const void* pixels, int layer, int map, float lower,
+                                float upper, double alpha_threshold) {
+  if (!c || !info || !pixels) return fail(TE_ERR_INVALID_ARG, "%s: NULL", who);
+  if (const int rc = check_image_args(who, info, lower, upper, alpha_threshold)) return rc;
+  CtxLock lk(c);
+  if (!c->have_geo) return fail(TE_ERR_NOT_READY, "%s: geometry not set", who);
+  if (c->geo.rows != info->height || c->geo.cols != info->width)
+    return fail(TE_ERR_INVALID_ARG, "%s: image size %d x %d does not correspond to grid map size %d x %d", who, info->height, info->width,
+                c->geo.rows, c->geo.cols);
+  if (const int rc = ensure_input_layer(c, layer)) return rc;
+  float* p = layer_ptr(c, layer);
+  if (!p) return fail(TE_ERR_INVALID_ARG, "%s: bad layer %d", who, layer);
+  if (map < 0 || map >= c->geo.batch) return fail(TE_ERR_INVALID_ARG, "%s: map %d of batch %d", who, map, c->geo.batch);
+  HIP_TRY(hipSetDevice(c->device));
+  // the image as it is -- 1 .. 8 bytes per cell -- into the context's staging buffer, then one kernel into the layer
+  const size_t bytes = img::payload_bytes(*info);
+  if (c->img_stage_bytes < bytes + img::kStagePad) {
+    if (c->img_stage) {
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      (void)hipFree(c->img_stage);
+      c->img_stage = nullptr;
+      c->img_stage_bytes = 0;
+    }
+    HIP_TRY(hipMalloc(&c->img_stage, bytes + img::kStagePad));
+    c->img_stage_bytes = bytes + img::kStagePad;
+  }
+  HIP_TRY(c->stager.upload(c->img_stage, pixels, bytes, c->stream));
+  HIP_TRY(img::launch_to_layer(c->img_stage, *info, p + (size_t)map * c->geo.rows * c->geo.cols, lower, upper,
+                               img::alpha_threshold_sample(alpha_threshold, info->bytes_per_channel), c->stream));
+  if (layer == TE_LAYER_ELEVATION) {
+    // (the count also waits for the copy and the kernel: the host buffer may be reused as soon as we return)
+    if (const int rc = count_invalid_elevation(c)) return rc;
+    c->have_elev = true;
+    c->chain_done = false;
+    c->footprint_done = false;
+    c->mask_done = false;
+  } else {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  if (layer == TE_LAYER_ROBOT_SLOPE) c->have_robot_slope = true;
+  if (layer == TE_LAYER_TRAVERSABILITY) c->trav_external = c->trav_ptr_out = true;
+  if (layer == TE_LAYER_SLOPE || layer == TE_LAYER_STEP || layer == TE_LAYER_ROUGHNESS) c->mask_done = false;  // (the mask reads them)
+  return TE_OK;
+}
+
+int te_upload_image(te_ctx* c, const te_image_info* info, const void* pixels, int layer, int map, float lower, float upper,
+                    double alpha_threshold) {
+  return upload_image_checked("te_upload_image", c, info, pixels, layer, map, lower, upper, alpha_threshold);
+}
+
+int te_upload_image_msg(te_ctx* c, const void* m, size_t len, int layer, float lower, float upper, double alpha_threshold,
+                        double resolution, double pos_x, double pos_y, te_image_info* info) {
+  if (!c || !m) return fail(TE_ERR_INVALID_ARG, "te_upload_image_msg: NULL");
+  std::string err;
+  te_image_info mi;
+  size_t off = 0;
+  if (!img::parse((const uint8_t*)m, len, mi, off, err)) return fail(TE_ERR_INVALID_ARG, "te_upload_image_msg: %s", err.c_str());
+  if (const int rc = check_image_args("te_upload_image_msg", &mi, lower, upper, alpha_threshold)) return rc;
+  // initializeFromImage: the map takes the image's size (rows = height, cols = width), the resolution and the position
+  bool same;
+  {
+    CtxLock lk(c);
+    same = c->have_geo && c->geo.rows == mi.height && c->geo.cols == mi.width && c->geo.batch == 1 && c->geo.res == resolution &&
+           c->geo.pos_x == pos_x && c->geo.pos_y == pos_y;
+  }
+  if (!same) {
+    const int rc = te_set_geometry(c, mi.height, mi.width, 1, resolution, pos_x, pos_y);
+    if (rc != TE_OK) return rc;
+  }
+  if (info) *info = mi;
+  // (a geometry another thread set in between is refused by the size check)
+  return upload_image_checked("te_upload_image_msg", c, &mi, (const uint8_t*)m + off, layer, 0, lower, upper, alpha_threshold);
 }
 
 int te_download_msg(te_ctx* c, const te_msg_info* info, int n_layers, const int* layers, const char* const* names, int n_basic,

@@ -10,6 +10,7 @@ LIB = os.path.join(HERE, "libtraversability_estimation_filters.so")
 TEST = os.path.join(HERE, "plugin_chain_test")
 RADIUS_TEST = os.path.join(HERE, "plugin_radius_test")
 PATHS_TEST = os.path.join(HERE, "plugin_paths_test")
+IMAGE_TEST = os.path.join(HERE, "plugin_image_test")
 SRCS = ["src/DeviceMap.cpp", "src/SlopeFilter.cpp", "src/StepFilter.cpp", "src/RoughnessFilter.cpp",
         "src/FusedChainFilter.cpp", "src/SurfaceNormalsFilter.cpp", "src/TraversabilityMap.cpp", "stubs/pluginlib/registry.cpp"]
 
@@ -38,6 +39,12 @@ def build(verbose=False):
     # TraversabilityMap::setPathCheckOnDemand (tests/test_plugins_paths_radius.py)
     cmd = cmd[:cmd.index(RADIUS_TEST)] + [PATHS_TEST]
     cmd[cmd.index(os.path.join(HERE, "test", "plugin_radius_test.cpp"))] = os.path.join(HERE, "test", "plugin_paths_test.cpp")
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    # TraversabilityMap::setElevationFromImage (tests/test_plugins_image.py)
+    cmd = cmd[:cmd.index(PATHS_TEST)] + [IMAGE_TEST]
+    cmd[cmd.index(os.path.join(HERE, "test", "plugin_paths_test.cpp"))] = os.path.join(HERE, "test", "plugin_image_test.cpp")
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

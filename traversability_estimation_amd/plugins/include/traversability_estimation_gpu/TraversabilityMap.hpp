@@ -14,6 +14,7 @@
 #include <vector>
 
 #include <grid_map_core/GridMap.hpp>
+#include <sensor_msgs/Image.h>
 #include <traversability_msgs/FootprintPath.h>
 #include <traversability_msgs/TraversabilityResult.h>
 
@@ -40,6 +41,13 @@ class TraversabilityMap {
   bool setCheckRobotInclination(bool enabled);
   /*! setElevationMap (:135-154): needs the layer "elevation"; any start index.  A layer "robot_slope" goes along. */
   bool setElevationMap(const grid_map::GridMap& elevationMap);
+  /*! imageCallback's body (TraversabilityEstimation.cpp:154-168) on the device: initializeFromImage -- the map takes the
+   *  image's size (rows = height, cols = width), `resolution` and `position` -- then addLayerFromImage(image, "elevation",
+   *  map, minHeight, maxHeight).  The image's own bytes cross PCIe (te_upload_image); computeTraversability() then works
+   *  from it as it does after setElevationMap.  False + error() for an encoding grid_map_ros refuses or a data size that is
+   *  not step * height.  An image carries no layer "robot_slope". */
+  bool setElevationFromImage(const sensor_msgs::Image& image, double resolution, const grid_map::Position& position,
+                             double minHeight, double maxHeight);
   /*! computeTraversability (:202-237): the filter chain; false if no elevation map has been set. */
   bool computeTraversability();
   /*! traversabilityFootprint(radius, offset) (:307-318): layer traversability_footprint. */

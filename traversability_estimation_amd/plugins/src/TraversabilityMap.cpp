@@ -2,6 +2,8 @@
 
 #include <cmath>
 #include <map>
+#include <string>
+#include <utility>
 
 #include <ros/ros.h>
 
@@ -85,6 +87,50 @@ bool TraversabilityMap::setElevationMap(const grid_map::GridMap& elevationMap) {
   geometry_ = grid_map::GridMap();
   geometry_.setGeometry(elevationMap.getLength(), elevationMap.getResolution(), elevationMap.getPosition());
   geometry_.setStartIndex(start);
+  elevationMapInitialized_ = true;
+  traversabilityMapInitialized_ = false;
+  footprintLayer_ = polygonLayers_ = false;
+  return true;
+}
+
+bool TraversabilityMap::setElevationFromImage(const sensor_msgs::Image& image, double resolution, const grid_map::Position& position,
+                                              double minHeight, double maxHeight) {
+  std::lock_guard<std::mutex> lock(mutex_);
+  if (!ctx_) return false;
+  // the encodings grid_map_ros's addLayerFromImage takes (its switch on the cv type): channels, bytes per channel
+  static const std::map<std::string, std::pair<int, int>> layouts = {
+      {"mono8", {1, 1}},  {"8UC1", {1, 1}},  {"mono16", {1, 2}}, {"16UC1", {1, 2}},  {"rgb8", {3, 1}},   {"bgr8", {3, 1}},
+      {"8UC3", {3, 1}},   {"rgba8", {4, 1}}, {"bgra8", {4, 1}},  {"8UC4", {4, 1}},   {"rgb16", {3, 2}},  {"bgr16", {3, 2}},
+      {"16UC3", {3, 2}},  {"rgba16", {4, 2}}, {"bgra16", {4, 2}}, {"16UC4", {4, 2}}};
+  const auto layout = layouts.find(image.encoding);
+  if (layout == layouts.end()) {
+    error_ = "setElevationFromImage: encoding '" + image.encoding + "'";
+    ROS_ERROR("Expected MONO8, MONO16, RGB(A)8, RGB(A)16, BGR(A)8, or BGR(A)16 image encoding.");
+    return false;
+  }
+  if (image.height == 0 || image.width == 0 || image.height > 0x7fffffffu || image.width > 0x7fffffffu || image.step > 0x7fffffffu ||
+      image.data.size() != (size_t)image.step * image.height) {
+    error_ = "setElevationFromImage: image size, step and data length do not fit";
+    ROS_ERROR("TraversabilityMap (MI355X): %s", error_.c_str());
+    return false;
+  }
+  te_image_info info = te_image_info();
+  info.height = (int32_t)image.height;
+  info.width = (int32_t)image.width;
+  info.step = (int32_t)image.step;
+  info.channels = layout->second.first;
+  info.bytes_per_channel = layout->second.second;
+  info.is_bigendian = image.is_bigendian;
+  // initializeFromImage: length = resolution * (height, width)
+  if (!check(te_set_geometry(ctx_, info.height, info.width, 1, resolution, position.x(), position.y()))) return false;
+  if (!check(te_upload_image(ctx_, &info, image.data.data(), TE_LAYER_ELEVATION, 0, (float)minHeight, (float)maxHeight, 0.5))) return false;
+  robotSlopeLayer_ = false;
+  (void)te_set_layer_present(ctx_, TE_LAYER_ROBOT_SLOPE, 0);  // (as setElevationMap does for a map without the layer)
+  geometry_ = grid_map::GridMap();
+  grid_map::Length length;
+  length(0) = resolution * info.height;
+  length(1) = resolution * info.width;
+  geometry_.setGeometry(length, resolution, position);
   elevationMapInitialized_ = true;
   traversabilityMapInitialized_ = false;
   footprintLayer_ = polygonLayers_ = false;

@@ -15,7 +15,10 @@ struct Vec2d {
   double x() const { return v[0]; }
   double y() const { return v[1]; }
   double operator()(int k) const { return v[k]; }
+  double& operator()(int k) { return v[k]; }
 };
+typedef Vec2d Position;  // (grid_map::Position = Eigen::Vector2d, grid_map::Length = Eigen::Array2d)
+typedef Vec2d Length;
 struct Arr2i {
   int v[2];
   int operator()(int k) const { return v[k]; }
