@@ -186,7 +186,17 @@ int te_get_params(te_ctx* ctx, te_params* p);
  * while a 40-cell radius is held -- TE_ERR_UNSUPPORTED, and the option and the discs stay as they were.  te_bcast_params
  * carries parameters only: each receiving context needs the option set as well.  The C++ plugins set 1. */
 #define TE_OPT_FILTER_ANY_RADIUS 8
+/* Face flags: a whole-layer elevation upload also records, per 64 x 4 cells, whether a drop of more than fp_critical_step
+ * between adjacent cells lies within 2 cells; the mask kernel of the footprint pass skips its step-check staging on tiles
+ * without one.  1 (default): the flags are passed whenever they are known (they are not after tile uploads, te_device_ptr
+ * of the elevation, a failed prefetch, or a te_set_params that changed fp_critical_step -- until the next whole upload);
+ * 0: never.  The layers are identical either way. */
+#define TE_OPT_FACE_FLAGS 9
 int te_set_option(te_ctx* ctx, int option, int value);
+/* The face flags a footprint run would be given now (tests, diagnostics): batch x ceil(cols / 4) x ceil(rows / 64) bytes, the
+ * flag of 64 cells along the rows fastest; `bytes` must be exactly that.  TE_ERR_NOT_READY while they are unknown or
+ * switched off. */
+int te_download_face_flags(te_ctx* ctx, unsigned char* out, size_t bytes);
 /* rows = size(0), cols = size(1) of every map of the batch; (pos_x,pos_y) = map centre. */
 int te_set_geometry(te_ctx* ctx, int rows, int cols, int batch, double resolution, double pos_x, double pos_y);
 

@@ -30,11 +30,12 @@ RUN_SEQUENTIAL = 0x10
 RUN_NORMALS_ONLY = 0x20
 OPT_FP_BLOCKED_WALK, OPT_FP_BLOCKED_BLOCKS_PER_CU, OPT_POLYGON_PER_CELL, OPT_GRAPH_REPLAY, OPT_BCAST_RCCL, OPT_NORMALS_RANK_RULE = 1, 2, 3, 4, 5, 6
 OPT_FP_ANY_REACH = 7  # circular footprint: 0 routes by reach (above 20 cells: the route of any reach), 1 that route always
+OPT_FACE_FLAGS = 9  # mask kernel of the footprint pass: 1 (default) skips the step-check staging on tiles the upload found without a vertical face, 0 never (identical layers)
 OPT_FILTER_ANY_RADIUS = 8  # filter discs: 0 up to 32 cells (TE_ERR_UNSUPPORTED above), 1 any radius, 2 the route of any radius for every disc
 
 # every symbol include/travgpu.h declares (tests/test_cabi.py checks the library exports them all)
 SYMBOLS = ["te_params_default", "te_params_validate", "te_device_count", "te_create", "te_destroy",
-           "te_set_params", "te_get_params", "te_set_option", "te_set_geometry", "te_upload_elevation", "te_upload_tile", "te_download_tile",
+           "te_set_params", "te_get_params", "te_set_option", "te_download_face_flags", "te_set_geometry", "te_upload_elevation", "te_upload_tile", "te_download_tile",
            "te_upload_tile_async", "te_download_tile_async",
            "te_device_ptr", "te_set_layer_present", "te_upload_layer", "te_prefetch_layers", "te_wait_prefetch", "te_upload_layer_circular", "te_download_layer_circular", "te_run_filter", "te_run_chain", "te_run_chain_region", "te_run_footprint", "te_check_footprint_paths", "te_check_footprint_paths_radius",
            "te_sync",
@@ -152,6 +153,8 @@ def load():
         L.te_set_params.argtypes = [vp, pp]
         L.te_get_params.argtypes = [vp, pp]
         L.te_set_option.argtypes = [vp, C.c_int, C.c_int]
+        if "TRAVGPU_LIB" not in os.environ or hasattr(L, "te_download_face_flags"):  # (as below: an A/B library of an earlier round)
+            L.te_download_face_flags.argtypes = [vp, C.POINTER(C.c_ubyte), C.c_size_t]
         L.te_set_geometry.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]
         L.te_upload_elevation.argtypes = [vp, fp, C.c_int, C.c_int]
         L.te_upload_tile.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -408,6 +411,12 @@ class Context:
 
     def set_option(self, option, value):
         _check(load().te_set_option(self._h, int(option), int(value)))
+
+    def download_face_flags(self):
+        """(batch, ceil(cols / 4), ceil(rows / 64)) uint8: the face flags a footprint run would be given now."""
+        out = np.empty((self.batch, (self.cols + 3) // 4, (self.rows + 63) // 64), np.uint8)
+        _check(load().te_download_face_flags(self._h, out.ctypes.data_as(C.POINTER(C.c_ubyte)), out.size))
+        return out
 
     def get_params(self):
         p = TeParams()

@@ -116,6 +116,15 @@ struct te_ctx {
   long long invalid_cells = -1;
   long long invalid_runs = -1;  // runs of invalid cells in memory order (k_count_invalid); meaningful with invalid_cells >= 0
   unsigned long long* d_count = nullptr;
+  // face flags (te_face_flags.h): built by the same pass over the whole elevation layer, for the fp_critical_step held then.
+  // face_crit: that value; NaN: unknown -- whatever makes invalid_cells unknown (tiles, the
+  // device pointer, a failed prefetch), or a te_set_params that changed fp_critical_step.  The bytes live in the slab.
+  uint8_t* face_flags = nullptr;
+  double face_crit = __builtin_nan("");
+  // te_device_ptr handed out the elevation layer: the caller may write it at any time from then on, behind any later upload's
+  // pass -- the flags are never passed again until the layers are allocated anew (te_set_geometry with another shape)
+  bool elev_ptr_out = false;
+  int opt_face_flags = 1;  // TE_OPT_FACE_FLAGS
   char* hole_queue = nullptr;  // scratch of k_normals3's sparse-hole march (allocated when a launch first picks it)
   float* tie_scratch = nullptr;  // one float per cell: the step filter at a tie radius (allocated when a launch first needs it, freed with the layers)
   bool tables_ready = false;
@@ -179,8 +188,10 @@ struct CtxLock {
   }
 };
 constexpr unsigned bit(int layer) { return (layer >= 0 && layer < 32) ? 1u << layer : 0u; }
-// counts the invalid cells of the whole elevation layer on the context's stream and waits for the result
+// counts the invalid cells of the whole elevation layer on the context's stream, builds its face flags and waits for the result
 int count_invalid_elevation(te_ctx* c);
+// the face flags a mask launch may read now (nullptr: unknown, or switched off)
+const uint8_t* usable_face_flags(const te_ctx* c);
 float* layer_ptr(te_ctx* c, int layer);
 int ensure_input_layer(te_ctx* c, int layer);
 int rebuild_tables(te_ctx* c);

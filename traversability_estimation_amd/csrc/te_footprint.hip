@@ -371,6 +371,10 @@ struct MaskArgs {
   // every flag of its strip is clear.)
   uint8_t* untrav_flags;
   int flag_ntx, flag_nfy;
+  // the same grid (te_face_flags.h), built from the elevation at upload: "a cell within 2 cells of these 64 x 4 lies more than
+  // crit_step above a cell of its 3x3 block".  A tile whose bytes are all clear has no lower step neighbour whatever the
+  // step scores are: it takes the flat path below.  nullptr: unknown, every tile stages its step check.
+  const uint8_t* face_flags;
   int whatif;  // lab library only (TE_MASK_WHATIF; 0 in the product): 1 no pair masks are evaluated, 2 the slow cells are not decided
 };
 
@@ -400,6 +404,17 @@ __global__ __launch_bounds__(MX* MBY) __attribute__((amdgpu_waves_per_eu(4, 4)))
   // (the footprint pass's list of blocked cells starts empty: k_fp_slide4 / k_fp_blocked run after this kernel)
   if (a.blocked_count && threadIdx.x == 0 && threadIdx.y == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)
     a.blocked_count[0] = a.blocked_count[1] = a.blocked_count[4] = 0u;
+  // A flat tile (uniform per block): its face flags are clear, so no cell that its t_kl would cover has a lower step
+  // neighbour -- `hit` below implies the flags' test cell by cell, te_face_flags.h -- and tile_has_kl would come out false:
+  // the screen clears every step check (the windows have nothing to find) and nothing reads t_elev / t_key / t_kl.  Such a
+  // tile loads neither the elevation nor the step halo, writes no tile and runs no minimum pass.  Not next to a border whose
+  // submap lookups fail: there check_step decides on the staged tiles.
+  const bool q5 = a.step_disc.Q == 5 && a.step_disc.n_ties == 0;
+  bool flat = false;
+  if (a.face_flags != nullptr && q5 && a.whatif == 0)
+    flat = face_tile_clear(a.face_flags, g.rows, g.cols, a.map >= 0 ? a.map : (int)blockIdx.z, i0, j0, MY) &&
+           !(a.edge_fail != 0 && face_tile_near_failing_border(g.rows, g.cols, a.edge_fail, i0, j0, MX, MY));
+  flat = __builtin_amdgcn_readfirstlane(flat ? 1 : 0) != 0;
   // my tile's flags (flag rows j0 / 4 .. of flag column i0 / 64: i0 and j0 are multiples of 64 and of MY)
   uint8_t* const my_flags = a.untrav_flags + ((size_t)(a.map >= 0 ? a.map : (int)blockIdx.z) * a.flag_nfy) * a.flag_ntx + (i0 >> 6);
   {
@@ -427,7 +442,7 @@ __global__ __launch_bounds__(MX* MBY) __attribute__((amdgpu_waves_per_eu(4, 4)))
     s_step[c] = step[o];
     s_rough[c] = (a.check_rough || a.combine) ? rough[o] : 1.0f;
   });
-  {
+  if (!flat) {
     // all loads of the tile in flight at once (clamped addresses), then the LDS writes.  A thread stages its own column
     // (tile column threadIdx.x + MH) in the tile rows threadIdx.y, + MBY, ... -- one clamped column, row offsets that are
     // multiples of MBY map rows, LDS addresses that differ by constants -- and the first 2 * MH * MTH threads one cell of
@@ -478,9 +493,10 @@ __global__ __launch_bounds__(MX* MBY) __attribute__((amdgpu_waves_per_eu(4, 4)))
       t_key[idx] = (in && hs == 0.0f) ? he : qnanf();
     }
   }
+  // (both paths: the counters zeroed above and the cleared flags of my tile are in place before any wavefront goes on)
   __syncthreads();
   bool any_kl = false;  // some cell of my share has a lower step neighbour (see below: without one in the whole tile the windows have nothing to find)
-  {
+  if (!flat) {
     // t_kl for the tile cells the windows can reach (rows 1..MTH-2, columns 1..MTW-2): the 3x3 minimum of
     // t_key slides down a column (row minimum of 3 cells, then the minimum of 3 consecutive rows).
     // Columns 2..65 are walked by the 64 lanes (MTH-2 = 36 rows in MBY segments of 9); the four remaining
@@ -522,7 +538,8 @@ __global__ __launch_bounds__(MX* MBY) __attribute__((amdgpu_waves_per_eu(4, 4)))
   // vertical faces -- a drop of more than crit_step between adjacent cells -- no tile does, t_kl is NaN throughout, both
   // branches of the screen's test are false for every cell (NaN > thr, NaN == NaN) and the window maxima need not be
   // formed at all: a third of the kernel's instructions on the bench map, where the step score is 0 in 98 % of the cells)
-  const bool tile_has_kl = __syncthreads_or(any_kl ? 1 : 0) != 0;
+  // (a flat tile has none by construction and skips the barrier: `flat` is uniform per block)
+  const bool tile_has_kl = flat ? false : __syncthreads_or(any_kl ? 1 : 0) != 0;
   const TileView ve = {t_elev, elev + mo, i0, j0, g.rows, MTH}, vs = {nullptr, step + mo, i0, j0, g.rows, MTH},
                  vl = {nullptr, slope + mo, i0, j0, g.rows, MTH}, vr = {nullptr, rough + mo, i0, j0, g.rows, MTH};
   const bool in_map = i < g.rows;  // (a thread beyond the last column takes no cells of its own but helps with the list below)
@@ -530,7 +547,6 @@ __global__ __launch_bounds__(MX* MBY) __attribute__((amdgpu_waves_per_eu(4, 4)))
   // (di^2+dj^2 <= 5: rows dj=0,+-1 span |di|<=2, rows dj=+-2 span |di|<=1) the two window maxima slide:
   // each tile row is reduced once along i (H1 = max over |di|<=1, H2 = max over |di|<=2: 5 LDS reads and
   // 2 v_max3 per array) and an output combines the run values of its 5 rows with 2 more v_max3.
-  const bool q5 = a.step_disc.Q == 5 && a.step_disc.n_ties == 0;
   float h1k[5], h2k[5], h1l[5], h2l[5];  // run maxima of the last 5 tile rows (slot = row mod 5)
   auto reduce_row = [&](int row, int slot) {  // tile row jb + row (window rows start 2 above the outputs)
     const int base = (jb + row + MH) * MTW + (threadIdx.x + MH);
@@ -806,7 +822,9 @@ __global__ __launch_bounds__(MX* MBY) __attribute__((amdgpu_waves_per_eu(4, 4)))
       // (the screen knows nothing about failing submap lookups: next to such a border the full function decides)
       const bool near_bad_edge = a.edge_fail && (((a.edge_fail & 1) && ci <= 2) || ((a.edge_fail & 2) && ci >= g.rows - 3) ||
                                                   ((a.edge_fail & 4) && j <= 2) || ((a.edge_fail & 8) && j >= g.cols - 3));
-      ok = (screen_ok && !near_bad_edge) || check_step(g, a.step_disc, ve, vs, ci, j, a.crit_step, a.max_gap, a.edge_fail);
+      // (a flat tile: every cell is screened and none is next to such a border -- check_step, which would read the tiles
+      // that were not staged, is out of reach by the first operand)
+      ok = flat || (screen_ok && !near_bad_edge) || check_step(g, a.step_disc, ve, vs, ci, j, a.crit_step, a.max_gap, a.edge_fail);
       m_step = ok ? 1.0f : 0.0f;
     }
     if (ok && a.check_rough && c_rough == 0.0f) {  // checkForRoughness
@@ -1246,7 +1264,7 @@ bool footprint_slide_general(const Geo& g, const FootprintParams& p, const Layer
 
 // The mask pass of launch_footprint / launch_footprint_mask: k_fp_mask on the cells whose mask the scores of `region` can
 // change (nullptr: every cell of every map).  *rf_out: the cells whose footprint can change with them.
-void launch_mask_pass(const Geo& g, const FootprintParams& p, const Layers& L, bool write_memo, const ChainParams* combine,
+void launch_mask_pass(const Geo& g, const FootprintParams& p, const Layers& L, const uint8_t* face_flags, bool write_memo, const ChainParams* combine,
                       hipStream_t stream, const Region* region, Region* rf_out) {
   MaskArgs m;
   m.slope_disc = p.slope_disc;
@@ -1267,6 +1285,7 @@ void launch_mask_pass(const Geo& g, const FootprintParams& p, const Layers& L, b
   m.map = -1;
   m.blocked_count = L.fp_blocked_count;
   m.untrav_flags = L.untrav_flags;
+  m.face_flags = face_flags;
   m.flag_ntx = untrav_flag_ntx(g.rows);
   m.flag_nfy = untrav_flag_nfy(g.cols);
   static const int mask_whatif = lab_int("TE_MASK_WHATIF", 0);  // (timing experiments: wrong results by construction)
@@ -1327,17 +1346,18 @@ void launch_mask_pass(const Geo& g, const FootprintParams& p, const Layers& L, b
 
 }  // namespace
 
-hipError_t launch_footprint_mask(const Geo& g, const FootprintParams& p, const Layers& L, const ChainParams* combine, hipStream_t stream) {
+hipError_t launch_footprint_mask(const Geo& g, const FootprintParams& p, const Layers& L, const uint8_t* face_flags, const ChainParams* combine,
+                                 hipStream_t stream) {
   Region rf;
-  launch_mask_pass(g, p, L, false, combine, stream, nullptr, &rf);
+  launch_mask_pass(g, p, L, face_flags, false, combine, stream, nullptr, &rf);
   return hipGetLastError();
 }
 
-hipError_t launch_footprint(const Geo& g, const FootprintParams& p, const Layers& L, const unsigned* ptab,
+hipError_t launch_footprint(const Geo& g, const FootprintParams& p, const Layers& L, const uint8_t* face_flags, const unsigned* ptab,
                             const int* clip_table, bool write_memo, const ChainParams* combine, double trav_cap, hipStream_t stream,
                             const Region* region) {
   Region rf;
-  launch_mask_pass(g, p, L, write_memo, combine, stream, region, &rf);
+  launch_mask_pass(g, p, L, face_flags, write_memo, combine, stream, region, &rf);
   TraceRange tr_sum("footprint: disc sums (+ blocked discs)");
   const Region* rfp = region ? &rf : nullptr;
   const Disc& d = p.fp_disc;

@@ -8,6 +8,7 @@
 
 #include <vector>
 
+#include "te_face_flags.h"
 #include "te_fp_route.h"
 #include "travgpu.h"
 
@@ -316,8 +317,10 @@ hipError_t launch_chain(const Geo& g, const ChainParams& p, const Layers& L, con
 // trav_cap: upper bound of the finite traversability values if the layer was written by the chain, else < 0
 // region (nullptr: all maps, all cells): the cells whose scores changed; the mask is recomputed within 3 cells of them
 // and the footprint within the footprint's reach of those (a footprint shape only the general kernel serves: on every cell).
+// face_flags: the face flags of the elevation layer (te_face_flags.h: "a vertical face within 2 cells" per 64 x 4 cells, built at
+// upload) if they describe it now, else nullptr -- unknown, or TE_OPT_FACE_FLAGS = 0: every tile of k_fp_mask stages its step check
 // The sum kernels are chosen by plan_fp_route (te_fp_route.h); a planned route without its instantiation is an error.
-hipError_t launch_footprint(const Geo& g, const FootprintParams& p, const Layers& L, const unsigned* ptab,
+hipError_t launch_footprint(const Geo& g, const FootprintParams& p, const Layers& L, const uint8_t* face_flags, const unsigned* ptab,
                             const int* clip_table, bool write_memo, const ChainParams* combine, double trav_cap, hipStream_t stream,
                             const Region* region = nullptr);
 // te_footprint_any.hip: the sum of the circular footprint pass at any reach (the mask kernel has run); rf: the output
@@ -357,8 +360,10 @@ hipError_t launch_path_discs(const Geo& g, const PathDiscScratch& s, const PathD
                              double fp_default, const float* robot_slope, int n_paths, const int* pose_offset, const double* pose_xy,
                              const int* path_class, unsigned char* is_safe, double* traversability, int* status, hipStream_t stream);
 // te_footprint.hip: the isTraversableForFilters mask of every cell of every map (Layers::untrav, untrav_flags) and nothing
-// else: no memo layers, no footprint layer; combine: also the weighted sum a whole-map chain left to the mask kernel
-hipError_t launch_footprint_mask(const Geo& g, const FootprintParams& p, const Layers& L, const ChainParams* combine, hipStream_t stream);
+// else: no memo layers, no footprint layer; combine: also the weighted sum a whole-map chain left to the mask kernel;
+// face_flags: as for launch_footprint
+hipError_t launch_footprint_mask(const Geo& g, const FootprintParams& p, const Layers& L, const uint8_t* face_flags, const ChainParams* combine,
+                                 hipStream_t stream);
 
 // te_filter_any.hip: the filters for the discs marked Disc::any (the other disc of a normals stage may be either kind)
 namespace any {

@@ -174,7 +174,7 @@ int te_check_footprint_paths_radius(te_ctx* c, int map, int n_paths, const int* 
   if (e == hipSuccess) e = hipMemsetAsync(s.counters, 0, b_cnt, c->stream);
   // the untraversable mask: built on the first call after the scores (or one of the three parameters it reads) changed
   if (e == hipSuccess && !c->mask_done) {
-    e = launch_footprint_mask(g, c->fp, c->L, c->combine_deferred ? &c->cp : nullptr, c->stream);
+    e = launch_footprint_mask(g, c->fp, c->L, usable_face_flags(c), c->combine_deferred ? &c->cp : nullptr, c->stream);
     if (e == hipSuccess) {
       c->combine_deferred = false;
       c->mask_done = true;

@@ -154,24 +154,99 @@ bool same_disc(const Disc& a, const Disc& b) {
 }  // namespace te
 
 
-// Invalid (non-finite) cells of a layer: one pass at upload time.  out[0]: their number; out[1]: the number of RUNS of them
-// in memory order (an invalid cell whose predecessor is valid, or that is the layer's first).  The two pick the march
-// k_normals3 uses for strips with invalid cells and its strip height: scattered cells (runs of one) against unobserved
-// regions (runs as long as the regions are wide), te_normals3.hip.
-__global__ void k_count_invalid(const float* __restrict__ v, size_t n, unsigned long long* __restrict__ out) {
+// The upload's pass over the whole elevation layer: one kernel, one wait.
+// Invalid (non-finite) cells: out[0] their number; out[1] the number of RUNS of them in memory order (an invalid cell whose
+// predecessor is valid, or that is the layer's first).  The two pick the march k_normals3 uses for strips with invalid cells
+// and its strip height: scattered cells (runs of one) against unobserved regions (runs as long as the regions are wide),
+// te_normals3.hip.
+// Face flags (te_face_flags.h): one byte per 64 x 4 cells, 1 iff some cell within 2 cells of the granule lies more than
+// crit_step above the lowest cell of its 3x3 block.  A wavefront owns one flag column (64 cells along i) over 32 columns of
+// the map (8 granules) and marches down j through them and a halo of 3 (2 cells of dilation + 1 of the 3x3 block; NaN
+// outside the map), straight from global memory: a lane loads its cell and the two beside it, the minimum of the three
+// slides over three steps in registers, and the lanes do the same for the two cells either side of the 64.  A step's
+// verdict is one bit of a wave-uniform word; a granule's flag ORs its own 4 steps and 2 either side: the dilation is done
+// here, the mask kernel reads only its own bytes.  The counts come from the same loads.
+namespace {
+constexpr int kCfX = 64, kCfY = 32, kCfH = te::kFaceDilate + 1, kCfT = kCfY + 2 * kCfH, kCfWaves = 4, kCfG = 10;
+static_assert(kCfX == te::kFaceGranI && kCfY % te::kFaceGranJ == 0 && kCfT <= 64 && kCfY / te::kFaceGranJ <= 64, "k_count_invalid: tile shape");
+}  // namespace
+__global__ __launch_bounds__(64 * kCfWaves) void k_count_invalid(const float* __restrict__ v, int rows, int cols, double crit_step,
+                                                                 uint8_t* __restrict__ flags, unsigned long long* __restrict__ out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ti = (int)blockIdx.x * kCfWaves + wave;
+  if (ti >= te::face_flag_ntx(rows)) return;  // (whole wavefronts; the kernel has no barrier)
+  const int map = blockIdx.z, i0 = ti * kCfX, j0 = (int)blockIdx.y * kCfY;
+  const size_t mo = (size_t)map * (size_t)rows * (size_t)cols;
+  const float nan = __builtin_nanf("");
+  // Every load is unconditional: a column's base is wave-uniform, a lane's offsets are fixed before the loop, and a neighbour
+  // outside the map reads the cell itself, which leaves the minimum as it is.  No branch and no address arithmetic stands
+  // between the loads of a group of steps.
+  const int i = i0 + lane, ic = i < rows ? i : rows - 1;
+  const bool own = i < rows, has_up = i > 0;
+  const int o_prev = ic - 1, o_prev0 = ic > 0 ? ic - 1 : 0, o_next = ic + 1 < rows ? ic + 1 : ic;
+  // the two cells either side of the 64: lanes 4 q + 0, 1 take i0 - 2, i0 - 1, lanes 4 q + 2, 3 take i0 + 64, i0 + 65 (every q the same)
+  const int xl = lane & 3;
+  const int ix = xl < te::kFaceDilate ? i0 - te::kFaceDilate + xl : i0 + kCfX + xl - te::kFaceDilate;
+  const bool xin = ix >= 0 && ix < rows;
+  const int ixc = ix < 0 ? 0 : (ix < rows ? ix : rows - 1);
+  const int ox_prev = ixc > 0 ? ixc - 1 : 0, ox_next = ixc + 1 < rows ? ixc + 1 : ixc;
+  auto mn = [](float a, float b) { return __builtin_fminf(a, b); };  // (ignores NaN like te::face_min; the sign of a zero does not reach the test)
   unsigned cnt = 0, runs = 0;
-  for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (size_t)gridDim.x * blockDim.x) {
-    const bool bad = !__builtin_isfinite(v[k]);
-    cnt += bad ? 1u : 0u;
-    runs += (bad && (k == 0 || __builtin_isfinite(v[k - 1]))) ? 1u : 0u;
+  unsigned long long step_any = 0ull;  // bit r: some cell of step r (map column j0 - kCfH + r) has the face test true
+  float a0 = nan, a1 = nan, e1 = nan, x0 = nan, x1 = nan, ex1 = nan;  // minima of the two steps before, and the cells of the one before
+  // kCfG steps at a time: all their loads first, into registers, then the arithmetic (a step's loads wait for nothing)
+#pragma unroll
+  for (int rb = 0; rb < kCfT; rb += kCfG) {
+    float prev[kCfG], mid[kCfG], next[kCfG], xprev[kCfG], xmid[kCfG], xnext[kCfG];
+#pragma unroll
+    for (int q = 0; q < kCfG; ++q) {
+      if (rb + q >= kCfT) continue;
+      const int j = j0 - kCfH + rb + q;
+      const size_t col = mo + (size_t)(j < 0 ? 0 : (j < cols ? j : cols - 1)) * rows;
+      const float* __restrict__ cp = v + col;
+      // the predecessor in memory: the cell above, or the last cell of the previous column / map (none before the layer's first)
+      prev[q] = cp[col == 0 ? o_prev0 : o_prev], mid[q] = cp[ic], next[q] = cp[o_next];
+      xprev[q] = cp[ox_prev], xmid[q] = cp[ixc], xnext[q] = cp[ox_next];
+    }
+#pragma unroll
+    for (int q = 0; q < kCfG; ++q) {
+      const int r = rb + q;
+      if (r >= kCfT) continue;
+      const int j = j0 - kCfH + r;
+      const bool jin = j >= 0 && j < cols;  // (uniform)
+      const bool in = jin && own, inx = jin && xin;
+      const float e2 = in ? mid[q] : nan, ex2 = inx ? xmid[q] : nan;
+      const float a2 = in ? mn(mn(has_up ? prev[q] : mid[q], mid[q]), next[q]) : nan;
+      const float x2 = inx ? mn(mn(xprev[q], xmid[q]), xnext[q]) : nan;
+      if (r >= kCfH && r < kCfH + kCfY) {  // the two counts: every cell of the layer belongs to exactly one wavefront
+        const bool bad = in && !__builtin_isfinite(mid[q]);
+        const bool first = map == 0 && j == 0 && i == 0;
+        cnt += bad ? 1u : 0u;
+        runs += (bad && (first || __builtin_isfinite(prev[q]))) ? 1u : 0u;
+      }
+      if (r >= 2) {  // step r - 1 has its three minima (a cell outside the map is NaN and never hits)
+        const bool hit = te::face_hit(mn(mn(a0, a1), a2), e1, crit_step) || te::face_hit(mn(mn(x0, x1), x2), ex1, crit_step);
+        if (__ballot(hit) != 0ull) step_any |= 1ull << (r - 1);
+      }
+      a0 = a1, a1 = a2, e1 = e2;
+      x0 = x1, x1 = x2, ex1 = ex2;
+    }
   }
   for (int d = 32; d >= 1; d >>= 1) {
     cnt += __shfl_xor((int)cnt, d);
     runs += __shfl_xor((int)runs, d);
   }
-  if ((threadIdx.x & 63) == 0 && cnt) {
+  if (lane == 0 && cnt) {
     atomicAdd(out, (unsigned long long)cnt);
     if (runs) atomicAdd(out + 1, (unsigned long long)runs);
+  }
+  if (flags != nullptr && lane < kCfY / te::kFaceGranJ) {  // granule `lane`: its own steps kCfH + 4 lane .. + 3, and kFaceDilate either side
+    const int fj = j0 / te::kFaceGranJ + lane;
+    if (fj < te::face_flag_nfy(cols)) {
+      const unsigned long long span = (1ull << (te::kFaceGranJ + 2 * te::kFaceDilate)) - 1ull;
+      const bool any = ((step_any >> (kCfH - te::kFaceDilate + te::kFaceGranJ * lane)) & span) != 0ull;
+      flags[((size_t)map * (size_t)te::face_flag_nfy(cols) + (size_t)fj) * (size_t)te::face_flag_ntx(rows) + (size_t)ti] = any ? 1 : 0;
+    }
   }
 }
 
@@ -196,6 +271,7 @@ void finish_prefetch_locked(te_ctx* c) {
     c->mask_done = false;
     c->invalid_cells = -1;
     c->invalid_runs = -1;
+    c->face_crit = __builtin_nan("");  // (a failed or partial prefetch leaves the face flags unknown as well)
     if (ok) {
       c->have_elev = true;
       // the invalid cells are counted like te_upload_elevation counts them (the count picks the normals kernel's march and
@@ -203,6 +279,7 @@ void finish_prefetch_locked(te_ctx* c) {
       if (hipSetDevice(c->device) != hipSuccess || count_invalid_elevation(c) != TE_OK) {
         (void)hipGetLastError();
         c->invalid_cells = -1;
+        c->face_crit = __builtin_nan("");
       }
     } else {
       c->have_elev = false;  // partly overwritten: the next chain needs a complete upload
@@ -232,21 +309,34 @@ unsigned filter_layers(int filter) {
 namespace te {
 namespace shim {
 
-// counts the invalid cells of the whole elevation layer on the context's stream and waits for the result
+// counts the invalid cells of the whole elevation layer on the context's stream, builds the layer's face flags for the
+// fp_critical_step held (te_face_flags.h) and waits for the result
 int count_invalid_elevation(te_ctx* c) {
   c->invalid_cells = -1;
+  c->face_crit = __builtin_nan("");
   if (!c->d_count) HIP_TRY(hipMalloc((void**)&c->d_count, 2 * sizeof(unsigned long long)));
   HIP_TRY(hipMemsetAsync(c->d_count, 0, 2 * sizeof(unsigned long long), c->stream));
-  const size_t n = c->layer_elems;
-  int blocks = (int)((n + 256 * 16 - 1) / (256 * 16));
-  blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
-  hipLaunchKernelGGL(k_count_invalid, dim3((unsigned)blocks), dim3(256), 0, c->stream, c->L.elev, n, c->d_count);
+  const bool with_flags = c->face_flags != nullptr;
+  const double crit = c->params.fp_critical_step;
+  const dim3 grid((unsigned)((face_flag_ntx(c->geo.rows) + kCfWaves - 1) / kCfWaves), (unsigned)((c->geo.cols + kCfY - 1) / kCfY), (unsigned)c->geo.batch);
+  if (grid.y > 65535u || grid.z > 65535u) return fail(TE_ERR_UNSUPPORTED, "elevation layer of %d columns x %d maps: too many for one pass", c->geo.cols, c->geo.batch);
+  hipLaunchKernelGGL(k_count_invalid, grid, dim3(64 * kCfWaves), 0, c->stream, c->L.elev, c->geo.rows, c->geo.cols, crit, c->face_flags, c->d_count);
+  HIP_TRY(hipGetLastError());
   unsigned long long h[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(h, c->d_count, sizeof(h), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->invalid_cells = (long long)h[0];
   c->invalid_runs = (long long)h[1];
+  if (with_flags) c->face_crit = crit;
   return TE_OK;
+}
+
+// the face flags a mask launch may read: built for the elevation that is resident and for the critical step of the footprint
+// parameters in force (NaN -- unknown -- compares false)
+const uint8_t* usable_face_flags(const te_ctx* c) {
+  return (c->opt_face_flags && c->face_flags && !c->elev_ptr_out && c->face_crit == c->fp.crit_step && c->face_crit == c->params.fp_critical_step)
+             ? c->face_flags
+             : nullptr;
 }
 
 // few invalid cells, scattered: at most 2 per mille (0.1 % speckle: the sparse march is 1.4x faster than the dense one,
@@ -551,6 +641,9 @@ void free_layers(te_ctx* c) {
   drop_graph(c);
   if (c->slab) (void)hipFree(c->slab);
   c->slab = nullptr;
+  c->face_flags = nullptr;  // (part of the slab)
+  c->face_crit = __builtin_nan("");
+  c->elev_ptr_out = false;
   guard_cache_generation().fetch_add(1, std::memory_order_acq_rel);  // (layer_has_guard_rows: verdicts about freed memory)
   if (c->poly_x) (void)hipFree(c->poly_x);
   c->poly_x = c->poly_rot = nullptr;
@@ -666,7 +759,7 @@ int run_footprint_locked(te_ctx* c, unsigned flags, bool fresh = false) {
   const ChainParams& q = c->cp;
   const bool bounded = !c->trav_external && (fresh || !c->trav_ptr_out) && q.w_scale >= 0.0f && q.w_slope >= 0.0f && q.w_step >= 0.0f && q.w_rough >= 0.0f;
   const double trav_cap = bounded ? (double)q.w_scale * ((double)q.w_slope + (double)q.w_step + (double)q.w_rough) : -1.0;
-  HIP_TRY(launch_footprint(c->geo, c->fp, c->L, c->d_spiral, c->fp_clip_table, (flags & TE_RUN_FOOTPRINT_MEMO) != 0,
+  HIP_TRY(launch_footprint(c->geo, c->fp, c->L, usable_face_flags(c), c->d_spiral, c->fp_clip_table, (flags & TE_RUN_FOOTPRINT_MEMO) != 0,
                            c->combine_deferred ? &c->cp : nullptr, trav_cap, c->stream));
   c->combine_deferred = false;
   c->footprint_done = true;
@@ -695,9 +788,10 @@ int run_whole_locked(te_ctx* c, unsigned flags) {
     if (int rc = refuse_rank_rule(c)) return rc;  // (before a capture: a failed one would end graph replay for good)
     HIP_TRY(hipSetDevice(c->device));
     int slot = -1;
-    // (the captured launches bake in which k_normals3 variant runs: the hint is part of the key)
+    // (the captured launches bake in which k_normals3 variant runs, and whether the mask kernel is given the face flags: the
+    // hints are part of the key)
     ensure_tie_scratch(c);
-    const unsigned key = flags | (sparse_holes(c) && ensure_hole_queue(c) ? 0x80000000u : 0u) | (c->invalid_cells == 0 ? 0x40000000u : 0u) | (skip_clean_march(c) ? 0x20000000u : 0u) | (short_strips(c) ? 0x10000000u : 0u);
+    const unsigned key = flags | (((flags & TE_RUN_FOOTPRINT) && usable_face_flags(c)) ? 0x08000000u : 0u) | (sparse_holes(c) && ensure_hole_queue(c) ? 0x80000000u : 0u) | (c->invalid_cells == 0 ? 0x40000000u : 0u) | (skip_clean_march(c) ? 0x20000000u : 0u) | (short_strips(c) ? 0x10000000u : 0u);
     for (int k = 0; k < te_ctx::kGraphs; ++k)
       if (c->graph_exec[k] && c->graph_flags[k] == key) slot = k;
     if (slot < 0) {
@@ -932,6 +1026,8 @@ int te_set_params(te_ctx* c, const te_params* p) {
   c->mask_done = c->mask_done && c->chain_done && old.fp_max_gap == p->fp_max_gap &&
                       old.fp_critical_step == p->fp_critical_step && old.fp_check_roughness == p->fp_check_roughness;
   c->footprint_done = false;
+  // the face flags were built for the critical step held at upload (te_face_flags.h): unknown until the next whole upload
+  if (!(old.fp_critical_step == p->fp_critical_step)) c->face_crit = __builtin_nan("");
   return TE_OK;
 }
 
@@ -984,6 +1080,10 @@ int te_set_option(te_ctx* c, int option, int value) {
         c->mask_done = false;
       }
       break;
+    case TE_OPT_FACE_FLAGS:
+      if (value < 0 || value > 1) return fail(TE_ERR_INVALID_ARG, "te_set_option: TE_OPT_FACE_FLAGS takes 0 (never passed to the mask kernel) or 1 (passed when known)");
+      c->opt_face_flags = value;  // (identical layers either way: nothing computed so far is invalidated)
+      break;
     case TE_OPT_NORMALS_RANK_RULE:
       c->opt_rank_rule = value != 0;
       c->chain_done = false;
@@ -994,6 +1094,19 @@ int te_set_option(te_ctx* c, int option, int value) {
       return fail(TE_ERR_INVALID_ARG, "te_set_option: unknown option %d", option);
   }
   drop_graph(c);  // (captured launches bake the choice in)
+  return TE_OK;
+}
+
+int te_download_face_flags(te_ctx* c, unsigned char* out, size_t bytes) {
+  if (!c || !out) return fail(TE_ERR_INVALID_ARG, "te_download_face_flags: NULL");
+  CtxLock lk(c);
+  const uint8_t* f = c->have_geo && c->have_elev ? usable_face_flags(c) : nullptr;
+  if (!f) return fail(TE_ERR_NOT_READY, "te_download_face_flags: the face flags of the elevation layer are unknown or switched off");
+  const size_t n = face_flag_bytes(c->geo.rows, c->geo.cols, c->geo.batch);
+  if (bytes != n) return fail(TE_ERR_INVALID_ARG, "te_download_face_flags: %zu bytes given, the flags are %zu", bytes, n);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(out, f, n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return TE_OK;
 }
 
@@ -1036,7 +1149,9 @@ int te_set_geometry(te_ctx* c, int rows, int cols, int batch, double res, double
     const size_t ufb = (untrav_flag_bytes(rows, cols, batch) + 255) & ~(size_t)255;
     // (+ the sum kernel's scratch: a second array of the list's size, see Layers::fp_scratch)
     const size_t pcb = qb;
-    const size_t total = guard + 13 * lb + ub + fb + qb + 256 + ufb + pcb + guard;
+    // (+ the face flags of the elevation layer, the same grid: te_face_flags.h, written by the upload's pass)
+    const size_t ffb = (face_flag_bytes(rows, cols, batch) + 255) & ~(size_t)255;
+    const size_t total = guard + 13 * lb + ub + fb + qb + 256 + ufb + pcb + ffb + guard;
     hipError_t e = hipMalloc(&slab, total);
     if (e != hipSuccess) return fail(TE_ERR_HIP, "te_set_geometry: hipMalloc(%zu bytes): %s", total, hipGetErrorString(e));
     c->slab = slab;
@@ -1051,10 +1166,13 @@ int te_set_geometry(te_ctx* c, int rows, int cols, int batch, double res, double
     c->L.fp_blocked_cap = list_cap;
     c->L.untrav_flags = (uint8_t*)(b + 13 * lb + ub + fb + qb + 256);
     c->L.fp_scratch = list_cap < ((size_t)1 << 32) ? (unsigned*)(b + 13 * lb + ub + fb + qb + 256 + ufb) : nullptr;
+    c->face_flags = (uint8_t*)(b + 13 * lb + ub + fb + qb + 256 + ufb + pcb);
+    c->face_crit = __builtin_nan("");
     c->layer_elems = elems;
     // outputs read as NaN until computed, like GridMap::add()
     HIP_TRY(hipMemsetAsync(slab, 0xFF, guard + 13 * lb + ub + fb, c->stream));
-    HIP_TRY(hipMemsetAsync(b + 13 * lb + ub + fb + qb + 256 + ufb + pcb, 0xFF, guard, c->stream));
+    HIP_TRY(hipMemsetAsync(b + 13 * lb + ub + fb + qb + 256 + ufb + pcb + ffb, 0xFF, guard, c->stream));
+    HIP_TRY(hipMemsetAsync(c->face_flags, 0x01, ffb, c->stream));
     HIP_TRY(hipMemsetAsync(c->L.untrav_flags, 0x01, ufb, c->stream));
     // the mask layer holds 0 / 1 only (k_fp_slide5 packs the byte as it is): "untraversable" until the mask kernel has
     // looked at the cell, as a byte of 0xFF would also say -- but 1 stays inside the packed word's flag bit
@@ -1159,7 +1277,7 @@ int te_run_chain_region(te_ctx* c, unsigned flags, int map, int row0, int col0, 
   const ChainParams& q = c->cp;
   const bool bounded = !c->trav_external && !c->trav_ptr_out && q.w_scale >= 0.0f && q.w_slope >= 0.0f && q.w_step >= 0.0f && q.w_rough >= 0.0f;
   const double trav_cap = bounded ? (double)q.w_scale * ((double)q.w_slope + (double)q.w_step + (double)q.w_rough) : -1.0;
-  HIP_TRY(launch_footprint(c->geo, c->fp, c->L, c->d_spiral, c->fp_clip_table, (flags & TE_RUN_FOOTPRINT_MEMO) != 0, nullptr, trav_cap,
+  HIP_TRY(launch_footprint(c->geo, c->fp, c->L, usable_face_flags(c), c->d_spiral, c->fp_clip_table, (flags & TE_RUN_FOOTPRINT_MEMO) != 0, nullptr, trav_cap,
                            c->stream, &changed));
   c->footprint_done = true;  // complete before, refreshed where it could change
   c->mask_done = mask_was_done;  // (likewise the mask -- unless a score layer was uploaded since it was built)

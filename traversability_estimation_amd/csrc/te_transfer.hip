@@ -44,6 +44,7 @@ int te_upload_tile(te_ctx* c, const float* host_tile, int map, int row0, int col
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->have_elev = true;
   c->invalid_cells = -1;  // tiles are not counted: the count of the last whole upload says nothing about them (dense march)
+  c->face_crit = __builtin_nan("");  // ... and neither do its face flags (te_face_flags.h): unknown until the next whole upload
   return TE_OK;
 }
 
@@ -119,6 +120,7 @@ int te_upload_tile_async(te_ctx* c, const float* host_tile, int map, int row0, i
   c->tiles_pending = true;
   c->have_elev = true;
   c->invalid_cells = -1;  // (as te_upload_tile)
+  c->face_crit = __builtin_nan("");
   return TE_OK;
 }
 
@@ -163,6 +165,8 @@ int te_device_ptr(te_ctx* c, int layer, void** dptr, size_t* bytes) {
   if (layer == TE_LAYER_SLOPE || layer == TE_LAYER_STEP || layer == TE_LAYER_ROUGHNESS) c->mask_done = false;  // (the mask reads them)
   if (layer == TE_LAYER_ELEVATION) {  // caller fills the elevation in place (zero-copy producer)
     c->invalid_cells = -1;
+    c->face_crit = __builtin_nan("");  // (the face flags describe the last whole upload ...
+    c->elev_ptr_out = true;            // ... and a write through the pointer behind a later one would go unseen: te_ctx.h)
     c->have_elev = true;
     c->chain_done = false;
     c->footprint_done = false;
