@@ -46,6 +46,10 @@
  *                           (GridMapRosConverter::initializeFromImage, then addLayerFromImage(image, "elevation", map,
  *                           min_height, max_height)): the image's own 1 .. 8 bytes per cell cross PCIe, the conversion
  *                           to float32 and the transposition into the column-major layer run on the device
+ *   te_download_occupancy / te_download_occupancy_msg / te_download_cloud / te_download_cloud_msg
+ *                        <- the grid_map_visualization entries of traversability_estimation/config/visualization/
+ *                           traversability.yaml (type occupancy_grid for the four score layers, type point_cloud for the
+ *                           elevation): GridMapRosConverter::toOccupancyGrid / toPointCloud, converted on the device
  *
  * Data contract (identical to grid_map::Matrix = Eigen::MatrixXf): float32, COLUMN-major,
  * element (row i, col j) of map m at ptr[m*rows*cols + j*rows + i]; invalid cell = non-finite.
@@ -509,6 +513,107 @@ int te_upload_image(te_ctx* ctx, const te_image_info* info, const void* pixels, 
  * cols = width, resolution, position), then te_upload_image into map 0.  `info` (may be NULL) receives the description. */
 int te_upload_image_msg(te_ctx* ctx, const void* msg, size_t len, int layer, float lower, float upper, double alpha_threshold,
                         double resolution, double pos_x, double pos_y, te_image_info* info);
+
+/* ---- nav_msgs/OccupancyGrid as an output: what traversability_estimation/config/visualization/traversability.yaml asks
+ * for (traversability, traversability_slope, traversability_step, traversability_roughness, each with data_min 1.0 and
+ * data_max 0.0) and what a costmap-based planner consumes.  One byte per cell crosses PCIe instead of four.
+ *
+ * Semantics = GridMapRosConverter::toOccupancyGrid(gridMap, layer, dataMin, dataMax, grid) (restated here: grid_map_ros is
+ * not vendored, so like the image route's colour branch this is a stated contract with no reference-held vector, DESIGN.md
+ * section 7).  For every cell, in float32, in this order, without contraction, with a correctly rounded division:
+ *       v    = (layer(i, j) - data_min) / (data_max - data_min)
+ *       cell = isnan(v) ? -1 : (int8)(0.0f + min(max(0.0f, v), 1.0f) * 100.0f)          (the conversion truncates)
+ *       data[n - 1 - (j * rows + i)] = cell                                              n = rows * cols
+ *   - +-inf clamp to 0 or 100.  data_min == data_max gives inf or NaN by the formula (0, 100 or -1); it is not rejected.
+ *   - The output is the layer's storage order reversed: grid_map's "reverse cell order" of
+ *     getLinearIndexFromIndex(.., rowMajor = false).  Device layers have start index (0, 0): nothing to unwrap.
+ *   - info.resolution = (float)resolution, info.width = rows, info.height = cols,
+ *     info.origin.position = (pos_x - len_x / 2, pos_y - len_y / 2, 0), info.origin.orientation = (0, 0, 0, 1),
+ *     info.map_load_time = the header stamp.
+ * Wire layout (ROS1, little endian): Header{u32 seq; u32 sec; u32 nsec; string frame_id}
+ *   MapMetaData{u32 sec; u32 nsec; f32 resolution; u32 width; u32 height; f64[7] origin}  int8[] data (u32 length, bytes).
+ *
+ * The calls read the layers and change nothing in the context: chain results, present flags and parameters stay. */
+typedef struct te_occupancy_info {
+  uint32_t seq, stamp_sec, stamp_nsec;   /* header */
+  char frame_id[TE_MSG_MAX_NAME];        /* NUL-terminated */
+  uint32_t map_load_sec, map_load_nsec;  /* info.map_load_time */
+  float resolution;
+  uint32_t width, height;                /* rows, cols of the layer */
+  double origin[7];                      /* position x y z, orientation x y z w */
+} te_occupancy_info;
+
+/* n_layers (1 .. 16) layers of map `map` -> out[k * rows * cols ..), layer k with its own data_min[k] / data_max[k]: ONE
+ * launch and ONE device -> host transfer of n_layers * rows * cols bytes, whatever n_layers is.  `out` may be pageable or
+ * page-locked (te_pin_host).  Synchronous.  TE_ERR_NOT_READY: no geometry, or a layer that does not exist (yet);
+ * TE_ERR_INVALID_ARG: NULL, a layer id or map index out of range, n_layers out of range, non-finite data_min / data_max. */
+#define TE_OCCUPANCY_MAX_LAYERS 16
+int te_download_occupancy(te_ctx* ctx, int map, int n_layers, const int* layers, const float* data_min, const float* data_max,
+                          int8_t* out);
+/* toOccupancyGrid of layer `layer` of map 0 as a serialised message; the cells land directly at their offset in `out`.
+ * seq, stamp and frame_id come from `info`, everything else from the context.  *written = bytes needed even when
+ * TE_ERR_INVALID_ARG reports that `cap` is too small (out = NULL, cap = 0 sizes the buffer without touching the device). */
+int te_download_occupancy_msg(te_ctx* ctx, const te_msg_info* info, int layer, float data_min, float data_max, void* out,
+                              size_t cap, size_t* written);
+/* Host only, no context: the message of `info` with the width * height cells `data`.  Sizing call as above. */
+int te_occupancy_msg_write(const te_occupancy_info* info, const int8_t* data, void* out, size_t cap, size_t* written);
+/* Validate and describe a serialised nav_msgs/OccupancyGrid; *data_offset = byte offset of its width * height cells.
+ * Rejected (TE_ERR_INVALID_ARG + message): truncation, a frame_id longer than TE_MSG_MAX_NAME - 1, width * height other
+ * than the data length, a product that overflows. */
+int te_occupancy_parse(const void* msg, size_t len, te_occupancy_info* info, size_t* data_offset);
+
+/* ---- sensor_msgs/PointCloud2 as an output: the visualization config's point cloud of the elevation layer.  Only the valid
+ * cells cross PCIe.
+ *
+ * Semantics = GridMapRosConverter::toPointCloud(gridMap, layers, pointLayer, cloud) (restated, as above):
+ *   - The point layer must appear in `layers` exactly once.  A point's record is the layers in order, one float32 field
+ *     each, named after the layer; the point layer is replaced by the three fields x, y, z.  n_fields = n_layers + 2,
+ *     point_step = 4 * n_fields, offsets 0, 4, 8, ..., datatype 7 (FLOAT32), count 1.
+ *   - x, y = (float) of the cell centre's double position (x(i) = pos_x + (len_x / 2 - res / 2) + res * (double)(-i), y(j)
+ *     likewise), z = the point layer's value, every other field = that layer's value (NaN included).
+ *   - A cell is emitted iff its point-layer value is finite and, with a basic-layer list, every basic layer is finite there
+ *     (GridMap::isValid(index, basicLayers)).
+ *   - Points come in GridMapIterator order; with start index (0, 0) that is storage order j * rows + i.
+ *   - height = 1, width = n_points, row_step = width * point_step, is_bigendian = 0, is_dense = 0.
+ *   - Not covered: the colour special case (a layer named "color" becoming the field "rgb"); the context owns no such layer.
+ * Wire layout: Header, u32 height, u32 width, PointField[]{string name; u32 offset; u8 datatype; u32 count}, u8 is_bigendian,
+ *   u32 point_step, u32 row_step, u8[] data, u8 is_dense.
+ *
+ * The compaction keeps the order with three launches on the context's stream -- per-workgroup counts, an exclusive scan of
+ * the counts, a scatter -- and no workgroup ever waits for another inside a kernel.  The count comes back with one small
+ * synchronous copy before the payload.  Scratch memory follows the map size; it is allocated on first use and kept. */
+#define TE_CLOUD_MAX_LAYERS 16
+typedef struct te_cloud_info {
+  uint32_t seq, stamp_sec, stamp_nsec; /* header */
+  char frame_id[TE_MSG_MAX_NAME];      /* NUL-terminated */
+  uint32_t height, width;
+  uint32_t n_fields, point_step, row_step;
+  int32_t is_bigendian, is_dense;
+} te_cloud_info;
+
+/* layers[n_layers] (1 .. TE_CLOUD_MAX_LAYERS te_layer ids, point_layer among them exactly once) of map `map`; basic_layers
+ * [n_basic] (may be 0 / NULL).  out receives n_points records of n_layers + 2 floats.  *n_points is always set when the
+ * count succeeded; more points than cap_points: TE_ERR_INVALID_ARG and nothing is written (cap_points = 0, out = NULL sizes).
+ * Error codes as te_download_occupancy.  Synchronous; the context is left as it was. */
+int te_download_cloud(te_ctx* ctx, int map, int n_layers, const int* layers, int point_layer, int n_basic, const int* basic_layers,
+                      float* out, size_t cap_points, size_t* n_points);
+/* toPointCloud of map 0 as a serialised message: field names[k] for layer k (the point layer's name is not used: x, y, z),
+ * seq / stamp / frame_id from `info`.  Sizing call as te_download_msg (it runs the count). */
+int te_download_cloud_msg(te_ctx* ctx, const te_msg_info* info, int n_layers, const int* layers, const char* const* names,
+                          int point_layer, int n_basic, const int* basic_layers, void* out, size_t cap, size_t* written);
+/* Host only: a cloud of info->width points (height 1) with n_fields float32 fields named field_names[k], offsets 4k; reads
+ * seq, stamp, frame_id, width, is_dense of `info`.  points = width * n_fields floats. */
+int te_cloud_msg_write(const te_cloud_info* info, int n_fields, const char* const* field_names, const float* points, void* out,
+                       size_t cap, size_t* written);
+/* Validate and describe a serialised sensor_msgs/PointCloud2; *data_offset = byte offset of its row_step * height bytes.
+ * Rejected: truncation, a name longer than TE_MSG_MAX_NAME - 1, a field datatype outside 1 .. 8 or a field that ends behind
+ * point_step, width * point_step above row_step, row_step * height other than the data length, a product that overflows. */
+int te_cloud_parse(const void* msg, size_t len, te_cloud_info* info, size_t* data_offset);
+/* Field k of a valid message: name (NUL-terminated into name[TE_MSG_MAX_NAME]), offset, datatype, count. */
+int te_cloud_field(const void* msg, size_t len, int k, char* name, uint32_t* offset, uint32_t* datatype, uint32_t* count);
+/* The spans of the compaction (tests place holes across them): cells[0] = cells of one wavefront's ballot, cells[1] = cells
+ * one workgroup counts, cells[2] = cells one scan workgroup's span covers. */
+int te_cloud_spans(size_t cells[3]);
 
 const char* te_last_error(void);
 const char* te_version(void);

@@ -45,8 +45,12 @@ SYMBOLS = ["te_params_default", "te_params_validate", "te_device_count", "te_cre
            "te_check_polygon_footprint_paths", "te_pin_host", "te_unpin_host", "te_path_polygons",
            "te_shard_range", "te_bcast_params", "te_run_chain_multi", "te_sync_multi",
            "te_set_check_robot_inclination", "te_check_inclination", "te_polygon_untraversable_hull",
-           "te_image_parse", "te_upload_image", "te_upload_image_msg"]
+           "te_image_parse", "te_upload_image", "te_upload_image_msg",
+           "te_download_occupancy", "te_download_occupancy_msg", "te_occupancy_msg_write", "te_occupancy_parse",
+           "te_download_cloud", "te_download_cloud_msg", "te_cloud_msg_write", "te_cloud_parse", "te_cloud_field", "te_cloud_spans"]
 MSG_MAX_NAME = 64
+OCCUPANCY_MAX_LAYERS = CLOUD_MAX_LAYERS = 16
+POINTFIELD_FLOAT32 = 7
 
 
 def shard_range(batch, n_shards, k):
@@ -100,6 +104,24 @@ class TeImageInfo(C.Structure):
                 ("height", C.c_int32), ("width", C.c_int32), ("step", C.c_int32),
                 ("channels", C.c_int32), ("bytes_per_channel", C.c_int32), ("is_bigendian", C.c_int32),
                 ("encoding", C.c_char * MSG_MAX_NAME)]
+
+
+class TeOccupancyInfo(C.Structure):
+    """te_occupancy_info: a nav_msgs/OccupancyGrid without its cells."""
+    _fields_ = [("seq", C.c_uint32), ("stamp_sec", C.c_uint32), ("stamp_nsec", C.c_uint32),
+                ("frame_id", C.c_char * MSG_MAX_NAME),
+                ("map_load_sec", C.c_uint32), ("map_load_nsec", C.c_uint32),
+                ("resolution", C.c_float), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("origin", C.c_double * 7)]
+
+
+class TeCloudInfo(C.Structure):
+    """te_cloud_info: a sensor_msgs/PointCloud2 without its fields and points."""
+    _fields_ = [("seq", C.c_uint32), ("stamp_sec", C.c_uint32), ("stamp_nsec", C.c_uint32),
+                ("frame_id", C.c_char * MSG_MAX_NAME),
+                ("height", C.c_uint32), ("width", C.c_uint32),
+                ("n_fields", C.c_uint32), ("point_step", C.c_uint32), ("row_step", C.c_uint32),
+                ("is_bigendian", C.c_int32), ("is_dense", C.c_int32)]
 
 
 # encoding name -> (channels, bytes per channel): the encodings te_image_parse accepts
@@ -214,6 +236,17 @@ def load():
         L.te_upload_image.argtypes = [vp, C.POINTER(TeImageInfo), vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_double]
         L.te_upload_image_msg.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double,
                                           C.c_double, C.c_double, C.POINTER(TeImageInfo)]
+        ip, i8p, u32p = C.POINTER(C.c_int), C.POINTER(C.c_int8), C.POINTER(C.c_uint32)
+        L.te_download_occupancy.argtypes = [vp, C.c_int, C.c_int, ip, fp, fp, vp]
+        L.te_download_occupancy_msg.argtypes = [vp, C.POINTER(TeMsgInfo), C.c_int, C.c_float, C.c_float, vp, C.c_size_t, szp]
+        L.te_occupancy_msg_write.argtypes = [C.POINTER(TeOccupancyInfo), i8p, vp, C.c_size_t, szp]
+        L.te_occupancy_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(TeOccupancyInfo), szp]
+        L.te_download_cloud.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, ip, vp, C.c_size_t, szp]
+        L.te_download_cloud_msg.argtypes = [vp, C.POINTER(TeMsgInfo), C.c_int, ip, cpp, C.c_int, C.c_int, ip, vp, C.c_size_t, szp]
+        L.te_cloud_msg_write.argtypes = [C.POINTER(TeCloudInfo), C.c_int, cpp, fp, vp, C.c_size_t, szp]
+        L.te_cloud_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(TeCloudInfo), szp]
+        L.te_cloud_field.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_char_p, u32p, u32p, u32p]
+        L.te_cloud_spans.argtypes = [szp]
         L.te_last_error.restype = C.c_char_p
         L.te_version.restype = C.c_char_p
         _lib = L
@@ -315,6 +348,64 @@ def image_parse(msg):
     info, off = TeImageInfo(), C.c_size_t()
     _check(load().te_image_parse(msg, len(msg), C.byref(info), C.byref(off)))
     return info, off.value
+
+
+def occupancy_parse(msg):
+    """Validate a serialised nav_msgs/OccupancyGrid; returns (TeOccupancyInfo, byte offset of its width * height cells)."""
+    info, off = TeOccupancyInfo(), C.c_size_t()
+    _check(load().te_occupancy_parse(msg, len(msg), C.byref(info), C.byref(off)))
+    return info, off.value
+
+
+def occupancy_msg_write(info, data):
+    """The message of a TeOccupancyInfo and its width * height int8 cells (host only)."""
+    d = np.ascontiguousarray(data, dtype=np.int8).reshape(-1)
+    need = C.c_size_t()
+    L = load()
+    L.te_occupancy_msg_write(C.byref(info), None, None, 0, C.byref(need))
+    out = C.create_string_buffer(max(need.value, 1))
+    _check(L.te_occupancy_msg_write(C.byref(info), d.ctypes.data_as(C.POINTER(C.c_int8)), out, need.value, C.byref(need)))
+    return out.raw[:need.value]
+
+
+def cloud_parse(msg):
+    """Validate a serialised sensor_msgs/PointCloud2; returns (TeCloudInfo, [(name, offset, datatype, count)], byte offset of
+    its row_step * height data bytes)."""
+    info, off = TeCloudInfo(), C.c_size_t()
+    L = load()
+    _check(L.te_cloud_parse(msg, len(msg), C.byref(info), C.byref(off)))
+    fields = []
+    name = C.create_string_buffer(MSG_MAX_NAME)
+    o, t, n = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    for k in range(info.n_fields):
+        _check(L.te_cloud_field(msg, len(msg), k, name, C.byref(o), C.byref(t), C.byref(n)))
+        fields.append((name.value.decode(errors="replace"), o.value, t.value, n.value))
+    return info, fields, off.value
+
+
+def cloud_msg_write(info, field_names, points):
+    """A cloud of info.width points of len(field_names) float32 fields (host only); points: width x n_fields."""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1)
+    assert p.size == info.width * len(field_names), (p.size, info.width, len(field_names))
+    need = C.c_size_t()
+    L = load()
+    args = (C.byref(info), len(field_names), _names(list(field_names)), p.ctypes.data_as(C.POINTER(C.c_float)))
+    L.te_cloud_msg_write(*args, None, 0, C.byref(need))
+    out = C.create_string_buffer(max(need.value, 1))
+    _check(L.te_cloud_msg_write(*args, out, need.value, C.byref(need)))
+    return out.raw[:need.value]
+
+
+def cloud_spans():
+    """Cells of one wavefront's ballot, of one counting workgroup and of one scan workgroup's span (te_cloud_spans)."""
+    c = (C.c_size_t * 3)()
+    _check(load().te_cloud_spans(c))
+    return tuple(int(v) for v in c)
+
+
+def _layer_ids(layers):
+    ids = [LAYERS[v] if isinstance(v, str) else int(v) for v in layers]
+    return (C.c_int * max(len(ids), 1))(*ids), len(ids)
 
 
 def _image_array(array):
@@ -640,6 +731,68 @@ class Context:
         L.te_download_msg(*args, None, 0, C.byref(need))
         out = C.create_string_buffer(max(need.value, 1))
         _check(L.te_download_msg(*args, out, need.value, C.byref(need)))
+        return out.raw[:need.value]
+
+    def download_occupancy(self, layers, data_min=1.0, data_max=0.0, map_index=0, out=None):
+        """toOccupancyGrid on the device: `layers` (names or ids) of one map -> int8 [len(layers), rows * cols], each layer in
+        the message's (reversed) cell order.  data_min / data_max: one value or one per layer.  out: a reusable (possibly
+        pinned) int8 buffer."""
+        ids, n = _layer_ids(layers)
+        mn = np.ascontiguousarray(np.broadcast_to(np.asarray(data_min, np.float32), (n,)))
+        mx = np.ascontiguousarray(np.broadcast_to(np.asarray(data_max, np.float32), (n,)))
+        if out is None:
+            out = np.empty((n, self.rows * self.cols), np.int8)
+        assert out.dtype == np.int8 and out.flags.c_contiguous and out.size == n * self.rows * self.cols
+        fpt = C.POINTER(C.c_float)
+        _check(load().te_download_occupancy(self._h, int(map_index), n, ids, mn.ctypes.data_as(fpt), mx.ctypes.data_as(fpt),
+                                            C.c_void_p(out.ctypes.data)))
+        return out
+
+    def download_occupancy_msg(self, info, layer, data_min=1.0, data_max=0.0):
+        """toOccupancyGrid of `layer` of map 0 -> serialised nav_msgs/OccupancyGrid bytes (seq, stamp, frame_id from `info`)."""
+        need = C.c_size_t()
+        L = load()
+        args = (self._h, C.byref(info), LAYERS[layer] if isinstance(layer, str) else int(layer), float(data_min), float(data_max))
+        L.te_download_occupancy_msg(*args, None, 0, C.byref(need))
+        out = C.create_string_buffer(max(need.value, 1))
+        _check(L.te_download_occupancy_msg(*args, out, need.value, C.byref(need)))
+        return out.raw[:need.value]
+
+    def count_cloud(self, layers, point_layer, basic_layers=(), map_index=0):
+        """The sizing call of te_download_cloud: the number of points."""
+        ids, n = _layer_ids(layers)
+        bids, nb = _layer_ids(basic_layers)
+        cnt = C.c_size_t()
+        _check(load().te_download_cloud(self._h, int(map_index), n, ids, _layer_ids([point_layer])[0][0], nb, bids, None, 0,
+                                        C.byref(cnt)))
+        return cnt.value
+
+    def download_cloud(self, layers, point_layer, basic_layers=(), map_index=0, out=None):
+        """toPointCloud on the device: float32 [n_points, len(layers) + 2], the point layer's column replaced by x, y, z.
+        out: a reusable (possibly pinned) float32 buffer with room for every cell; the result is a view of it."""
+        ids, n = _layer_ids(layers)
+        bids, nb = _layer_ids(basic_layers)
+        pid = _layer_ids([point_layer])[0][0]
+        cnt = C.c_size_t()
+        L = load()
+        if out is None:  # (room for every cell: one call, the count is not run twice)
+            out = np.empty(max(self.rows * self.cols, 1) * (n + 2), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous
+        cap = out.size // (n + 2)
+        _check(L.te_download_cloud(self._h, int(map_index), n, ids, pid, nb, bids, C.c_void_p(out.ctypes.data), cap, C.byref(cnt)))
+        return out.reshape(-1)[:cnt.value * (n + 2)].reshape(cnt.value, n + 2)
+
+    def download_cloud_msg(self, info, layers, point_layer, basic_layers=()):
+        """toPointCloud of map 0: {field name: device layer} -> serialised sensor_msgs/PointCloud2 bytes."""
+        names = list(layers)
+        ids, n = _layer_ids(layers.values())
+        bids, nb = _layer_ids(basic_layers)
+        need = C.c_size_t()
+        L = load()
+        args = (self._h, C.byref(info), n, ids, _names(names), _layer_ids([point_layer])[0][0], nb, bids)
+        L.te_download_cloud_msg(*args, None, 0, C.byref(need))
+        out = C.create_string_buffer(max(need.value, 1))
+        _check(L.te_download_cloud_msg(*args, out, need.value, C.byref(need)))
         return out.raw[:need.value]
 
     def run_polygon_footprint(self, points_xy, yaw):

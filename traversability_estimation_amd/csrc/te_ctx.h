@@ -155,6 +155,13 @@ struct te_ctx {
   // the largest image so far, freed with the layers
   void* img_stage = nullptr;
   size_t img_stage_bytes = 0;
+  // te_download_occupancy (te_occupancy.hip) / te_download_cloud (te_cloud.hip): the converted cells / the block counts, block
+  // offsets and compacted records on the device; grown to the largest request so far, freed with the layers
+  struct OutScratch {
+    void* p = nullptr;
+    size_t bytes = 0;
+  };
+  OutScratch occ_out, cloud_counts, cloud_out;
   // te_prefetch_layers: whole-layer uploads on a thread of their own, through a second staging ring and the second copy
   // pool, beside whatever the caller does meanwhile (a filter on other layers, the download of its output)
   te::HostStager prefetcher;
@@ -199,5 +206,23 @@ void rebuild_footprint_tables(te_ctx* c);
 int sync_tiles(te_ctx* c);  // waits for the copy streams of the streaming-tile calls
 int run_whole_locked(te_ctx* c, unsigned flags);
 void release_path_discs(te_ctx* c);  // te_paths_api.hip: the spiral tables and the scratch of te_check_footprint_paths_radius
+// an output scratch buffer of at least `bytes` (grown after the stream has drained; caller holds c->mu, device set)
+inline int grow_out_scratch(te_ctx* c, te_ctx::OutScratch& s, size_t bytes) {
+  if (s.bytes >= bytes) return TE_OK;
+  if (s.p) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    (void)hipFree(s.p);
+    s.p = nullptr;
+    s.bytes = 0;
+  }
+  HIP_TRY(hipMalloc(&s.p, bytes));
+  s.bytes = bytes;
+  return TE_OK;
+}
+inline void release_out_scratch(te_ctx::OutScratch& s) {
+  if (s.p) (void)hipFree(s.p);
+  s.p = nullptr;
+  s.bytes = 0;
+}
 }  // namespace shim
 }  // namespace te

@@ -657,6 +657,9 @@ void free_layers(te_ctx* c) {
   if (c->img_stage) (void)hipFree(c->img_stage);
   c->img_stage = nullptr;
   c->img_stage_bytes = 0;
+  release_out_scratch(c->occ_out);
+  release_out_scratch(c->cloud_counts);
+  release_out_scratch(c->cloud_out);
   release_fp_any(c);  // (its prefix sums are sized by the geometry; rebuilt with the tables)
   release_path_discs(c);  // (its spiral tables are clipped to the map)
   c->have_robot_slope = false;

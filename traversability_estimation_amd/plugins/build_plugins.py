@@ -11,6 +11,7 @@ TEST = os.path.join(HERE, "plugin_chain_test")
 RADIUS_TEST = os.path.join(HERE, "plugin_radius_test")
 PATHS_TEST = os.path.join(HERE, "plugin_paths_test")
 IMAGE_TEST = os.path.join(HERE, "plugin_image_test")
+OUTPUT_TEST = os.path.join(HERE, "plugin_output_test")
 SRCS = ["src/DeviceMap.cpp", "src/SlopeFilter.cpp", "src/StepFilter.cpp", "src/RoughnessFilter.cpp",
         "src/FusedChainFilter.cpp", "src/SurfaceNormalsFilter.cpp", "src/TraversabilityMap.cpp", "stubs/pluginlib/registry.cpp"]
 
@@ -45,6 +46,12 @@ def build(verbose=False):
     # TraversabilityMap::setElevationFromImage (tests/test_plugins_image.py)
     cmd = cmd[:cmd.index(PATHS_TEST)] + [IMAGE_TEST]
     cmd[cmd.index(os.path.join(HERE, "test", "plugin_paths_test.cpp"))] = os.path.join(HERE, "test", "plugin_image_test.cpp")
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    # TraversabilityMap::getOccupancyGrid / getPointCloud (tests/test_plugins_output.py)
+    cmd = cmd[:cmd.index(IMAGE_TEST)] + [OUTPUT_TEST]
+    cmd[cmd.index(os.path.join(HERE, "test", "plugin_image_test.cpp"))] = os.path.join(HERE, "test", "plugin_output_test.cpp")
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

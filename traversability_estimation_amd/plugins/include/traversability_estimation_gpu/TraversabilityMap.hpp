@@ -14,7 +14,9 @@
 #include <vector>
 
 #include <grid_map_core/GridMap.hpp>
+#include <nav_msgs/OccupancyGrid.h>
 #include <sensor_msgs/Image.h>
+#include <sensor_msgs/PointCloud2.h>
 #include <traversability_msgs/FootprintPath.h>
 #include <traversability_msgs/TraversabilityResult.h>
 
@@ -73,12 +75,21 @@ class TraversabilityMap {
   }
   /*! The elevation map's geometry with the layers computed so far (getTraversabilityMap :196-199). */
   grid_map::GridMap getTraversabilityMap();
+  /*! GridMapRosConverter::toOccupancyGrid(map, layer, dataMin, dataMax, grid) on the device, for the layers
+   *  getTraversabilityMap() would return (config/visualization/traversability.yaml: the four score layers with dataMin 1,
+   *  dataMax 0): one byte per cell crosses PCIe (te_download_occupancy).  The caller stamps grid.header BEFORE the call:
+   *  info.map_load_time is set to that stamp, as toOccupancyGrid does.  False + error() for a layer that is not there. */
+  bool getOccupancyGrid(const std::string& layer, float dataMin, float dataMax, nav_msgs::OccupancyGrid& grid);
+  /*! GridMapRosConverter::toPointCloud(map, layers, pointLayer, cloud) on the device: only the cells whose point layer is
+   *  finite cross PCIe (te_download_cloud).  pointLayer must be one of `layers`. */
+  bool getPointCloud(const std::vector<std::string>& layers, const std::string& pointLayer, sensor_msgs::PointCloud2& cloud);
   bool traversabilityMapInitialized() const { return traversabilityMapInitialized_; }
   const std::string& error() const { return error_; }
 
  private:
   bool check(int rc);
   bool ensureCircularFootprint(double radius);
+  int deviceLayer(const std::string& name) const;  // te_layer of a layer getTraversabilityMap() would return, else -1
   mutable std::mutex mutex_;
   te_ctx* ctx_;
   te_params params_;

@@ -4,6 +4,7 @@
 #include <map>
 #include <string>
 #include <utility>
+#include <vector>
 
 #include <ros/ros.h>
 
@@ -342,6 +343,85 @@ bool TraversabilityMap::checkFootprintPaths(const std::vector<traversability_msg
     }
   }
   return complete;
+}
+
+int TraversabilityMap::deviceLayer(const std::string& name) const {
+  if (!elevationMapInitialized_) return -1;
+  if (name == "elevation") return TE_LAYER_ELEVATION;
+  if (traversabilityMapInitialized_) {
+    if (name == "traversability_slope") return TE_LAYER_SLOPE;
+    if (name == "traversability_step") return TE_LAYER_STEP;
+    if (name == "traversability_roughness") return TE_LAYER_ROUGHNESS;
+    if (name == "traversability") return TE_LAYER_TRAVERSABILITY;
+  }
+  if (footprintLayer_ && name == "traversability_footprint") return TE_LAYER_FOOTPRINT;
+  if (polygonLayers_ && name == "traversability_x") return TE_LAYER_TRAVERSABILITY_X;
+  if (polygonLayers_ && name == "traversability_rot") return TE_LAYER_TRAVERSABILITY_ROT;
+  return -1;
+}
+
+bool TraversabilityMap::getOccupancyGrid(const std::string& layer, float dataMin, float dataMax, nav_msgs::OccupancyGrid& grid) {
+  std::lock_guard<std::mutex> lock(mutex_);
+  const int id = deviceLayer(layer);
+  if (!ctx_ || id < 0) {
+    error_ = "getOccupancyGrid: no layer '" + layer + "'";
+    return false;
+  }
+  const int rows = geometry_.getSize()(0), cols = geometry_.getSize()(1);
+  grid.data.resize((size_t)rows * cols);
+  if (!check(te_download_occupancy(ctx_, 0, 1, &id, &dataMin, &dataMax, grid.data.data()))) return false;
+  // (toOccupancyGrid: the device layers are in logical order, so the start index does not enter)
+  grid.info.map_load_time = grid.header.stamp;  // (toOccupancyGrid: the header's stamp, which the caller has set)
+  grid.info.resolution = (float)geometry_.getResolution();
+  grid.info.width = (uint32_t)rows;
+  grid.info.height = (uint32_t)cols;
+  grid.info.origin = geometry_msgs::Pose();
+  grid.info.origin.position.x = geometry_.getPosition().x() - 0.5 * geometry_.getLength().x();
+  grid.info.origin.position.y = geometry_.getPosition().y() - 0.5 * geometry_.getLength().y();
+  return true;
+}
+
+bool TraversabilityMap::getPointCloud(const std::vector<std::string>& layers, const std::string& pointLayer, sensor_msgs::PointCloud2& cloud) {
+  std::lock_guard<std::mutex> lock(mutex_);
+  std::vector<int> ids;
+  const int point = deviceLayer(pointLayer);
+  for (const std::string& name : layers) ids.push_back(deviceLayer(name));
+  for (size_t k = 0; k < ids.size(); ++k)
+    if (ids[k] < 0) {
+      error_ = "getPointCloud: no layer '" + layers[k] + "'";
+      return false;
+    }
+  if (!ctx_ || point < 0 || ids.empty()) {
+    error_ = "getPointCloud: no point layer '" + pointLayer + "'";
+    return false;
+  }
+  // one call -- count, scan, scatter, one transfer of the points found -- into room for every cell; the rest is given back
+  size_t n = 0;
+  const size_t cells = (size_t)geometry_.getSize()(0) * geometry_.getSize()(1);
+  const uint32_t nFields = (uint32_t)ids.size() + 2;
+  cloud.data.resize(cells * nFields * sizeof(float));
+  if (!check(te_download_cloud(ctx_, 0, (int)ids.size(), ids.data(), point, 0, nullptr, reinterpret_cast<float*>(cloud.data.data()), cells, &n))) {
+    cloud.data.clear();
+    return false;
+  }
+  cloud.data.resize(n * nFields * sizeof(float));
+  cloud.fields.clear();
+  for (size_t k = 0; k < ids.size(); ++k)
+    for (const std::string& name : ids[k] == point ? std::vector<std::string>{"x", "y", "z"} : std::vector<std::string>{layers[k]}) {
+      sensor_msgs::PointField f;
+      f.name = name;
+      f.offset = (uint32_t)(4 * cloud.fields.size());
+      f.datatype = sensor_msgs::PointField::FLOAT32;
+      f.count = 1;
+      cloud.fields.push_back(f);
+    }
+  cloud.height = 1;
+  cloud.width = (uint32_t)n;
+  cloud.is_bigendian = 0;
+  cloud.point_step = 4 * nFields;
+  cloud.row_step = cloud.width * cloud.point_step;
+  cloud.is_dense = 0;
+  return true;
 }
 
 grid_map::GridMap TraversabilityMap::getTraversabilityMap() {

@@ -3,9 +3,16 @@
 #include <string>
 #include <vector>
 
+namespace ros {
+struct Time {  // (stand-in for ros::Time: the two fields a message carries)
+  unsigned sec = 0, nsec = 0;
+};
+}  // namespace ros
+
 namespace std_msgs {
 struct Header {
   unsigned seq = 0;
+  ros::Time stamp;
   std::string frame_id;
 };
 }  // namespace std_msgs
