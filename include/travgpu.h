@@ -80,7 +80,8 @@ typedef enum te_status {
   TE_ERR_HIP = -4,         /* HIP runtime error (message has hipGetErrorString) */
   TE_ERR_NO_DEVICE = -5,   /* no usable gfx950 device: the library never falls back to the CPU */
   TE_ERR_UNSUPPORTED = -6  /* a filter disc above 32 cells or with more than 32 offsets on its circle, under TE_OPT_FILTER_ANY_RADIUS = 0 (the
-                              default); under 1 or 2, and for a circular footprint, only tables that do not fit in device memory */
+                              default); under 1 or 2, and for a circular footprint, only tables that do not fit in device memory; te_expr_check /
+                              te_run_expression: valid EigenLab that is not built (the matrix product, transpose, plain min / max ...) */
 } te_status;
 
 /* Layers owned by a context (device-resident, [batch][cols][rows] float32). */
@@ -614,6 +615,67 @@ int te_cloud_field(const void* msg, size_t len, int k, char* name, uint32_t* off
 /* The spans of the compaction (tests place holes across them): cells[0] = cells of one wavefront's ballot, cells[1] = cells
  * one workgroup counts, cells[2] = cells one scan workgroup's span covers. */
 int te_cloud_spans(size_t cells[3]);
+
+/* ---- gridMapFilters/MathExpressionFilter with ANY expression (robot_filter_parameter.yaml:29-33) ----
+ * te_run_chain / TE_FILTER_COMBINE run the weighted sum of the three scores (te_params: w_scale, w_slope, w_step, w_rough) and
+ * keep their fused path.  te_run_expression evaluates any expression of the language below over the resident layers into
+ * TE_LAYER_TRAVERSABILITY, one pass over the map (plus two short reduction launches when the text holds reductions).
+ *
+ * The language restates EigenLab as MathExpressionFilter uses it on MatrixXf.  EigenLab is not part of the reference tree nor of
+ * this project's build, so like the image and output routes this is a STATED CONTRACT restated from memory;
+ * the one reference-held pin is the shipped expression on the bag map.
+ *   operands   a layer by its reference name (elevation, traversability_slope, traversability_step, traversability_roughness,
+ *              traversability, traversability_footprint, surface_normal_x / _y / _z, slope_footprint, step_footprint,
+ *              roughness_footprint, traversability_x, traversability_rot, robot_slope); a number (digits with an optional
+ *              fraction and exponent, or .digits), read as (float)(double)text.  Every value is float32 and every operation
+ *              rounds to float32.  A node is a scalar (1 x 1) or a map; a scalar broadcasts.
+ *   operators  + - (binary, any mix of scalar and map); * with at least one scalar side (map * map is EigenLab's MATRIX product:
+ *              TE_ERR_UNSUPPORTED, write .* instead); .* ./ and / element-wise (map / map is the element-wise quotient);
+ *              ^ with a scalar exponent and .^ are element-wise powf, left-associative; unary - and + bind as in MATLAB:
+ *              -a^2 = -(a^2), 2^-1 is allowed; parentheses.
+ *   functions  abs sqrt square exp log log10 sin cos tan asin acos, element-wise; cwiseMin(a, b) = (b < a) ? b : a and
+ *              cwiseMax(a, b) = (a < b) ? b : a -- std::min / std::max operand order, so they are NOT symmetric in NaN: a NaN in
+ *              `a` is returned, a NaN in `b` is dropped.
+ *   reductions sum mean sumOfFinites meanOfFinites minOfFinites maxOfFinites numberOfFinites of any element-wise
+ *              sub-expression, taken per map of the batch; the result is a scalar.  They do not nest; at most 4 per expression.
+ *              Sums accumulate in double in a fixed order (the same bits run after run) and are rounded to float32 at the end;
+ *              mean = sum / count in double, then rounded.  A map without a finite cell gives NaN for min / max /
+ *              meanOfFinites and 0 for sumOfFinites / numberOfFinites.
+ *   constants  folded at compile time through + - * / and unary minus only (exact in IEEE float32 on both sides), never through
+ *              a function.
+ *   limits     64 instructions after folding, 8 distinct layers, an operand stack of 8, 4 reductions, 64 nested parentheses /
+ *              prefix signs.
+ *   errors     TE_ERR_BAD_PARAM, the message carries the column: syntax errors, unknown names, wrong arity, a limit above.
+ *              TE_ERR_UNSUPPORTED: valid EigenLab that is not built -- the matrix product, transpose, trace, norm, zeros / ones /
+ *              eye and the other matrix functions, plain min / max (Eigen's NaN behaviour there depends on its version),
+ *              indexing, assignment, relational operators. */
+typedef struct te_expr_info {
+  int32_t n_instructions; /* after constant folding, reduction arguments included */
+  uint32_t layer_mask;    /* bit TE_LAYER_* of every layer the expression reads */
+  int32_t n_reductions;
+  int32_t stack_depth;    /* deepest operand stack of the main expression and of the reduction arguments */
+} te_expr_info;
+/* Host only, no context: compiles `text` and describes it (`info` may be NULL). */
+int te_expr_check(const char* text, te_expr_info* info);
+/* traversability = text, on every map of the batch; asynchronous on the context's stream like te_run_chain.
+ *   out_layer must be TE_LAYER_TRAVERSABILITY, the filter's output_layer (TE_ERR_INVALID_ARG otherwise).  The layer may appear
+ *     in the text: the evaluation is in place, cell by cell, behind the reductions.
+ *   TE_ERR_NOT_READY: no geometry; an input layer that does not exist yet -- surface_normal_* unless the last whole-map chain
+ *     ran with TE_RUN_KEEP_NORMALS (or they were uploaded / written by TE_FILTER_NORMALS), the three memo layers before a
+ *     footprint pass wrote them, traversability_x / _rot before te_run_polygon_footprint, robot_slope while absent.
+ *   A failed call leaves every layer as it was.
+ *   Afterwards the context is what te_upload_layer(TE_LAYER_TRAVERSABILITY, the same values) leaves: the layer counts as
+ *     written from outside (te_run_footprint takes the double-precision kernel), footprint and mask results follow the upload
+ *     path, the chain's state and te_get_params are untouched.  te_run_footprint and the path checks then read the new values;
+ *     the next te_run_chain writes the weighted sum again.
+ *   A prefetch in flight that writes a layer the text reads (or the traversability layer) is joined first.
+ *   Limit: te_run_chain_region still recombines its region with the weights.  With a general expression run the region without
+ *     TE_RUN_FOOTPRINT, then te_run_expression, then te_run_footprint. */
+int te_run_expression(te_ctx* ctx, const char* text, int out_layer);
+/* Measurement aid: `iters` te_run_expression launches of `text`, one HIP event pair each, ms[k] = device time of the k-th
+ * (after `warmup` untimed ones), like te_time_chain_samples.  text = NULL times te_run_filter(TE_FILTER_COMBINE) the same way: the
+ * weighted sum's own kernel, the yardstick of tools/expr_bench.py. */
+int te_time_expression_samples(te_ctx* ctx, const char* text, int warmup, int iters, float* ms);
 
 const char* te_last_error(void);
 const char* te_version(void);

@@ -47,7 +47,8 @@ SYMBOLS = ["te_params_default", "te_params_validate", "te_device_count", "te_cre
            "te_set_check_robot_inclination", "te_check_inclination", "te_polygon_untraversable_hull",
            "te_image_parse", "te_upload_image", "te_upload_image_msg",
            "te_download_occupancy", "te_download_occupancy_msg", "te_occupancy_msg_write", "te_occupancy_parse",
-           "te_download_cloud", "te_download_cloud_msg", "te_cloud_msg_write", "te_cloud_parse", "te_cloud_field", "te_cloud_spans"]
+           "te_download_cloud", "te_download_cloud_msg", "te_cloud_msg_write", "te_cloud_parse", "te_cloud_field", "te_cloud_spans",
+           "te_expr_check", "te_run_expression", "te_time_expression_samples"]
 MSG_MAX_NAME = 64
 OCCUPANCY_MAX_LAYERS = CLOUD_MAX_LAYERS = 16
 POINTFIELD_FLOAT32 = 7
@@ -128,6 +129,10 @@ class TeCloudInfo(C.Structure):
 IMAGE_ENCODINGS = {"mono8": (1, 1), "8UC1": (1, 1), "mono16": (1, 2), "16UC1": (1, 2),
                    "rgb8": (3, 1), "bgr8": (3, 1), "8UC3": (3, 1), "rgba8": (4, 1), "bgra8": (4, 1), "8UC4": (4, 1),
                    "rgb16": (3, 2), "bgr16": (3, 2), "16UC3": (3, 2), "rgba16": (4, 2), "bgra16": (4, 2), "16UC4": (4, 2)}
+
+
+class TeExprInfo(C.Structure):
+    _fields_ = [("n_instructions", C.c_int32), ("layer_mask", C.c_uint32), ("n_reductions", C.c_int32), ("stack_depth", C.c_int32)]
 
 
 class TePathCheckStats(C.Structure):
@@ -247,6 +252,9 @@ def load():
         L.te_cloud_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(TeCloudInfo), szp]
         L.te_cloud_field.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_char_p, u32p, u32p, u32p]
         L.te_cloud_spans.argtypes = [szp]
+        L.te_expr_check.argtypes = [C.c_char_p, C.POINTER(TeExprInfo)]
+        L.te_run_expression.argtypes = [vp, C.c_char_p, C.c_int]
+        L.te_time_expression_samples.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.te_last_error.restype = C.c_char_p
         L.te_version.restype = C.c_char_p
         _lib = L
@@ -466,6 +474,16 @@ def path_polygons(paths, points_xyz, conservative=None):
     return [[(xy[voff[q]:voff[q + 1]].copy(), float(area[q])) for q in range(first[k], first[k + 1])] for k in range(n)]
 
 
+def expr_check(text):
+    """te_expr_check: compiles a MathExpressionFilter expression on the host (no device, no context).  Returns
+    {"n_instructions", "layers" (names, in te_layer order), "n_reductions", "stack_depth"}; raises TeError with the library's
+    message and class (TE_ERR_BAD_PARAM: not an expression of the language; TE_ERR_UNSUPPORTED: valid EigenLab that is not built)."""
+    info = TeExprInfo()
+    _check(load().te_expr_check(str(text).encode(), C.byref(info)))
+    return {"n_instructions": int(info.n_instructions), "layers": [k for k, v in LAYERS.items() if info.layer_mask >> v & 1],
+            "n_reductions": int(info.n_reductions), "stack_depth": int(info.stack_depth)}
+
+
 def device_count():
     n = C.c_int(0)
     rc = load().te_device_count(C.byref(n))
@@ -614,6 +632,17 @@ class Context:
 
     def run_footprint(self):
         _check(load().te_run_footprint(self._h))
+
+    def run_expression(self, text, out="traversability"):
+        """te_run_expression: `out` = text over the resident layers (any MathExpressionFilter expression of the language in
+        include/travgpu.h); asynchronous like run_chain.  The context is then what upload_layer(out, the same values) leaves."""
+        _check(load().te_run_expression(self._h, str(text).encode(), LAYERS[out] if isinstance(out, str) else int(out)))
+
+    def time_expression_samples(self, text, warmup=3, iters=50):
+        """Device ms of `iters` run_expression(text) launches, one event pair each; text=None times run_filter("combine")."""
+        ms = (C.c_float * int(iters))()
+        _check(load().te_time_expression_samples(self._h, None if text is None else str(text).encode(), int(warmup), int(iters), ms))
+        return np.array(ms[:], dtype=np.float64)
 
     def check_footprint_paths(self, paths, map_index=0):
         """paths: sequence of (n_i, 2) arrays of (x, y) poses.  Returns (is_safe[bool], traversability[float64], status[int32])

@@ -162,6 +162,14 @@ struct te_ctx {
     size_t bytes = 0;
   };
   OutScratch occ_out, cloud_counts, cloud_out;
+  // te_run_expression (te_expr.hip): the per-block partials of its reductions and, behind them, the folded results per
+  // (map, reduction); grown to the largest request so far, freed with the layers
+  OutScratch expr_scratch;
+  // bit TE_LAYER_* of the optional layers that hold values: surface_normal_* (a whole-map chain with TE_RUN_KEEP_NORMALS or
+  // TE_FILTER_NORMALS sets them, a whole-map chain without the flag clears them like the DeletionFilter), the three memo layers
+  // (a whole-map footprint pass with TE_RUN_FOOTPRINT_MEMO), and any layer an upload or te_device_ptr touched (ensure_input_layer).
+  // Read by te_run_expression only; cleared with the layers.
+  unsigned layers_written = 0;
   // te_prefetch_layers: whole-layer uploads on a thread of their own, through a second staging ring and the second copy
   // pool, beside whatever the caller does meanwhile (a filter on other layers, the download of its output)
   te::HostStager prefetcher;

@@ -660,6 +660,8 @@ void free_layers(te_ctx* c) {
   release_out_scratch(c->occ_out);
   release_out_scratch(c->cloud_counts);
   release_out_scratch(c->cloud_out);
+  release_out_scratch(c->expr_scratch);
+  c->layers_written = 0;
   release_fp_any(c);  // (its prefix sums are sized by the geometry; rebuilt with the tables)
   release_path_discs(c);  // (its spiral tables are clipped to the map)
   c->have_robot_slope = false;
@@ -695,6 +697,7 @@ float* layer_ptr(te_ctx* c, int layer) {
 
 // the optional input layer robot_slope exists from its first upload on (every cell NaN = not valid until written)
 int ensure_input_layer(te_ctx* c, int layer) {
+  c->layers_written |= bit(layer);  // (every upload route and te_device_ptr pass here before they write: te_ctx.h)
   if (layer != TE_LAYER_ROBOT_SLOPE || c->robot_slope) return TE_OK;
   HIP_TRY(hipSetDevice(c->device));
   void* p = nullptr;
@@ -706,6 +709,16 @@ int ensure_input_layer(te_ctx* c, int layer) {
   }
   c->robot_slope = (float*)p;
   return TE_OK;
+}
+
+// te_ctx::layers_written: a whole-map chain leaves the normal layers with TE_RUN_KEEP_NORMALS and drops them without
+constexpr unsigned kNormalLayers = bit(TE_LAYER_NORMAL_X) | bit(TE_LAYER_NORMAL_Y) | bit(TE_LAYER_NORMAL_Z);
+constexpr unsigned kMemoLayers = bit(TE_LAYER_SLOPE_FOOTPRINT) | bit(TE_LAYER_STEP_FOOTPRINT) | bit(TE_LAYER_ROUGHNESS_FOOTPRINT);
+static void note_normals_kept(te_ctx* c, unsigned flags) {
+  if (flags & (TE_RUN_KEEP_NORMALS | TE_RUN_NORMALS_ONLY))
+    c->layers_written |= kNormalLayers;
+  else
+    c->layers_written &= ~kNormalLayers;
 }
 
 int run_chain_locked(te_ctx* c, unsigned flags, const Region& r) {
@@ -749,6 +762,7 @@ int run_chain_locked(te_ctx* c, unsigned flags, const Region& r) {
   c->footprint_done = false;  // the layers the footprint pass reads have changed
   c->mask_done = false;
   if (r.map < 0) c->trav_external = false;  // every cell of the combined layer now comes from the chain
+  if (r.map < 0) note_normals_kept(c, flags);
   return TE_OK;
 }
 
@@ -767,6 +781,7 @@ int run_footprint_locked(te_ctx* c, unsigned flags, bool fresh = false) {
   c->combine_deferred = false;
   c->footprint_done = true;
   c->mask_done = true;
+  if (flags & TE_RUN_FOOTPRINT_MEMO) c->layers_written |= kMemoLayers;
   return TE_OK;
 }
 
@@ -829,6 +844,8 @@ int run_whole_locked(te_ctx* c, unsigned flags) {
       c->footprint_done = (flags & TE_RUN_FOOTPRINT) != 0;
       c->mask_done = c->footprint_done;
       c->combine_deferred = false;
+      note_normals_kept(c, flags);
+      if ((flags & TE_RUN_FOOTPRINT) && (flags & TE_RUN_FOOTPRINT_MEMO)) c->layers_written |= kMemoLayers;
       return TE_OK;
     }
   }
@@ -1236,6 +1253,7 @@ int te_run_filter(te_ctx* c, int filter, unsigned flags) {
   c->footprint_done = false;
   c->mask_done = false;
   c->trav_external = true;
+  if (filter == TE_FILTER_NORMALS) c->layers_written |= kNormalLayers;
   return TE_OK;
 }
 

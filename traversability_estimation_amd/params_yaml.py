@@ -9,7 +9,9 @@ What the ROS node does with these files (reference, file:line):
 
 The chain this library runs is the fixed sequence normals -> slope -> step -> roughness -> weighted sum -> deletion; a file
 that asks for anything else (another order, another filter type, an expression that is not a weighted sum of the three
-scores, an input layer other than `elevation`) is refused with a message rather than half-applied.  Host-side plumbing
+scores, an input layer other than `elevation`) is refused with a message rather than half-applied.  An expression of any other
+form is served by `params_and_expression_from_yaml`: the chain runs with default weights and the text goes to
+`Context.run_expression` (te_run_expression) behind it.  Host-side plumbing
 for bench.py and the tests: the plugins themselves get their parameters from `FilterBase::getParam`, as in the reference.
 """
 import re
@@ -79,8 +81,10 @@ def _axis(v):
         raise ParamsYamlError(f"normal_vector_positive_axis must be x, y or z (got '{v}')")
 
 
-def filter_chain_fields(doc):
-    """te_params fields (plain dict) + {"keep_normals": bool} from the `traversability_map_filters` list."""
+def filter_chain_fields(doc, general_expression=False):
+    """te_params fields (plain dict) + {"keep_normals": bool} from the `traversability_map_filters` list.
+    general_expression: an expression parse_weighted_sum refuses leaves the four weights out (their defaults hold) instead
+    of raising: the caller hands the text to te_run_expression."""
     if not isinstance(doc, dict) or CHAIN_KEY not in doc:
         raise ParamsYamlError(f"no '{CHAIN_KEY}' list in the filter parameter file")
     chain = doc[CHAIN_KEY]
@@ -118,7 +122,12 @@ def filter_chain_fields(doc):
             raise ParamsYamlError(f"map_type must stay '{dflt}': the footprint checks read the layers by these names (TraversabilityMap.cpp:52-56)")
     if str(comb.get("output_layer", "traversability")) != "traversability":
         raise ParamsYamlError("MathExpressionFilter: output_layer must be 'traversability'")
-    out.update({k: float(v) for k, v in parse_weighted_sum(str(need(comb, "expression", "MathExpressionFilter"))).items()})
+    text = str(need(comb, "expression", "MathExpressionFilter"))
+    try:
+        out.update({k: float(v) for k, v in parse_weighted_sum(text).items()})
+    except ParamsYamlError:
+        if not general_expression:
+            raise
     deleted = set()
     if len(chain) == 6:
         deleted = {str(s) for s in (prm[5].get("layers") or [])}
@@ -154,8 +163,25 @@ def robot_fields(doc):
     return out
 
 
-def fields_from_yaml(filter_yaml, footprint_yaml=None, robot_yaml=None):
-    f = filter_chain_fields(_load(filter_yaml))
+def chain_expression(filter_yaml):
+    """(text, is_weighted_sum): the MathExpressionFilter's expression as the file has it, and whether parse_weighted_sum
+    accepts it -- te_run_chain's fused combine runs that form, te_run_expression any other."""
+    doc = _load(filter_yaml)
+    if not isinstance(doc, dict) or CHAIN_KEY not in doc:
+        raise ParamsYamlError(f"no '{CHAIN_KEY}' list in the filter parameter file")
+    found = [f for f in doc[CHAIN_KEY] if str(f.get("type")) == "gridMapFilters/MathExpressionFilter"]
+    if len(found) != 1 or "expression" not in (found[0].get("params") or {}):
+        raise ParamsYamlError("MathExpressionFilter did not find param expression")
+    text = str(found[0]["params"]["expression"])
+    try:
+        parse_weighted_sum(text)
+        return text, True
+    except ParamsYamlError:
+        return text, False
+
+
+def fields_from_yaml(filter_yaml, footprint_yaml=None, robot_yaml=None, general_expression=False):
+    f = filter_chain_fields(_load(filter_yaml), general_expression)
     if footprint_yaml is not None:
         f.update(footprint_fields(_load(footprint_yaml)))
     if robot_yaml is not None:
@@ -170,3 +196,19 @@ def params_from_yaml(capi, filter_yaml, footprint_yaml=None, robot_yaml=None):
     p = capi.default_params(**f)
     capi.validate_params(p)
     return p, (capi.RUN_KEEP_NORMALS if keep else 0)
+
+
+def params_and_expression_from_yaml(capi, filter_yaml, footprint_yaml=None, robot_yaml=None):
+    """(te_params, run flags, text or None).  A weighted sum: what params_from_yaml gives, and None.  Any other expression: the
+    params with the four weights at their defaults, and the text to hand to Context.run_expression behind run_chain (before
+    run_footprint); the library's own compiler has accepted it (capi.expr_check raises TeError otherwise)."""
+    text, weighted = chain_expression(filter_yaml)
+    if weighted:
+        p, flags = params_from_yaml(capi, filter_yaml, footprint_yaml, robot_yaml)
+        return p, flags, None
+    f = fields_from_yaml(filter_yaml, footprint_yaml, robot_yaml, general_expression=True)
+    keep = f.pop("keep_normals")
+    p = capi.default_params(**f)
+    capi.validate_params(p)
+    capi.expr_check(text)
+    return p, (capi.RUN_KEEP_NORMALS if keep else 0), text

@@ -12,6 +12,7 @@ RADIUS_TEST = os.path.join(HERE, "plugin_radius_test")
 PATHS_TEST = os.path.join(HERE, "plugin_paths_test")
 IMAGE_TEST = os.path.join(HERE, "plugin_image_test")
 OUTPUT_TEST = os.path.join(HERE, "plugin_output_test")
+EXPRESSION_TEST = os.path.join(HERE, "plugin_expression_test")
 SRCS = ["src/DeviceMap.cpp", "src/SlopeFilter.cpp", "src/StepFilter.cpp", "src/RoughnessFilter.cpp",
         "src/FusedChainFilter.cpp", "src/SurfaceNormalsFilter.cpp", "src/TraversabilityMap.cpp", "stubs/pluginlib/registry.cpp"]
 
@@ -52,6 +53,12 @@ def build(verbose=False):
     # TraversabilityMap::getOccupancyGrid / getPointCloud (tests/test_plugins_output.py)
     cmd = cmd[:cmd.index(IMAGE_TEST)] + [OUTPUT_TEST]
     cmd[cmd.index(os.path.join(HERE, "test", "plugin_image_test.cpp"))] = os.path.join(HERE, "test", "plugin_output_test.cpp")
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    # FusedChainFilter with an `expression` parameter (tests/test_plugins_expression.py)
+    cmd = cmd[:cmd.index(OUTPUT_TEST)] + [EXPRESSION_TEST]
+    cmd[cmd.index(os.path.join(HERE, "test", "plugin_output_test.cpp"))] = os.path.join(HERE, "test", "plugin_expression_test.cpp")
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

@@ -22,7 +22,10 @@ class FusedChainFilter : public FilterBase<T> {
   virtual ~FusedChainFilter();
   /*! Parameters (all optional, defaults = the shipped YAML): normals_radius, slope_critical_value,
    *  step_critical_value, first_window_radius, second_window_radius, critical_cell_number,
-   *  roughness_critical_value, estimation_radius, keep_surface_normals (int). */
+   *  roughness_critical_value, estimation_radius, keep_surface_normals (int), expression (string: the
+   *  MathExpressionFilter's expression when it is not the shipped weighted sum -- any text te_expr_check
+   *  accepts, include/travgpu.h; it is evaluated on the device behind the chain and replaces the
+   *  "traversability" layer; configure() fails with the library's message for a text it refuses). */
   virtual bool configure();
   virtual bool update(const T& mapIn, T& mapOut);
 
@@ -30,6 +33,7 @@ class FusedChainFilter : public FilterBase<T> {
   te_params params_;
   int keepNormals_;
   int rankRule_;  // unit_z_for_planar_discs (TE_OPT_NORMALS_RANK_RULE)
+  std::string expression_;  // empty: the weighted sum of the chain
 };
 
 }  // namespace filters

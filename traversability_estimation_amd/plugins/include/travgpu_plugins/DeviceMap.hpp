@@ -46,6 +46,8 @@ class DeviceMap {
   unsigned long uploadsSkipped() const { return uploads_skipped_; }
   bool runFilter(int filter);
   bool runChain(unsigned flags);
+  /*! traversability = text over the resident layers (te_run_expression), behind runChain. */
+  bool runExpression(const std::string& text);
   bool download(grid_map::GridMap& map, const std::string& layer, int te_layer);
   const std::string& error() const { return error_; }
 

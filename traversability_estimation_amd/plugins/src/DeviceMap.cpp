@@ -227,6 +227,10 @@ bool DeviceMap::runChain(unsigned flags) {
   resident_[TE_LAYER_NORMAL_X].valid = resident_[TE_LAYER_NORMAL_Y].valid = resident_[TE_LAYER_NORMAL_Z].valid = false;
   return check(te_run_chain(ctx_, flags));
 }
+bool DeviceMap::runExpression(const std::string& text) {
+  resident_[TE_LAYER_TRAVERSABILITY].valid = false;  // (written on the device: whatever a plugin uploaded there is gone)
+  return check(te_run_expression(ctx_, text.c_str(), TE_LAYER_TRAVERSABILITY));
+}
 
 bool DeviceMap::download(grid_map::GridMap& map, const std::string& layer, int te_layer) {
   if (start_row_ || start_col_) return check(te_download_layer_circular(ctx_, te_layer, map.get(layer).data(), 0, start_row_, start_col_));

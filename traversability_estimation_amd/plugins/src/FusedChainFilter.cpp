@@ -33,6 +33,13 @@ bool FusedChainFilter<T>::configure() {
   FilterBase<T>::getParam(std::string("estimation_radius"), params_.rough_radius);
   FilterBase<T>::getParam(std::string("keep_surface_normals"), keepNormals_);
   FilterBase<T>::getParam(std::string("unit_z_for_planar_discs"), rankRule_);  // TE_OPT_NORMALS_RANK_RULE (see SurfaceNormalsFilter)
+  // the MathExpressionFilter's expression when it is not the weighted sum: compiled here, run behind the chain
+  expression_.clear();
+  FilterBase<T>::getParam(std::string("expression"), expression_);
+  if (!expression_.empty() && te_expr_check(expression_.c_str(), nullptr) != TE_OK) {
+    ROS_ERROR("%s", te_last_error());
+    return false;
+  }
   if (te_params_validate(&params_) != TE_OK) {
     ROS_ERROR("%s", te_last_error());
     return false;
@@ -51,7 +58,7 @@ bool FusedChainFilter<T>::update(const T& mapIn, T& mapOut) {
   std::lock_guard<std::mutex> lock(dev.mutex());
   bool ok = dev.prepare(mapOut) && dev.setParams(params_) && dev.setOption(TE_OPT_NORMALS_RANK_RULE, rankRule_ ? 1 : 0) &&
             dev.upload(mapOut, "elevation", TE_LAYER_ELEVATION) &&
-            dev.runChain(keepNormals_ ? TE_RUN_KEEP_NORMALS : 0u);
+            dev.runChain(keepNormals_ ? TE_RUN_KEEP_NORMALS : 0u) && (expression_.empty() || dev.runExpression(expression_));
   for (int k = 0; ok && k < 4; ++k) {
     mapOut.add(kOut[k]);
     ok = dev.download(mapOut, kOut[k], kLayer[k]);
