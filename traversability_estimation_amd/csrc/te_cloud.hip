@@ -192,9 +192,9 @@ int count_points(te_ctx* c, const Spec& s, size_t& total) {
   HIP_TRY(hipSetDevice(c->device));
   const size_t n = (size_t)c->geo.rows * c->geo.cols, nb = n_blocks(n);
   const size_t counts_bytes = (nb * sizeof(unsigned) + 7) & ~(size_t)7;
-  if (const int rc = grow_out_scratch(c, c->cloud_counts, counts_bytes + (nb + 1) * sizeof(unsigned long long))) return rc;
-  unsigned* counts = (unsigned*)c->cloud_counts.p;
-  unsigned long long* offsets = (unsigned long long*)((char*)c->cloud_counts.p + counts_bytes);
+  HIP_TRY(c->lmem.cloud_counts.reserve(counts_bytes + (nb + 1) * sizeof(unsigned long long), c->stream));
+  unsigned* counts = c->lmem.cloud_counts.as<unsigned>();
+  unsigned long long* offsets = (unsigned long long*)(c->lmem.cloud_counts.as<char>() + counts_bytes);
   HIP_TRY(launch_count_scan(s, n, counts, offsets, c->stream));
   unsigned long long t = 0;
   HIP_TRY(hipMemcpyAsync(&t, offsets + nb, sizeof(t), hipMemcpyDeviceToHost, c->stream));
@@ -208,11 +208,11 @@ int scatter_points(te_ctx* c, const Spec& s, size_t total, void* dst) {
   if (total == 0) return TE_OK;
   const size_t n = (size_t)c->geo.rows * c->geo.cols, nb = n_blocks(n);
   const size_t counts_bytes = (nb * sizeof(unsigned) + 7) & ~(size_t)7;
-  const unsigned long long* offsets = (const unsigned long long*)((char*)c->cloud_counts.p + counts_bytes);
+  const unsigned long long* offsets = (const unsigned long long*)(c->lmem.cloud_counts.as<char>() + counts_bytes);
   const size_t bytes = total * (size_t)s.n_fields * sizeof(float);
-  if (const int rc = grow_out_scratch(c, c->cloud_out, bytes)) return rc;
-  HIP_TRY(launch_scatter(s, c->geo, n, offsets, total, (float*)c->cloud_out.p, c->stream));
-  HIP_TRY(c->stager.download(dst, c->cloud_out.p, bytes, c->stream));  // (returns when dst holds the records)
+  HIP_TRY(c->lmem.cloud_out.reserve(bytes, c->stream));
+  HIP_TRY(launch_scatter(s, c->geo, n, offsets, total, c->lmem.cloud_out.as<float>(), c->stream));
+  HIP_TRY(c->stager.download(dst, c->lmem.cloud_out.p, bytes, c->stream));  // (returns when dst holds the records)
   return TE_OK;
 }
 

@@ -4,6 +4,13 @@
 //   te_paths_api.hip path checks, inclination, polygon footprint layers (N2, N3)
 //   te_multi.hip     the batch axis over several contexts / devices (te_shard_range, te_bcast_params over RCCL, *_multi)
 // No CPU fallback of any kind: without a gfx950 device te_create() fails with TE_ERR_NO_DEVICE.
+//
+// Device memory: every allocation the context keeps is a DevBuf (te_devbuf.h) declared in one of two groups, and the group
+// says when it is freed -- te_ctx::LayerMem with the layers (free_layers: te_set_geometry to another shape, te_destroy),
+// te_ctx::CtxMem with the context (te_destroy).  Each group is released in one statement, so a buffer declared there
+// cannot be forgotten.  What must stay next to a release are the pointers DERIVED from a buffer: they are cleared or
+// re-derived wherever their buffer is released or regrown (c->fp.any_*, Disc::tab, Layers::tie_scratch / hole_queue,
+// c->poly_rot, c->face_flags and the slab's layer pointers in c->L).  A call's own temporaries are local DevBufs.
 #pragma once
 #include <math.h>
 #include <stdarg.h>
@@ -21,6 +28,7 @@
 #include <vector>
 
 #include <cstdlib>
+#include "te_devbuf.h"
 #include "te_disc_table.h"
 #include "te_internal.h"
 #include "te_msg.h"
@@ -52,48 +60,63 @@ struct te_ctx {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   te_params params;
   bool have_params = false, have_geo = false, have_elev = false, chain_done = false, footprint_done = false;
-  float* poly_x = nullptr;  // traversability_x / traversability_rot (one allocation, made by the first te_run_polygon_footprint)
-  float* poly_rot = nullptr;
-  float* robot_slope = nullptr;  // layer robot_slope (checkInclination); allocated by its first upload, NaN until written
+  // te_check_footprint_paths_radius (te_path_discs.hip): the spiral table of one radius class on the device, by (radius,
+  // offset, resolution, map size)
+  struct PdTable {
+    double radius = 0.0, offset = 0.0, res = 0.0;
+    int rows = 0, cols = 0;  // (the clip)
+    te::DevBuf dev;          // FpEntry [n_spiral]
+    int n_spiral = 0;
+    unsigned long long used = 0;  // pd_clock at its last use
+  };
+  static constexpr int kPdTables = 16;
+  // Device memory freed with the layers (free_layers).  The "grown" ones hold the largest request so far.
+  struct LayerMem {
+    te::DevBuf slab;         // te_slab.h: the layers of c->L, the mask, the lists and flag grids of the footprint pass, c->face_flags
+    te::DevBuf poly;         // traversability_x, and behind it traversability_rot (c->poly_rot); made by the first te_run_polygon_footprint
+    te::DevBuf poly_stream;  // offset tables of the two footprint polygons (device copy of poly_stream_host); grown
+    te::DevBuf robot_slope;  // layer robot_slope (checkInclination); allocated by its first upload, NaN until written
+    te::DevBuf tie_scratch;  // one float per cell: the step filter at a tie radius (allocated when a launch first needs it)
+    te::DevBuf img_stage;    // te_upload_image: the raw image bytes (te_image.hip converts and transposes them into a layer); grown
+    // te_download_occupancy (te_occupancy.hip) / te_download_cloud (te_cloud.hip): the converted cells / the block counts,
+    // block offsets and compacted records; grown
+    te::DevBuf occ_out, cloud_counts, cloud_out;
+    // te_run_expression (te_expr.hip): the per-block partials of its reductions and, behind them, the folded results per
+    // (map, reduction); grown
+    te::DevBuf expr_scratch;
+    // the circular footprint at any reach (te_footprint_any.hip): its tables and its prefix-sum scratch ([batch][cols][rows + 1]
+    // doubles, then as many unsigned), allocated when the footprint tables are rebuilt for that route; c->fp.any_* point into them
+    struct FpAny {
+      te::DevBuf tab, prefix;
+    } fpa;
+    // te_check_footprint_paths_radius: at most kPdTables spiral tables, the least recently used one replaced (they are
+    // clipped to the map); pd_scratch: the call's staging buffers and memo, grown
+    PdTable pd_tables[kPdTables];
+    te::DevBuf pd_scratch;
+  } lmem;
+  // Device memory freed with the context (te_destroy)
+  struct CtxMem {
+    te::DevBuf spiral;         // uint32_t [kMaxSpiral]: the footprint spiral of reach <= 20, packed (fp_pack)
+    te::DevBuf count;          // two counters of k_count_invalid
+    te::DevBuf hole_queue;     // scratch of k_normals3's sparse-hole march (allocated when a launch first picks it)
+    te::DevBuf clip_table, fp_clip_table;
+    te::DevBuf fa_tab;         // the tables of the filter discs of any radius (Disc::tab points into it); grown
+    te::DevBuf tile_in[2], tile_out[2];  // the device staging of in_slot / out_slot; grown
+  } cmem;
+  float* poly_rot = nullptr;  // (derived: lmem.poly)
   bool have_robot_slope = false, check_inclination = false;  // footprint/check_robot_inclination (:114)
-  unsigned* poly_stream = nullptr;        // offset tables of the two footprint polygons (device copy)
-  size_t poly_stream_cap = 0;             // in words
   std::vector<unsigned> poly_stream_host;  // stays alive until the asynchronous upload has been consumed
   te::Geo geo;
   te::ChainParams cp;
   te::FootprintParams fp;
   te::Layers L;
   size_t layer_elems = 0;
-  void* slab = nullptr;
-  uint32_t* d_spiral = nullptr;  // [kMaxSpiral]: the footprint spiral of reach <= 20, packed (fp_pack)
-  int* clip_table = nullptr;
-  int* fp_clip_table = nullptr;
-  // the circular footprint at any reach (te_footprint_any.hip): its tables and its prefix-sum scratch, allocated when the
-  // footprint tables are rebuilt for that route (never inside a launch: whole-map launches are captured into a hipGraph)
-  void* fpa_tab = nullptr;
-  size_t fpa_tab_bytes = 0;
-  void* fpa_prefix = nullptr;  // [batch][cols][rows + 1] doubles, then as many unsigned
-  size_t fpa_prefix_bytes = 0;
   // mask_done: the untraversable mask (L.untrav) is complete for the scores and the three parameters it reads (fp_max_gap,
   // fp_critical_step, fp_check_roughness).  Set by every footprint pass and by te_check_footprint_paths_radius, which builds
   // the mask on its own when it is not; cleared wherever footprint_done is cleared -- except that te_set_params keeps it
   // when nothing the mask reads changed -- and by an upload of a score layer (which leaves footprint_done as it was).
-  // te_check_footprint_paths_radius (te_path_discs.hip) -- pd_tables: the spiral tables of the radius classes on the device,
-  // by (radius, offset, resolution, map size), at most kPdTables of them, the least recently used one replaced; dropped
-  // with the layers.  pd_scratch: the call's staging buffers and memo, grown to the largest request so far.
   bool mask_done = false;
-  struct PdTable {
-    double radius = 0.0, offset = 0.0, res = 0.0;
-    int rows = 0, cols = 0;  // (the clip)
-    void* dev = nullptr;     // FpEntry [n_spiral]
-    int n_spiral = 0;
-    unsigned long long used = 0;  // pd_clock at its last use
-  };
-  static constexpr int kPdTables = 16;
-  PdTable pd_tables[kPdTables];
-  unsigned long long pd_clock = 0;
-  void* pd_scratch = nullptr;
-  size_t pd_scratch_bytes = 0;
+  unsigned long long pd_clock = 0;  // (lmem.pd_tables)
   bool combine_deferred = false;
   // the traversability layer was written from outside (upload, device pointer, a per-plugin combine of uploaded scores):
   // its values are then not bounded by the weights, and the fixed-point footprint kernel must not be used
@@ -106,16 +129,13 @@ struct te_ctx {
   int opt_fb_walk = 0, opt_fb_blocks_per_cu = 0, opt_polygon_per_cell = 0, opt_graph = 0, opt_bcast_rccl = 0, opt_rank_rule = 0,
       opt_fp_any = 0;
   // TE_OPT_FILTER_ANY_RADIUS (0: discs above 32 cells refused, 1: those take te_filter_any.hip, 2: every disc does), the host
-  // tables of the filter discs that route takes (normals, roughness, step windows 1 and 2) and their device copy, uploaded
-  // by rebuild_tables (never inside a launch: whole-map launches are captured)
+  // tables of the filter discs that route takes (normals, roughness, step windows 1 and 2) and their device copy (cmem.fa_tab),
+  // uploaded by rebuild_tables (never inside a launch: whole-map launches are captured)
   int opt_filter_any = 0;
   te::DiscTable fa_host[4];
-  void* fa_tab = nullptr;
-  size_t fa_tab_bytes = 0;
   // invalid cells of the elevation layer as of the last whole upload (-1: unknown -- tiles, device pointer): see sparse_holes()
   long long invalid_cells = -1;
   long long invalid_runs = -1;  // runs of invalid cells in memory order (k_count_invalid); meaningful with invalid_cells >= 0
-  unsigned long long* d_count = nullptr;
   // face flags (te_face_flags.h): built by the same pass over the whole elevation layer, for the fp_critical_step held then.
   // face_crit: that value; NaN: unknown -- whatever makes invalid_cells unknown (tiles, the
   // device pointer, a failed prefetch), or a te_set_params that changed fp_critical_step.  The bytes live in the slab.
@@ -125,8 +145,6 @@ struct te_ctx {
   // pass -- the flags are never passed again until the layers are allocated anew (te_set_geometry with another shape)
   bool elev_ptr_out = false;
   int opt_face_flags = 1;  // TE_OPT_FACE_FLAGS
-  char* hole_queue = nullptr;  // scratch of k_normals3's sparse-hole march (allocated when a launch first picks it)
-  float* tie_scratch = nullptr;  // one float per cell: the step filter at a tie radius (allocated when a launch first needs it, freed with the layers)
   bool tables_ready = false;
   // the circular-footprint tables are built separately: a footprint whose tables do not fit in device memory must not
   // stop the filter chain or the per-plugin entry points, which never use them (the reference has no such coupling)
@@ -140,9 +158,7 @@ struct te_ctx {
   int graph_next = 0;
   bool graph_ok = true;  // cleared after a failed capture: direct launches from then on
   // streaming tiles (te_upload_tile_async / te_download_tile_async): copy streams, two device staging slots each way
-  struct TileSlot {
-    float* buf = nullptr;
-    size_t cap = 0;                              // in floats
+  struct TileSlot {  // (its device buffer: cmem.tile_in / tile_out)
     hipEvent_t ready = nullptr, freed = nullptr;  // filled / consumed
     bool used = false;
   };
@@ -151,20 +167,6 @@ struct te_ctx {
   int in_next = 0, out_next = 0;
   bool tiles_pending = false;  // te_sync has copy streams to wait for
   te::HostStager stager;           // whole-layer transfers through pageable host buffers (te_stage.hip)
-  // te_upload_image: the raw image bytes on the device (te_image.hip converts and transposes them into a layer); grown to
-  // the largest image so far, freed with the layers
-  void* img_stage = nullptr;
-  size_t img_stage_bytes = 0;
-  // te_download_occupancy (te_occupancy.hip) / te_download_cloud (te_cloud.hip): the converted cells / the block counts, block
-  // offsets and compacted records on the device; grown to the largest request so far, freed with the layers
-  struct OutScratch {
-    void* p = nullptr;
-    size_t bytes = 0;
-  };
-  OutScratch occ_out, cloud_counts, cloud_out;
-  // te_run_expression (te_expr.hip): the per-block partials of its reductions and, behind them, the folded results per
-  // (map, reduction); grown to the largest request so far, freed with the layers
-  OutScratch expr_scratch;
   // bit TE_LAYER_* of the optional layers that hold values: surface_normal_* (a whole-map chain with TE_RUN_KEEP_NORMALS or
   // TE_FILTER_NORMALS sets them, a whole-map chain without the flag clears them like the DeletionFilter), the three memo layers
   // (a whole-map footprint pass with TE_RUN_FOOTPRINT_MEMO), and any layer an upload or te_device_ptr touched (ensure_input_layer).
@@ -213,24 +215,5 @@ int rebuild_tables(te_ctx* c);
 void rebuild_footprint_tables(te_ctx* c);
 int sync_tiles(te_ctx* c);  // waits for the copy streams of the streaming-tile calls
 int run_whole_locked(te_ctx* c, unsigned flags);
-void release_path_discs(te_ctx* c);  // te_paths_api.hip: the spiral tables and the scratch of te_check_footprint_paths_radius
-// an output scratch buffer of at least `bytes` (grown after the stream has drained; caller holds c->mu, device set)
-inline int grow_out_scratch(te_ctx* c, te_ctx::OutScratch& s, size_t bytes) {
-  if (s.bytes >= bytes) return TE_OK;
-  if (s.p) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    (void)hipFree(s.p);
-    s.p = nullptr;
-    s.bytes = 0;
-  }
-  HIP_TRY(hipMalloc(&s.p, bytes));
-  s.bytes = bytes;
-  return TE_OK;
-}
-inline void release_out_scratch(te_ctx::OutScratch& s) {
-  if (s.p) (void)hipFree(s.p);
-  s.p = nullptr;
-  s.bytes = 0;
-}
 }  // namespace shim
 }  // namespace te

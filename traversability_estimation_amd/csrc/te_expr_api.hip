@@ -41,8 +41,8 @@ int make_args(const char* who, te_ctx* c, const expr::Program& p, expr::Args& a)
 int launch_locked(te_ctx* c, const expr::Program& p, const expr::Args& a) {
   void* scratch = nullptr;
   if (p.n_red > 0) {
-    if (const int rc = grow_out_scratch(c, c->expr_scratch, expr::scratch_bytes(p, a.cells, (size_t)c->geo.batch))) return rc;
-    scratch = c->expr_scratch.p;
+    HIP_TRY(c->lmem.expr_scratch.reserve(expr::scratch_bytes(p, a.cells, (size_t)c->geo.batch), c->stream));
+    scratch = c->lmem.expr_scratch.p;
   }
   HIP_TRY(expr::launch(p, a, (size_t)c->geo.batch, scratch, c->stream));
   return TE_OK;

@@ -10,6 +10,7 @@
 
 #include "te_face_flags.h"
 #include "te_fp_route.h"
+#include "te_slab.h"
 #include "travgpu.h"
 
 namespace te {
@@ -45,8 +46,8 @@ bool trace_available();
 constexpr int kMaxRadiusCells = 32;  // largest stencil radius (in cells) a launch supports
 // The marching kernels of te_march5.h load the rows above / below a map unconditionally (and stage them as "nothing
 // there"): up to the stencil radius above the first row, and the radius plus the prefetch distance below the last.  The
-// context's slab therefore starts and ends with this many rows of slack (te_set_geometry).
-constexpr int kSlabGuardRows = kMaxRadiusCells + 16;
+// context's slab therefore starts and ends with this many rows of slack (kSlabGuardRows of te_slab.h, the plan of the slab).
+static_assert(kSlabGuardRows == kMaxRadiusCells + 16, "te_slab.h: the guard rows cover the largest radius and the prefetch distance");
 constexpr int kMaxTies = 32;         // offsets lying exactly on the circle (tie radii)
 constexpr int kMaxSpiral = 4096;     // ordered offsets of the footprint spiral
 
@@ -255,7 +256,7 @@ struct HostStager {
 };
 
 // The marching kernels of te_march5.h read kSlabGuardRows rows above and below the layers they are given (unconditional
-// raw buffer loads, no bounds check: DESIGN.md).  Layers of a context's slab have that slack by construction; any other
+// raw buffer loads, no bounds check: DESIGN.md).  Layers of a context's slab have that slack by its plan (te_slab.h); any other
 // pointer -- a caller's own allocation handed in through a future entry point -- is checked here against the allocation
 // that holds it, and the launchers fall back to the bounds-checked generic kernels when the slack is not there.
 // (One driver query per distinct (pointer, shape); the verdicts are dropped whenever a context frees its layers.)

@@ -211,14 +211,10 @@ __device__ __forceinline__ void accumulate_disc(Mom& m, const Geo& g, const Disc
   }
 }
 
-struct NormalsArgs {
-  Disc dn, dr;
-  int same_disc, axis;
-  double slope_crit, rough_crit;
-  float w_scale, w_slope, w_step, w_rough;
-  int combine;  // also write the traversability layer (reads the step layer)
-  int given_normals;  // RoughnessFilter alone: surface_normal_{x,y,z} are INPUT layers (RoughnessFilter.cpp:108-110)
-  int rank_rule;      // TE_OPT_NORMALS_RANK_RULE (te_cell.h: rank_deficient)
+// any::NormalsJob (te_internal.h: the discs, the rule of the rank -- TE_OPT_NORMALS_RANK_RULE, te_cell.h: rank_deficient --,
+// combine, given_normals -- RoughnessFilter.cpp:108-110 --, the criticals and the weights), which the route of any radius takes
+// as it is, and what only the kernels of this file read
+struct NormalsArgs : any::NormalsJob {
   float band_slope, band_rough;  // k_normals_fixup: a fast-tail score within this of its clip takes the generic arithmetic (te_internal.h)
 };
 
@@ -501,25 +497,6 @@ inline dim3 tile_grid(const Geo& g, const Region& r) {
 
 inline size_t tile_bytes(int K) { return (size_t)(TX + 2 * K) * (TY + 2 * K) * sizeof(float); }
 
-// a normals stage with a disc marked Disc::any: te_filter_any.hip, whatever the flags
-inline any::NormalsJob any_job(const NormalsArgs& na) {
-  any::NormalsJob j;
-  j.dn = na.dn;
-  j.dr = na.dr;
-  j.same_disc = na.same_disc;
-  j.axis = na.axis;
-  j.rank_rule = na.rank_rule;
-  j.combine = na.combine;
-  j.given_normals = na.given_normals;
-  j.slope_crit = na.slope_crit;
-  j.rough_crit = na.rough_crit;
-  j.w_scale = na.w_scale;
-  j.w_slope = na.w_slope;
-  j.w_step = na.w_step;
-  j.w_rough = na.w_rough;
-  return j;
-}
-
 }  // namespace
 
 int chain_max_reach(const ChainParams& p) {
@@ -571,7 +548,7 @@ hipError_t launch_filter(const Geo& g, const ChainParams& p, const Layers& L, in
     // tie-free discs: the sliding kernel with the layers' normals (interior, hole-free discs in closed form from the
     // moments), the fix-up pass for the frame and the holes; otherwise the generic kernel on every cell
     FastGrid fg;
-    if (p.rough.any) return any::normals(g, any_job(na), L, L.nx, L.ny, L.nz, r, stream);
+    if (p.rough.any) return any::normals(g, na, L, L.nx, L.ny, L.nz, r, stream);  // (a disc marked Disc::any: te_filter_any.hip, whatever the flags)
     if (use_fast && fast::roughness_given_fast(g, p, L, r, L.block_flags, &fg, stream))
       hipLaunchKernelGGL(k_normals_fixup, dim3((unsigned)fix_groups(fg.ntx * fg.nty * fg.nbz)), blk, tile_bytes(p.rough.reach), stream, g, na,
                          L.elev, L.step, L.slope, L.rough, L.trav, L.nx, L.ny, L.nz, L.block_flags, fg, r);
@@ -683,7 +660,7 @@ hipError_t launch_chain(const Geo& g, const ChainParams& p, const Layers& L, con
   TraceRange tr_normals("chain: normals + slope + roughness (+ fix-up)");
   if (any_normals) {
     combined = na.combine != 0;
-    const hipError_t e = any::normals(g, any_job(na), L, knx, kny, knz, rn, stream);
+    const hipError_t e = any::normals(g, na, L, knx, kny, knz, rn, stream);
     if (e != hipSuccess) return e;
   } else if (use_fast && p.same_rough_disc && p.axis == 2 &&
       fast::normals_fast(g, p, L, keep, fused_combine, rn, L.block_flags, L.clip_table, &fg, stream, &combined)) {

@@ -73,33 +73,33 @@ int te_bcast_params(te_ctx** ctxs, int n, int root) {
     if (!rccl.ok) return fail(TE_ERR_UNSUPPORTED, "te_bcast_params: %zu devices but librccl could not be loaded", devs.size());
     const int nd = (int)devs.size();
     std::vector<Rccl::comm_t> comms(nd, nullptr);
-    std::vector<void*> buf(nd, nullptr);
+    std::vector<DevBuf> buf(nd);  // (one per device: released below with its device current, before they go out of scope)
     // streams of this call's own: the contexts' streams belong to their mutexes, and this is configure-time
     std::vector<hipStream_t> st(nd, nullptr);
     int e = rccl.CommInitAll(comms.data(), nd, devs.data());
     if (e) return fail(TE_ERR_HIP, "te_bcast_params: ncclCommInitAll failed (%d)", e);
     bool bad = false;
     for (int d = 0; d < nd && !bad; ++d) {
-      bad = hipSetDevice(devs[d]) != hipSuccess || hipMalloc(&buf[d], sizeof(te_params)) != hipSuccess ||
+      bad = hipSetDevice(devs[d]) != hipSuccess || buf[d].once(sizeof(te_params)) != hipSuccess ||
             hipStreamCreateWithFlags(&st[d], hipStreamNonBlocking) != hipSuccess;
-      if (!bad && d == 0) bad = hipMemcpy(buf[0], &p, sizeof(te_params), hipMemcpyHostToDevice) != hipSuccess;
+      if (!bad && d == 0) bad = hipMemcpy(buf[0].p, &p, sizeof(te_params), hipMemcpyHostToDevice) != hipSuccess;
     }
     if (!bad) {
       rccl.GroupStart();
       for (int d = 0; d < nd; ++d) {  // rank 0 is the root's device; ncclChar == 0
         (void)hipSetDevice(devs[d]);
-        e = e ? e : rccl.Broadcast(buf[d], buf[d], sizeof(te_params), 0, 0, comms[d], st[d]);
+        e = e ? e : rccl.Broadcast(buf[d].p, buf[d].p, sizeof(te_params), 0, 0, comms[d], st[d]);
       }
       e = rccl.GroupEnd() || e;
       for (int d = 0; d < nd && !e; ++d) {
         (void)hipSetDevice(devs[d]);
         bad = bad || hipStreamSynchronize(st[d]) != hipSuccess ||
-              hipMemcpy(&got[d], buf[d], sizeof(te_params), hipMemcpyDeviceToHost) != hipSuccess;
+              hipMemcpy(&got[d], buf[d].p, sizeof(te_params), hipMemcpyDeviceToHost) != hipSuccess;
       }
     }
     for (int d = 0; d < nd; ++d) {
       (void)hipSetDevice(devs[d]);
-      if (buf[d]) (void)hipFree(buf[d]);
+      buf[d].release();
       if (st[d]) (void)hipStreamDestroy(st[d]);
       if (comms[d]) rccl.CommDestroy(comms[d]);
     }

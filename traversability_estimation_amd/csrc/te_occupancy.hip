@@ -92,9 +92,9 @@ int convert_locked(te_ctx* c, const Job& job, int n_layers, void* dst) {
   const size_t n = (size_t)c->geo.rows * c->geo.cols;
   HIP_TRY(hipSetDevice(c->device));
   const size_t bytes = n * (size_t)n_layers;
-  if (const int rc = grow_out_scratch(c, c->occ_out, (bytes + 3) & ~(size_t)3)) return rc;
-  HIP_TRY(launch(job, n_layers, n, (uint8_t*)c->occ_out.p, c->stream));
-  HIP_TRY(c->stager.download(dst, c->occ_out.p, bytes, c->stream));  // (returns when dst holds the cells)
+  HIP_TRY(c->lmem.occ_out.reserve((bytes + 3) & ~(size_t)3, c->stream));
+  HIP_TRY(launch(job, n_layers, n, c->lmem.occ_out.as<uint8_t>(), c->stream));
+  HIP_TRY(c->stager.download(dst, c->lmem.occ_out.p, bytes, c->stream));  // (returns when dst holds the cells)
   return TE_OK;
 }
 

@@ -8,25 +8,11 @@
 using namespace te;
 using namespace te::shim;
 
-namespace te {
-namespace shim {
-void release_path_discs(te_ctx* c) {
-  for (te_ctx::PdTable& t : c->pd_tables) {
-    if (t.dev) (void)hipFree(t.dev);
-    t = te_ctx::PdTable();
-  }
-  if (c->pd_scratch) (void)hipFree(c->pd_scratch);
-  c->pd_scratch = nullptr;
-  c->pd_scratch_bytes = 0;
-}
-}  // namespace shim
-}  // namespace te
-
 namespace {
 // The spiral table of circle(radius + offset) on the device, from the context's cache or built now (te_fp_table.h: the
 // table of the footprint pass at any reach).  A request with more classes than the cache holds keeps the rest in `temps`
 // for the call.  first_clock: pd_clock when the call began (entries used since then serve this call and stay).
-int path_disc_table(te_ctx* c, double radius, double offset, unsigned long long first_clock, std::vector<void*>& temps,
+int path_disc_table(te_ctx* c, double radius, double offset, unsigned long long first_clock, std::vector<DevBuf>& temps,
                     PathDiscClass* out) {
   const Geo& g = c->geo;
   out->rmin = radius;
@@ -34,42 +20,40 @@ int path_disc_table(te_ctx* c, double radius, double offset, unsigned long long 
   out->r2 = out->rmax * out->rmax;
   out->pad = 0;
   te_ctx::PdTable* victim = nullptr;
-  for (te_ctx::PdTable& t : c->pd_tables) {
-    if (t.dev && t.radius == radius && t.offset == offset && t.res == g.res && t.rows == g.rows && t.cols == g.cols) {
+  for (te_ctx::PdTable& t : c->lmem.pd_tables) {
+    if (t.dev.p && t.radius == radius && t.offset == offset && t.res == g.res && t.rows == g.rows && t.cols == g.cols) {
       t.used = ++c->pd_clock;
-      out->spiral = (const int4*)t.dev;
+      out->spiral = t.dev.as<const int4>();
       out->n_spiral = t.n_spiral;
       return TE_OK;
     }
-    if ((!t.dev || t.used <= first_clock) && (!victim || (victim->dev && (!t.dev || t.used < victim->used)))) victim = &t;
+    if ((!t.dev.p || t.used <= first_clock) && (!victim || (victim->dev.p && (!t.dev.p || t.used < victim->used)))) victim = &t;
   }
   FpTable tab;
   build_fp_table(out->rmax, g.res, g.rows, g.cols, &tab);
   const size_t bytes = tab.spiral.size() * sizeof(FpEntry);
   if (tab.spiral.size() > (size_t)0x7fffffff) return fail(TE_ERR_UNSUPPORTED, "te_check_footprint_paths_radius: a spiral of %zu entries", tab.spiral.size());
-  void* dev = nullptr;
-  hipError_t e = hipMalloc(&dev, bytes);
-  if (e == hipSuccess) e = hipMemcpyAsync(dev, tab.spiral.data(), bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (tab goes out of scope)
+  DevBuf dev;
+  hipError_t e = dev.once(bytes);
+  if (e == hipSuccess) e = hipMemcpyAsync(dev.p, tab.spiral.data(), bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (tab goes out of scope; and the stream has drained before a victim's table is freed)
   if (e != hipSuccess) {
-    if (dev) (void)hipFree(dev);
     (void)hipGetLastError();
     return fail(TE_ERR_HIP, "te_check_footprint_paths_radius: the spiral table of radius %g m (%zu bytes): %s", radius, bytes, hipGetErrorString(e));
   }
-  out->spiral = (const int4*)dev;
+  out->spiral = dev.as<const int4>();
   out->n_spiral = (int)tab.spiral.size();
   if (victim) {
-    if (victim->dev) (void)hipFree(victim->dev);  // (no launch is in flight: every call ends with a stream synchronize)
     victim->radius = radius;
     victim->offset = offset;
     victim->res = g.res;
     victim->rows = g.rows;
     victim->cols = g.cols;
-    victim->dev = dev;
+    victim->dev = std::move(dev);
     victim->n_spiral = out->n_spiral;
     victim->used = ++c->pd_clock;
   } else {
-    temps.push_back(dev);
+    temps.push_back(std::move(dev));
   }
   return TE_OK;
 }
@@ -116,62 +100,47 @@ int te_check_footprint_paths_radius(te_ctx* c, int map, int n_paths, const int* 
   HIP_TRY(hipSetDevice(c->device));
   const unsigned long long first_clock = c->pd_clock;
   std::vector<PathDiscClass> classes(uniq.size());
-  std::vector<void*> temps;
-  auto drop_temps = [&]() {
-    for (void* t : temps) (void)hipFree(t);
-  };
+  std::vector<DevBuf> temps;  // the tables of this call alone: freed when it returns, behind its stream synchronize
   for (size_t q = 0; q < uniq.size(); ++q)
-    if (const int rc = path_disc_table(c, uniq[q], offset, first_clock, temps, &classes[q])) {
-      drop_temps();
-      return rc;
-    }
+    if (const int rc = path_disc_table(c, uniq[q], offset, first_clock, temps, &classes[q])) return rc;
   // one scratch buffer: the staged request and its results, the class array, the memo (keys, values, work list, counters)
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t list_cap = n_visits > 0 ? (size_t)n_visits : 1;
-  const size_t b_off = (size_t)(n_paths + 1) * sizeof(int), b_xy = (size_t)2 * (n_poses > 0 ? n_poses : 1) * sizeof(double);
-  const size_t b_cls = (size_t)n_paths * sizeof(int), b_trav = (size_t)n_paths * sizeof(double), b_st = (size_t)n_paths * sizeof(int);
-  const size_t b_safe = (size_t)n_paths, b_classes = classes.size() * sizeof(PathDiscClass);
-  const size_t b_keys = (size_t)entries * sizeof(uint64_t), b_vals = (size_t)entries * sizeof(float), b_list = list_cap * sizeof(unsigned);
-  const size_t b_cnt = kPdCounters * sizeof(unsigned);
-  const size_t sizes[11] = {b_keys, b_xy, b_trav, b_classes, b_off, b_cls, b_st, b_vals, b_list, b_cnt, b_safe};
-  size_t at[12];
-  at[0] = 0;
-  for (int k = 0; k < 11; ++k) at[k + 1] = at[k] + up(sizes[k]);
-  if (at[11] > c->pd_scratch_bytes) {
-    if (c->pd_scratch) (void)hipFree(c->pd_scratch);
-    c->pd_scratch = nullptr;
-    c->pd_scratch_bytes = 0;
-    const hipError_t e = hipMalloc(&c->pd_scratch, at[11]);
-    if (e != hipSuccess) {
-      c->pd_scratch = nullptr;
-      (void)hipGetLastError();
-      drop_temps();
-      return fail(TE_ERR_HIP, "te_check_footprint_paths_radius: hipMalloc(%zu bytes) for %llu centres: %s", at[11], n_visits, hipGetErrorString(e));
-    }
-    c->pd_scratch_bytes = at[11];
-  }
-  char* d = (char*)c->pd_scratch;
+  Carve cv;
+  const auto p_keys = cv.add<uint64_t>((size_t)entries);
+  const auto p_xy = cv.add<double>((size_t)2 * (n_poses > 0 ? n_poses : 1));
+  const auto p_trav = cv.add<double>(n_paths);
+  const auto p_classes = cv.add<PathDiscClass>(classes.size());
+  const auto p_off = cv.add<int>((size_t)n_paths + 1);
+  const auto p_cls = cv.add<int>(n_paths);
+  const auto p_st = cv.add<int>(n_paths);
+  const auto p_vals = cv.add<float>((size_t)entries);
+  const auto p_list = cv.add<unsigned>(list_cap);
+  const auto p_cnt = cv.add<unsigned>(kPdCounters);
+  const auto p_safe = cv.add<unsigned char>(n_paths);
+  DevBuf& scratch = c->lmem.pd_scratch;
+  if (const hipError_t e = scratch.reserve(cv.total, c->stream))
+    return fail(TE_ERR_HIP, "te_check_footprint_paths_radius: hipMalloc(%zu bytes) for %llu centres: %s", cv.total, n_visits, hipGetErrorString(e));
   PathDiscScratch s;
-  s.keys = (uint64_t*)(d + at[0]);
-  double* d_xy = (double*)(d + at[1]);
-  double* d_trav = (double*)(d + at[2]);
-  PathDiscClass* d_classes = (PathDiscClass*)(d + at[3]);
-  int* d_off = (int*)(d + at[4]);
-  int* d_cls = (int*)(d + at[5]);
-  int* d_st = (int*)(d + at[6]);
-  s.vals = (float*)(d + at[7]);
-  s.list = (unsigned*)(d + at[8]);
-  s.counters = (unsigned*)(d + at[9]);
-  unsigned char* d_safe = (unsigned char*)(d + at[10]);
+  s.keys = p_keys.in(scratch);
+  double* d_xy = p_xy.in(scratch);
+  double* d_trav = p_trav.in(scratch);
+  PathDiscClass* d_classes = p_classes.in(scratch);
+  int* d_off = p_off.in(scratch);
+  int* d_cls = p_cls.in(scratch);
+  int* d_st = p_st.in(scratch);
+  s.vals = p_vals.in(scratch);
+  s.list = p_list.in(scratch);
+  s.counters = p_cnt.in(scratch);
+  unsigned char* d_safe = p_safe.in(scratch);
   s.mask = entries - 1;
   s.list_cap = (unsigned)list_cap;
   unsigned counters[kPdCounters] = {0, 0, 0, 0};
-  hipError_t e = hipMemcpyAsync(d_off, pose_offset, b_off, hipMemcpyHostToDevice, c->stream);
+  hipError_t e = hipMemcpyAsync(d_off, pose_offset, p_off.bytes(), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess && n_poses > 0) e = hipMemcpyAsync(d_xy, pose_xy, (size_t)2 * n_poses * sizeof(double), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_cls, cls.data(), b_cls, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_classes, classes.data(), b_classes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(s.keys, 0xFF, b_keys, c->stream);  // pv::kEmptyKey
-  if (e == hipSuccess) e = hipMemsetAsync(s.counters, 0, b_cnt, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_cls, cls.data(), p_cls.bytes(), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_classes, classes.data(), p_classes.bytes(), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(s.keys, 0xFF, p_keys.bytes(), c->stream);  // pv::kEmptyKey
+  if (e == hipSuccess) e = hipMemsetAsync(s.counters, 0, p_cnt.bytes(), c->stream);
   // the untraversable mask: built on the first call after the scores (or one of the three parameters it reads) changed
   if (e == hipSuccess && !c->mask_done) {
     e = launch_footprint_mask(g, c->fp, c->L, usable_face_flags(c), c->combine_deferred ? &c->cp : nullptr, c->stream);
@@ -183,15 +152,14 @@ int te_check_footprint_paths_radius(te_ctx* c, int map, int n_paths, const int* 
   const size_t per = (size_t)g.rows * g.cols;
   if (e == hipSuccess)
     e = launch_path_discs(g, s, d_classes, c->L.trav + per * map, c->L.untrav + per * map, c->params.fp_default,
-                          c->check_inclination ? c->robot_slope + per * map : nullptr, n_paths, d_off, d_xy, d_cls, d_safe, d_trav, d_st,
+                          c->check_inclination ? c->lmem.robot_slope.as<float>() + per * map : nullptr, n_paths, d_off, d_xy, d_cls, d_safe, d_trav, d_st,
                           c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(is_safe, d_safe, b_safe, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(traversability, d_trav, b_trav, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(status, d_st, b_st, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(counters, s.counters, b_cnt, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(is_safe, d_safe, p_safe.bytes(), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(traversability, d_trav, p_trav.bytes(), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(status, d_st, p_st.bytes(), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(counters, s.counters, p_cnt.bytes(), hipMemcpyDeviceToHost, c->stream);
   const hipError_t e_sync = hipStreamSynchronize(c->stream);  // (also before the tables of this call alone are freed)
   if (e == hipSuccess) e = e_sync;
-  drop_temps();
   if (e != hipSuccess) {
     (void)hipGetLastError();
     return fail(TE_ERR_HIP, "te_check_footprint_paths_radius: %s", hipGetErrorString(e));
@@ -226,28 +194,30 @@ int te_check_footprint_paths(te_ctx* c, int map, int n_paths, const int* pose_of
     if (pose_offset[k + 1] < pose_offset[k]) return fail(TE_ERR_INVALID_ARG, "te_check_footprint_paths: bad pose offsets");
   HIP_TRY(hipSetDevice(c->device));
   // staging buffers for this call (paths are small: a few KB .. MB)
-  const size_t b_off = (size_t)(n_paths + 1) * sizeof(int), b_xy = (size_t)2 * (n_poses > 0 ? n_poses : 1) * sizeof(double);
-  const size_t b_safe = (size_t)n_paths, b_trav = (size_t)n_paths * sizeof(double), b_st = (size_t)n_paths * sizeof(int);
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  char* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, up(b_off) + up(b_xy) + up(b_trav) + up(b_st) + up(b_safe)));
-  int* d_off = (int*)d;
-  double* d_xy = (double*)(d + up(b_off));
-  double* d_trav = (double*)(d + up(b_off) + up(b_xy));
-  int* d_st = (int*)(d + up(b_off) + up(b_xy) + up(b_trav));
-  unsigned char* d_safe = (unsigned char*)(d + up(b_off) + up(b_xy) + up(b_trav) + up(b_st));
-  hipError_t e = hipMemcpyAsync(d_off, pose_offset, b_off, hipMemcpyHostToDevice, c->stream);
+  Carve cv;
+  const auto p_off = cv.add<int>((size_t)n_paths + 1);
+  const auto p_xy = cv.add<double>((size_t)2 * (n_poses > 0 ? n_poses : 1));
+  const auto p_trav = cv.add<double>(n_paths);
+  const auto p_st = cv.add<int>(n_paths);
+  const auto p_safe = cv.add<unsigned char>(n_paths);
+  DevBuf tmp;
+  HIP_TRY(tmp.once(cv.total));
+  int* d_off = p_off.in(tmp);
+  double* d_xy = p_xy.in(tmp);
+  double* d_trav = p_trav.in(tmp);
+  int* d_st = p_st.in(tmp);
+  unsigned char* d_safe = p_safe.in(tmp);
+  hipError_t e = hipMemcpyAsync(d_off, pose_offset, p_off.bytes(), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess && n_poses > 0) e = hipMemcpyAsync(d_xy, pose_xy, (size_t)2 * n_poses * sizeof(double), hipMemcpyHostToDevice, c->stream);
   const size_t per = (size_t)c->geo.rows * c->geo.cols;
   if (e == hipSuccess)
     e = launch_check_circular_paths(c->geo, c->L.footprint + per * map, c->params.fp_default,
-                                    c->check_inclination ? c->robot_slope + per * map : nullptr, n_paths, d_off, d_xy, d_safe,
+                                    c->check_inclination ? c->lmem.robot_slope.as<float>() + per * map : nullptr, n_paths, d_off, d_xy, d_safe,
                                     d_trav, d_st, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(is_safe, d_safe, b_safe, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(traversability, d_trav, b_trav, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(status, d_st, b_st, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(is_safe, d_safe, p_safe.bytes(), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(traversability, d_trav, p_trav.bytes(), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(status, d_st, p_st.bytes(), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
   if (e != hipSuccess) return fail(TE_ERR_HIP, "te_check_footprint_paths: %s", hipGetErrorString(e));
   return TE_OK;
 }
@@ -267,20 +237,19 @@ int check_inclination_locked(te_ctx* c, int map, int n, const double* start_end_
   if (map < 0 || map >= c->geo.batch) return fail(TE_ERR_INVALID_ARG, "%s: map %d of %d", who, map, c->geo.batch);
   if (n == 0) return TE_OK;
   HIP_TRY(hipSetDevice(c->device));
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t b_seg = (size_t)4 * n * sizeof(double), b_ok = (size_t)n, b_st = (size_t)n * sizeof(int);
-  char* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, up(b_seg) + up(b_st) + up(b_ok)));
-  double* d_seg = (double*)d;
-  int* d_st = (int*)(d + up(b_seg));
-  unsigned char* d_ok = (unsigned char*)(d + up(b_seg) + up(b_st));
+  Carve cv;
+  const auto p_seg = cv.add<double>((size_t)4 * n);
+  const auto p_st = cv.add<int>(n);
+  const auto p_ok = cv.add<unsigned char>(n);
+  DevBuf tmp;
+  HIP_TRY(tmp.once(cv.total));
   const size_t per = (size_t)c->geo.rows * c->geo.cols;
-  hipError_t e = hipMemcpyAsync(d_seg, start_end_xy, b_seg, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = launch_check_inclination(c->geo, c->robot_slope + per * map, n, d_seg, d_ok, d_st, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(ok, d_ok, b_ok, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(status, d_st, b_st, hipMemcpyDeviceToHost, c->stream);
+  hipError_t e = hipMemcpyAsync(p_seg.in(tmp), start_end_xy, p_seg.bytes(), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess)
+    e = launch_check_inclination(c->geo, c->lmem.robot_slope.as<float>() + per * map, n, p_seg.in(tmp), p_ok.in(tmp), p_st.in(tmp), c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(ok, p_ok.in(tmp), p_ok.bytes(), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(status, p_st.in(tmp), p_st.bytes(), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
   if (e != hipSuccess) return fail(TE_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
   return TE_OK;
 }
@@ -305,14 +274,13 @@ int te_run_polygon_footprint(te_ctx* c, int n_points, const double* points_xy, d
     return fail(TE_ERR_NOT_READY, "te_run_polygon_footprint: run the chain with the footprint pass first (it marks the untraversable cells)");
   if (c->geo.cols > 65535) return fail(TE_ERR_UNSUPPORTED, "te_run_polygon_footprint: more than 65535 columns");
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->poly_x) {
-    const size_t lb = (c->layer_elems * sizeof(float) + 255) & ~(size_t)255;
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, 2 * lb);
-    if (e != hipSuccess) return fail(TE_ERR_HIP, "te_run_polygon_footprint: hipMalloc(%zu bytes): %s", 2 * lb, hipGetErrorString(e));
-    c->poly_x = (float*)p;
-    c->poly_rot = (float*)((char*)p + lb);
-  }
+  Carve poly;
+  poly.add<float>(c->layer_elems);
+  const auto p_rot = poly.add<float>(c->layer_elems);
+  if (const hipError_t e = c->lmem.poly.once(poly.total))
+    return fail(TE_ERR_HIP, "te_run_polygon_footprint: hipMalloc(%zu bytes): %s", poly.total, hipGetErrorString(e));
+  float* const poly_x = c->lmem.poly.as<float>();
+  c->poly_rot = p_rot.in(c->lmem.poly);
   PolygonArgs a;
   memset(&a, 0, sizeof(a));
   a.n = n_points;
@@ -327,22 +295,17 @@ int te_run_polygon_footprint(te_ctx* c, int n_points, const double* points_xy, d
   bool table = !c->opt_polygon_per_cell;
   for (int w = 0; w < 2 && table; ++w) table = build_polygon_table(c->geo, n_points, a.off[w], c->poly_stream_host, tabs.t[w]);
   if (!table) {
-    HIP_TRY(launch_polygon_footprint(c->geo, a, c->L.trav, c->L.untrav, c->poly_x, c->poly_rot, c->stream));
+    HIP_TRY(launch_polygon_footprint(c->geo, a, c->L.trav, c->L.untrav, poly_x, c->poly_rot, c->stream));
     return TE_OK;
   }
   if (c->poly_stream_host.empty()) c->poly_stream_host.push_back(0);
-  if (c->poly_stream_host.size() > c->poly_stream_cap) {
-    if (c->poly_stream) (void)hipFree(c->poly_stream);
-    c->poly_stream = nullptr;
-    c->poly_stream_cap = 0;
-    const size_t cap = c->poly_stream_host.size() + 1024;
-    hipError_t e = hipMalloc((void**)&c->poly_stream, cap * sizeof(unsigned));
-    if (e != hipSuccess) return fail(TE_ERR_HIP, "te_run_polygon_footprint: hipMalloc: %s", hipGetErrorString(e));
-    c->poly_stream_cap = cap;
-  }
-  HIP_TRY(hipMemcpyAsync(c->poly_stream, c->poly_stream_host.data(), c->poly_stream_host.size() * sizeof(unsigned),
-                         hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(launch_polygon_footprint_table(c->geo, a, tabs, c->poly_stream, c->L.trav, c->L.untrav, c->poly_x, c->poly_rot,
+  DevBuf& stream_tab = c->lmem.poly_stream;  // (grown with room to spare: the tables' size moves with the yaw)
+  const size_t words = c->poly_stream_host.size();
+  if (stream_tab.bytes < words * sizeof(unsigned))
+    if (const hipError_t e = stream_tab.reserve((words + 1024) * sizeof(unsigned), c->stream))
+      return fail(TE_ERR_HIP, "te_run_polygon_footprint: hipMalloc: %s", hipGetErrorString(e));
+  HIP_TRY(hipMemcpyAsync(stream_tab.p, c->poly_stream_host.data(), words * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(launch_polygon_footprint_table(c->geo, a, tabs, stream_tab.as<unsigned>(), c->L.trav, c->L.untrav, poly_x, c->poly_rot,
                                          c->stream));
   return TE_OK;
 }
@@ -354,25 +317,26 @@ int polygons_traversable_locked(te_ctx* c, int map, int n_polygons, const int* v
   if (n_polygons == 0) return TE_OK;
   const int n_vert = vertex_offset[n_polygons];
   HIP_TRY(hipSetDevice(c->device));
-  const size_t b_off = (size_t)(n_polygons + 1) * sizeof(int), b_xy = (size_t)2 * n_vert * sizeof(double);
-  const size_t b_ok = (size_t)n_polygons, b_trav = (size_t)n_polygons * sizeof(double);
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  char* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, up(b_off) + up(b_xy) + up(b_trav) + up(b_ok)));
-  int* d_off = (int*)d;
-  double* d_xy = (double*)(d + up(b_off));
-  double* d_trav = (double*)(d + up(b_off) + up(b_xy));
-  unsigned char* d_ok = (unsigned char*)(d + up(b_off) + up(b_xy) + up(b_trav));
+  Carve cv;
+  const auto p_off = cv.add<int>((size_t)n_polygons + 1);
+  const auto p_xy = cv.add<double>((size_t)2 * n_vert);
+  const auto p_trav = cv.add<double>(n_polygons);
+  const auto p_ok = cv.add<unsigned char>(n_polygons);
+  DevBuf tmp;
+  HIP_TRY(tmp.once(cv.total));
+  int* d_off = p_off.in(tmp);
+  double* d_xy = p_xy.in(tmp);
+  double* d_trav = p_trav.in(tmp);
+  unsigned char* d_ok = p_ok.in(tmp);
   const size_t per = (size_t)c->geo.rows * c->geo.cols;
-  hipError_t e = hipMemcpyAsync(d_off, vertex_offset, b_off, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_xy, vertex_xy, b_xy, hipMemcpyHostToDevice, c->stream);
+  hipError_t e = hipMemcpyAsync(d_off, vertex_offset, p_off.bytes(), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_xy, vertex_xy, p_xy.bytes(), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess)
     e = launch_polygons_traversable(c->geo, c->params.fp_default, n_polygons, d_off, d_xy, c->L.trav + per * map,
                                     c->L.untrav + per * map, d_ok, d_trav, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(is_traversable, d_ok, b_ok, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(traversability, d_trav, b_trav, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(is_traversable, d_ok, p_ok.bytes(), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(traversability, d_trav, p_trav.bytes(), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
   if (e != hipSuccess) return fail(TE_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
   return TE_OK;
 }
@@ -415,19 +379,17 @@ int te_polygon_untraversable_hull(te_ctx* c, int map, int n_vertices, const doub
   if (rc != TE_OK || *is_traversable) return rc;  // :635-636 traversable: the empty polygon
   // untraversable: the rows of the bounding box that hold untraversable cells, then the hull on the host
   HIP_TRY(hipSetDevice(c->device));
-  const size_t b_xy = (size_t)2 * n_vertices * sizeof(double), b_rows = (size_t)5 * c->geo.rows * sizeof(double);
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  char* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, up(b_xy) + b_rows));
-  double* d_xy = (double*)d;
-  double* d_rows = (double*)(d + up(b_xy));
+  Carve cv;
+  const auto p_xy = cv.add<double>((size_t)2 * n_vertices);
+  const auto p_rows = cv.add<double>((size_t)5 * c->geo.rows);
+  DevBuf tmp;
+  HIP_TRY(tmp.once(cv.total));
   std::vector<double> rows5((size_t)5 * c->geo.rows);
   const size_t per = (size_t)c->geo.rows * c->geo.cols;
-  hipError_t e = hipMemcpyAsync(d_xy, vertex_xy, b_xy, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = launch_polygon_untraversable_rows(c->geo, n_vertices, d_xy, c->L.untrav + per * map, d_rows, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(rows5.data(), d_rows, b_rows, hipMemcpyDeviceToHost, c->stream);
+  hipError_t e = hipMemcpyAsync(p_xy.in(tmp), vertex_xy, p_xy.bytes(), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = launch_polygon_untraversable_rows(c->geo, n_vertices, p_xy.in(tmp), c->L.untrav + per * map, p_rows.in(tmp), c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(rows5.data(), p_rows.in(tmp), p_rows.bytes(), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
   if (e != hipSuccess) return fail(TE_ERR_HIP, "te_polygon_untraversable_hull: %s", hipGetErrorString(e));
   std::vector<double> hull;
   untraversable_hull_from_rows(c->geo.rows, rows5.data(), hull);

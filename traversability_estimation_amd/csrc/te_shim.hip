@@ -124,21 +124,12 @@ int upload_any_discs(te_ctx* c) {
   if (ints.empty()) return TE_OK;
   const size_t bytes = ints.size() * sizeof(int32_t);
   HIP_TRY(hipSetDevice(c->device));
-  if (bytes > c->fa_tab_bytes) {
-    if (c->fa_tab) (void)hipFree(c->fa_tab);
-    c->fa_tab = nullptr;
-    c->fa_tab_bytes = 0;
-    if (hipMalloc(&c->fa_tab, bytes) != hipSuccess) {
-      c->fa_tab = nullptr;
-      (void)hipGetLastError();
-      return fail(TE_ERR_UNSUPPORTED, "filter discs of any radius: their tables (%zu bytes) do not fit in device memory", bytes);
-    }
-    c->fa_tab_bytes = bytes;
-  }
-  HIP_TRY(hipMemcpyAsync(c->fa_tab, ints.data(), bytes, hipMemcpyHostToDevice, c->stream));
+  if (c->cmem.fa_tab.reserve(bytes, c->stream) != hipSuccess)
+    return fail(TE_ERR_UNSUPPORTED, "filter discs of any radius: their tables (%zu bytes) do not fit in device memory", bytes);
+  HIP_TRY(hipMemcpyAsync(c->cmem.fa_tab.p, ints.data(), bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int k = 0; k < 4; ++k)
-    if (ds[k]->any) ds[k]->tab = (const int*)c->fa_tab + off[k];
+  for (int k = 0; k < 4; ++k)  // (every Disc::tab is derived again: the buffer may have moved)
+    if (ds[k]->any) ds[k]->tab = c->cmem.fa_tab.as<const int>() + off[k];
   return TE_OK;
 }
 
@@ -314,16 +305,17 @@ namespace shim {
 int count_invalid_elevation(te_ctx* c) {
   c->invalid_cells = -1;
   c->face_crit = __builtin_nan("");
-  if (!c->d_count) HIP_TRY(hipMalloc((void**)&c->d_count, 2 * sizeof(unsigned long long)));
-  HIP_TRY(hipMemsetAsync(c->d_count, 0, 2 * sizeof(unsigned long long), c->stream));
+  HIP_TRY(c->cmem.count.once(2 * sizeof(unsigned long long)));
+  unsigned long long* const d_count = c->cmem.count.as<unsigned long long>();
+  HIP_TRY(hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned long long), c->stream));
   const bool with_flags = c->face_flags != nullptr;
   const double crit = c->params.fp_critical_step;
   const dim3 grid((unsigned)((face_flag_ntx(c->geo.rows) + kCfWaves - 1) / kCfWaves), (unsigned)((c->geo.cols + kCfY - 1) / kCfY), (unsigned)c->geo.batch);
   if (grid.y > 65535u || grid.z > 65535u) return fail(TE_ERR_UNSUPPORTED, "elevation layer of %d columns x %d maps: too many for one pass", c->geo.cols, c->geo.batch);
-  hipLaunchKernelGGL(k_count_invalid, grid, dim3(64 * kCfWaves), 0, c->stream, c->L.elev, c->geo.rows, c->geo.cols, crit, c->face_flags, c->d_count);
+  hipLaunchKernelGGL(k_count_invalid, grid, dim3(64 * kCfWaves), 0, c->stream, c->L.elev, c->geo.rows, c->geo.cols, crit, c->face_flags, d_count);
   HIP_TRY(hipGetLastError());
   unsigned long long h[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(h, c->d_count, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(h, d_count, sizeof(h), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->invalid_cells = (long long)h[0];
   c->invalid_runs = (long long)h[1];
@@ -366,28 +358,29 @@ bool short_strips(const te_ctx* c) {
 
 // the sparse march's queues; false (and the dense kernel) if the allocation fails
 bool ensure_hole_queue(te_ctx* c) {
-  if (c->hole_queue) return true;
-  if (hipSetDevice(c->device) != hipSuccess) return false;
-  void* p = nullptr;
-  if (hipMalloc(&p, fast::normals_hole_queue_bytes()) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  c->hole_queue = (char*)p;
-  return true;
+  if (c->cmem.hole_queue.p) return true;
+  return hipSetDevice(c->device) == hipSuccess && c->cmem.hole_queue.once(fast::normals_hole_queue_bytes()) == hipSuccess;
 }
 
 // the step filter's scratch layer at a tie radius (te_fast_step.hip); without it the generic kernels serve
 void ensure_tie_scratch(te_ctx* c) {
-  if (c->tie_scratch || !c->tables_ready || c->layer_elems == 0) return;
+  if (c->lmem.tie_scratch.p || !c->tables_ready || c->layer_elems == 0) return;
   if ((c->cp.step1.n_ties == 0 || c->cp.step1.any) && (c->cp.step2.n_ties == 0 || c->cp.step2.any)) return;
-  if (hipSetDevice(c->device) != hipSuccess) return;
-  void* p = nullptr;
-  if (hipMalloc(&p, c->layer_elems * sizeof(float)) != hipSuccess) {
-    (void)hipGetLastError();
-    return;
-  }
-  c->tie_scratch = (float*)p;
+  if (hipSetDevice(c->device) == hipSuccess) (void)c->lmem.tie_scratch.once(c->layer_elems * sizeof(float));
+}
+
+// What a launch of the filters takes from the context beside its parameters: the hints the normals kernel takes from the
+// upload's count, TE_OPT_NORMALS_RANK_RULE, and the two scratch buffers with the pointers derived from them (allocated on
+// first need, outside any capture; a failed allocation leaves the pointer null and the kernels that need none serve)
+void set_launch_hints(te_ctx* c) {
+  c->L.sparse_holes = sparse_holes(c) && ensure_hole_queue(c) ? 1 : 0;
+  c->L.no_holes = c->invalid_cells == 0 ? 1 : 0;
+  c->L.skip_clean = c->L.sparse_holes && skip_clean_march(c) ? 1 : 0;
+  c->L.short_strips = short_strips(c) ? 1 : 0;
+  c->L.hole_queue = c->cmem.hole_queue.as<char>();
+  ensure_tie_scratch(c);
+  c->L.tie_scratch = c->lmem.tie_scratch.as<float>();
+  c->cp.rank_rule = c->opt_rank_rule;
 }
 
 // TE_OPT_NORMALS_RANK_RULE decides on the rank of an exactly planar disc; on a normals disc above 32 cells the moment form's
@@ -406,31 +399,23 @@ void drop_graph(te_ctx* c) {
   }
 }
 
-void release_fp_any(te_ctx* c) {
-  if (c->fpa_tab) (void)hipFree(c->fpa_tab);
-  if (c->fpa_prefix) (void)hipFree(c->fpa_prefix);
-  c->fpa_tab = c->fpa_prefix = nullptr;
-  c->fpa_tab_bytes = c->fpa_prefix_bytes = 0;
+// the pointers into the buffers of the route of any reach (lmem.fpa): cleared wherever those are released
+void clear_fp_any_ptrs(te_ctx* c) {
   c->fp.any_spiral = nullptr;
   c->fp.any_ints = nullptr;
   c->fp.any_psum = nullptr;
   c->fp.any_pcnt = nullptr;
 }
+void release_fp_any(te_ctx* c) {
+  c->lmem.fpa = te_ctx::LayerMem::FpAny();
+  clear_fp_any_ptrs(c);
+}
 
 // (device memory for the route of any reach: the only way its tables can fail)
-static int fp_any_alloc(te_ctx* c, void** buf, size_t* have, size_t bytes, const char* what) {
-  if (*buf && *have >= bytes) return TE_OK;
-  if (*buf) (void)hipFree(*buf);
-  *buf = nullptr;
-  *have = 0;
-  if (hipMalloc(buf, bytes) != hipSuccess) {
-    *buf = nullptr;
-    (void)hipGetLastError();
-    return fail(TE_ERR_UNSUPPORTED, "footprint radius %.3g m is %d cells: its %s (%zu bytes) do not fit in device memory", c->fp.rmax,
-                c->fp.reach, what, bytes);
-  }
-  *have = bytes;
-  return TE_OK;
+static int fp_any_alloc(te_ctx* c, DevBuf& buf, size_t bytes, const char* what) {
+  if (buf.reserve(bytes, c->stream) == hipSuccess) return TE_OK;
+  return fail(TE_ERR_UNSUPPORTED, "footprint radius %.3g m is %d cells: its %s (%zu bytes) do not fit in device memory", c->fp.rmax,
+              c->fp.reach, what, bytes);
 }
 
 // The tables of the route of any reach (te_footprint_any.hip) on the device: run half-widths, those of the inner disc (the
@@ -468,16 +453,19 @@ int build_fp_any_tables(te_ctx* c, const FpTable& t) {
   const size_t ib = ints.size() * sizeof(int32_t), sb = t.spiral.size() * sizeof(FpEntry);
   HIP_TRY(hipSetDevice(c->device));
   int rc;
-  if ((rc = fp_any_alloc(c, &c->fpa_tab, &c->fpa_tab_bytes, ib + sb, "tables"))) return rc;
+  clear_fp_any_ptrs(c);  // (a failure leaves no pointer into a buffer that was freed on the way)
+  DevBuf& tab = c->lmem.fpa.tab;
+  DevBuf& prefix = c->lmem.fpa.prefix;
+  if ((rc = fp_any_alloc(c, tab, ib + sb, "tables"))) return rc;
   const size_t cells = (size_t)g.batch * g.cols * (size_t)(g.rows + 1);
-  if ((rc = fp_any_alloc(c, &c->fpa_prefix, &c->fpa_prefix_bytes, cells * (sizeof(double) + sizeof(unsigned)), "prefix sums"))) return rc;
-  HIP_TRY(hipMemcpyAsync(c->fpa_tab, ints.data(), ib, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync((char*)c->fpa_tab + ib, t.spiral.data(), sb, hipMemcpyHostToDevice, c->stream));
+  if ((rc = fp_any_alloc(c, prefix, cells * (sizeof(double) + sizeof(unsigned)), "prefix sums"))) return rc;
+  HIP_TRY(hipMemcpyAsync(tab.p, ints.data(), ib, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(tab.as<char>() + ib, t.spiral.data(), sb, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  f.any_ints = (const int*)c->fpa_tab;
-  f.any_spiral = (const int*)((const char*)c->fpa_tab + ib);
-  f.any_psum = (double*)c->fpa_prefix;
-  f.any_pcnt = (unsigned*)((char*)c->fpa_prefix + cells * sizeof(double));
+  f.any_ints = tab.as<const int>();
+  f.any_spiral = (const int*)(tab.as<const char>() + ib);
+  f.any_psum = prefix.as<double>();
+  f.any_pcnt = (unsigned*)(prefix.as<char>() + cells * sizeof(double));
   return TE_OK;
 }
 
@@ -531,9 +519,10 @@ int rebuild_footprint_tables_impl(te_ctx* c) {
     std::vector<int> ctab((size_t)(2 * f.reach + 1) * (2 * f.reach + 1) * 6);
     fast::build_clip_table(d, f.reach, ctab.data());
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->d_spiral) HIP_TRY(hipMalloc((void**)&c->d_spiral, sizeof(uint32_t) * kMaxSpiral));
-    HIP_TRY(hipMemcpyAsync(c->d_spiral, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    if (!c->fp_clip_table) HIP_TRY(hipMalloc((void**)&c->fp_clip_table, sizeof(int) * (2 * fast::kFpClipInts + kMaxTies)));
+    HIP_TRY(c->cmem.spiral.once(sizeof(uint32_t) * kMaxSpiral));
+    HIP_TRY(hipMemcpyAsync(c->cmem.spiral.p, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c->cmem.fp_clip_table.once(sizeof(int) * (2 * fast::kFpClipInts + kMaxTies)));
+    int* const fp_clip_table = c->cmem.fp_clip_table.as<int>();
     std::vector<int> ctab_full;
     int gen_tab[kMaxTies];
     if (d.n_ties) {  // the disc with the cells on its circle (fixed-point sliding sum of a tie radius, te_footprint4.hip)
@@ -545,14 +534,14 @@ int rebuild_footprint_tables_impl(te_ctx* c) {
       }
       ctab_full.resize(ctab.size());
       fast::build_clip_table(full, f.reach, ctab_full.data());
-      HIP_TRY(hipMemcpyAsync(c->fp_clip_table + fast::kFpClipInts, ctab_full.data(), ctab_full.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipMemcpyAsync(fp_clip_table + fast::kFpClipInts, ctab_full.data(), ctab_full.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
       // ... and the offsets on the circle with both parts non-zero, packed (the kernel handles (+-R, 0) and (0, +-R) itself)
       int n_gen = 0;
       for (int t = 0; t < d.n_ties; ++t)
         if (d.tie_di[t] != 0 && d.tie_dj[t] != 0) gen_tab[n_gen++] = ((int)d.tie_di[t] & 0xff) | (((int)d.tie_dj[t] & 0xff) << 8);
-      if (n_gen) HIP_TRY(hipMemcpyAsync(c->fp_clip_table + 2 * fast::kFpClipInts, gen_tab, n_gen * sizeof(int), hipMemcpyHostToDevice, c->stream));
+      if (n_gen) HIP_TRY(hipMemcpyAsync(fp_clip_table + 2 * fast::kFpClipInts, gen_tab, n_gen * sizeof(int), hipMemcpyHostToDevice, c->stream));
     }
-    HIP_TRY(hipMemcpyAsync(c->fp_clip_table, ctab.data(), ctab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(fp_clip_table, ctab.data(), ctab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (f.any) return build_fp_any_tables(c, any);  // TE_OPT_FP_ANY_REACH
     release_fp_any(c);
@@ -605,14 +594,15 @@ int rebuild_tables(te_ctx* c) {
   if (!c->cp.normals.any && (c->cp.normals.R >= 1 || c->cp.normals.n_ties != 0)) {
     const Disc& dn = c->cp.normals;
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->clip_table) HIP_TRY(hipMalloc((void**)&c->clip_table, sizeof(int) * (2 * fast::kClipInts + kMaxTies)));
+    HIP_TRY(c->cmem.clip_table.once(sizeof(int) * (2 * fast::kClipInts + kMaxTies)));
+    int* const clip_table = c->cmem.clip_table.as<int>();
     std::vector<int> tab, tab_full;
     int gen_tab[kMaxTies];
     if (dn.n_ties == 0) {
       const int R = dn.R;
       tab.resize((size_t)(2 * R + 1) * (2 * R + 1) * 6);
       fast::build_clip_table(dn, R, tab.data());
-      HIP_TRY(hipMemcpyAsync(c->clip_table, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipMemcpyAsync(clip_table, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     } else {
       Disc full = dn;
       int n_gen = 0;
@@ -625,12 +615,12 @@ int rebuild_tables(te_ctx* c) {
       const int R = dn.reach;
       tab_full.resize((size_t)(2 * R + 1) * (2 * R + 1) * 6);
       fast::build_clip_table(full, R, tab_full.data());
-      HIP_TRY(hipMemcpyAsync(c->clip_table + fast::kClipInts, tab_full.data(), tab_full.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-      if (n_gen) HIP_TRY(hipMemcpyAsync(c->clip_table + 2 * fast::kClipInts, gen_tab, n_gen * sizeof(int), hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipMemcpyAsync(clip_table + fast::kClipInts, tab_full.data(), tab_full.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+      if (n_gen) HIP_TRY(hipMemcpyAsync(clip_table + 2 * fast::kClipInts, gen_tab, n_gen * sizeof(int), hipMemcpyHostToDevice, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
-  c->L.clip_table = c->clip_table;
+  c->L.clip_table = c->cmem.clip_table.as<int>();
 
   c->tables_ready = true;
   rebuild_footprint_tables(c);
@@ -639,33 +629,18 @@ int rebuild_tables(te_ctx* c) {
 
 void free_layers(te_ctx* c) {
   drop_graph(c);
-  if (c->slab) (void)hipFree(c->slab);
-  c->slab = nullptr;
-  c->face_flags = nullptr;  // (part of the slab)
+  c->lmem = te_ctx::LayerMem();  // every buffer of the group, the spiral tables of the path checks (clipped to the map) included
+  // ... and what pointed into them: the slab's parts (c->L with its tie_scratch, c->face_flags), the second polygon layer,
+  // the tables of the route of any reach (their prefix sums are sized by the geometry; rebuilt with the tables)
+  memset(&c->L, 0, sizeof(c->L));
+  c->face_flags = nullptr;
+  c->poly_rot = nullptr;
+  clear_fp_any_ptrs(c);
   c->face_crit = __builtin_nan("");
   c->elev_ptr_out = false;
   guard_cache_generation().fetch_add(1, std::memory_order_acq_rel);  // (layer_has_guard_rows: verdicts about freed memory)
-  if (c->poly_x) (void)hipFree(c->poly_x);
-  c->poly_x = c->poly_rot = nullptr;
-  if (c->poly_stream) (void)hipFree(c->poly_stream);
-  c->poly_stream = nullptr;
-  c->poly_stream_cap = 0;
-  if (c->robot_slope) (void)hipFree(c->robot_slope);
-  c->robot_slope = nullptr;
-  if (c->tie_scratch) (void)hipFree(c->tie_scratch);
-  c->tie_scratch = nullptr;
-  if (c->img_stage) (void)hipFree(c->img_stage);
-  c->img_stage = nullptr;
-  c->img_stage_bytes = 0;
-  release_out_scratch(c->occ_out);
-  release_out_scratch(c->cloud_counts);
-  release_out_scratch(c->cloud_out);
-  release_out_scratch(c->expr_scratch);
   c->layers_written = 0;
-  release_fp_any(c);  // (its prefix sums are sized by the geometry; rebuilt with the tables)
-  release_path_discs(c);  // (its spiral tables are clipped to the map)
   c->have_robot_slope = false;
-  memset(&c->L, 0, sizeof(c->L));
   c->layer_elems = 0;
   c->trav_ptr_out = false;
   c->have_elev = false;
@@ -688,9 +663,9 @@ float* layer_ptr(te_ctx* c, int layer) {
     case TE_LAYER_SLOPE_FOOTPRINT: return c->L.slope_fp;
     case TE_LAYER_STEP_FOOTPRINT: return c->L.step_fp;
     case TE_LAYER_ROUGHNESS_FOOTPRINT: return c->L.rough_fp;
-    case TE_LAYER_TRAVERSABILITY_X: return c->poly_x;
+    case TE_LAYER_TRAVERSABILITY_X: return c->lmem.poly.as<float>();
     case TE_LAYER_TRAVERSABILITY_ROT: return c->poly_rot;
-    case TE_LAYER_ROBOT_SLOPE: return c->robot_slope;
+    case TE_LAYER_ROBOT_SLOPE: return c->lmem.robot_slope.as<float>();
     default: return nullptr;
   }
 }
@@ -698,16 +673,15 @@ float* layer_ptr(te_ctx* c, int layer) {
 // the optional input layer robot_slope exists from its first upload on (every cell NaN = not valid until written)
 int ensure_input_layer(te_ctx* c, int layer) {
   c->layers_written |= bit(layer);  // (every upload route and te_device_ptr pass here before they write: te_ctx.h)
-  if (layer != TE_LAYER_ROBOT_SLOPE || c->robot_slope) return TE_OK;
+  DevBuf& rs = c->lmem.robot_slope;
+  if (layer != TE_LAYER_ROBOT_SLOPE || rs.p) return TE_OK;
   HIP_TRY(hipSetDevice(c->device));
-  void* p = nullptr;
-  HIP_TRY(hipMalloc(&p, c->layer_elems * sizeof(float)));
-  const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)p, 0x7fc00000, c->layer_elems, c->stream);
+  HIP_TRY(rs.once(c->layer_elems * sizeof(float)));
+  const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)rs.p, 0x7fc00000, c->layer_elems, c->stream);
   if (e != hipSuccess) {
-    (void)hipFree(p);
+    rs.release();
     return fail(TE_ERR_HIP, "robot_slope layer: %s", hipGetErrorString(e));
   }
-  c->robot_slope = (float*)p;
   return TE_OK;
 }
 
@@ -748,14 +722,7 @@ int run_chain_locked(te_ctx* c, unsigned flags, const Region& r) {
   c->L.ev_join = c->ev_join;
   c->L.fb_walk = c->opt_fb_walk;
   c->L.fb_blocks_per_cu = c->opt_fb_blocks_per_cu;
-  c->L.sparse_holes = sparse_holes(c) && ensure_hole_queue(c) ? 1 : 0;  // (run_whole_locked allocates before it captures)
-  c->L.no_holes = c->invalid_cells == 0 ? 1 : 0;
-  c->L.skip_clean = c->L.sparse_holes && skip_clean_march(c) ? 1 : 0;
-  c->L.short_strips = short_strips(c) ? 1 : 0;
-  c->L.hole_queue = c->hole_queue;
-  ensure_tie_scratch(c);  // (likewise)
-  c->L.tie_scratch = c->tie_scratch;
-  c->cp.rank_rule = c->opt_rank_rule;
+  set_launch_hints(c);  // (run_whole_locked allocates their buffers before it captures)
   if (c->opt_rank_rule) flags |= TE_RUN_GENERIC_KERNELS;  // (the rule lives in the generic normals kernel only)
   HIP_TRY(launch_chain(c->geo, c->cp, c->L, r, flags, c->stream));
   c->chain_done = true;
@@ -776,7 +743,7 @@ int run_footprint_locked(te_ctx* c, unsigned flags, bool fresh = false) {
   const ChainParams& q = c->cp;
   const bool bounded = !c->trav_external && (fresh || !c->trav_ptr_out) && q.w_scale >= 0.0f && q.w_slope >= 0.0f && q.w_step >= 0.0f && q.w_rough >= 0.0f;
   const double trav_cap = bounded ? (double)q.w_scale * ((double)q.w_slope + (double)q.w_step + (double)q.w_rough) : -1.0;
-  HIP_TRY(launch_footprint(c->geo, c->fp, c->L, usable_face_flags(c), c->d_spiral, c->fp_clip_table, (flags & TE_RUN_FOOTPRINT_MEMO) != 0,
+  HIP_TRY(launch_footprint(c->geo, c->fp, c->L, usable_face_flags(c), c->cmem.spiral.as<unsigned>(), c->cmem.fp_clip_table.as<int>(), (flags & TE_RUN_FOOTPRINT_MEMO) != 0,
                            c->combine_deferred ? &c->cp : nullptr, trav_cap, c->stream));
   c->combine_deferred = false;
   c->footprint_done = true;
@@ -996,13 +963,6 @@ int te_destroy(te_ctx* c) {
     c->stager.release();
     c->prefetcher.release();
     if (c->prefetch_order) (void)hipStreamDestroy(c->prefetch_order);
-    if (c->d_spiral) (void)hipFree(c->d_spiral);
-    if (c->d_count) (void)hipFree(c->d_count);
-    if (c->hole_queue) (void)hipFree(c->hole_queue);
-    if (c->clip_table) (void)hipFree(c->clip_table);
-    if (c->fp_clip_table) (void)hipFree(c->fp_clip_table);
-    release_fp_any(c);
-    if (c->fa_tab) (void)hipFree(c->fa_tab);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
@@ -1014,8 +974,8 @@ int te_destroy(te_ctx* c) {
         (void)hipStreamSynchronize(st);
         (void)hipStreamDestroy(st);
       }
+    c->cmem = te_ctx::CtxMem();  // (every stream has drained; the device is still current for `delete c`, which finds them empty)
     for (te_ctx::TileSlot* sl : {&c->in_slot[0], &c->in_slot[1], &c->out_slot[0], &c->out_slot[1]}) {
-      if (sl->buf) (void)hipFree(sl->buf);
       if (sl->ready) (void)hipEventDestroy(sl->ready);
       if (sl->freed) (void)hipEventDestroy(sl->freed);
     }
@@ -1150,56 +1110,43 @@ int te_set_geometry(te_ctx* c, int rows, int cols, int batch, double res, double
   // shape must not be served as if they belonged to this one
   if (elems != c->layer_elems || rows != c->geo.rows || cols != c->geo.cols || batch != c->geo.batch) {
     free_layers(c);
-    // one slab: 13 float layers + 1 byte layer, each 256-byte aligned
-    const size_t lb = (elems * sizeof(float) + 255) & ~(size_t)255;
-    const size_t ub = (elems + 255) & ~(size_t)255;
-    void* slab = nullptr;
+    // one slab (te_slab.h: the plan of its parts, with kSlabGuardRows rows of slack before the first and behind the last)
     Geo gtmp;
     gtmp.rows = rows;
     gtmp.cols = cols;
     gtmp.batch = batch;
-    const size_t fb = ((size_t)fast::normals_fast_max_blocks(gtmp) * sizeof(int) + 255) & ~(size_t)255;
-    // (+ the footprint pass's list of cells with an untraversable cell in their disc: one 32-bit entry per cell at
-    // most, and its counter)
-    const size_t list_cap = elems + fast::fp_list_slack(rows, cols, batch, device_cus());
-    const size_t qb = (list_cap * sizeof(unsigned) + 255) & ~(size_t)255;
-    // (guard: kSlabGuardRows rows of slack before the first and behind the last layer -- te_internal.h)
-    const size_t guard = ((size_t)kSlabGuardRows * (size_t)rows * sizeof(float) + 255) & ~(size_t)255;
-    // (+ one byte per 64 x 4 cells: "holds an untraversable cell", written by the mask kernel, 1 = unknown until then)
-    const size_t ufb = (untrav_flag_bytes(rows, cols, batch) + 255) & ~(size_t)255;
-    // (+ the sum kernel's scratch: a second array of the list's size, see Layers::fp_scratch)
-    const size_t pcb = qb;
-    // (+ the face flags of the elevation layer, the same grid: te_face_flags.h, written by the upload's pass)
-    const size_t ffb = (face_flag_bytes(rows, cols, batch) + 255) & ~(size_t)255;
-    const size_t total = guard + 13 * lb + ub + fb + qb + 256 + ufb + pcb + ffb + guard;
-    hipError_t e = hipMalloc(&slab, total);
-    if (e != hipSuccess) return fail(TE_ERR_HIP, "te_set_geometry: hipMalloc(%zu bytes): %s", total, hipGetErrorString(e));
-    c->slab = slab;
-    char* b = (char*)slab + guard;
-    float** ptrs[13] = {&c->L.elev, &c->L.slope, &c->L.step,     &c->L.rough,   &c->L.trav,     &c->L.footprint, &c->L.nx,
-                        &c->L.ny,   &c->L.nz,    &c->L.slope_fp, &c->L.step_fp, &c->L.rough_fp, &c->L.step_height};
-    for (int k = 0; k < 13; ++k) *ptrs[k] = (float*)(b + (size_t)k * lb);
-    c->L.untrav = (uint8_t*)(b + 13 * lb);
-    c->L.block_flags = (int*)(b + 13 * lb + ub);
-    c->L.fp_blocked = list_cap < ((size_t)1 << 32) ? (unsigned*)(b + 13 * lb + ub + fb) : nullptr;
-    c->L.fp_blocked_count = (unsigned*)(b + 13 * lb + ub + fb + qb);
-    c->L.fp_blocked_cap = list_cap;
-    c->L.untrav_flags = (uint8_t*)(b + 13 * lb + ub + fb + qb + 256);
-    c->L.fp_scratch = list_cap < ((size_t)1 << 32) ? (unsigned*)(b + 13 * lb + ub + fb + qb + 256 + ufb) : nullptr;
-    c->face_flags = (uint8_t*)(b + 13 * lb + ub + fb + qb + 256 + ufb + pcb);
+    const SlabPlan sp = plan_slab(rows, cols, batch, (size_t)fast::normals_fast_max_blocks(gtmp), fast::fp_list_slack(rows, cols, batch, device_cus()),
+                                  untrav_flag_bytes(rows, cols, batch), face_flag_bytes(rows, cols, batch));
+    const hipError_t e = c->lmem.slab.once(sp.total);
+    if (e != hipSuccess) return fail(TE_ERR_HIP, "te_set_geometry: hipMalloc(%zu bytes): %s", sp.total, hipGetErrorString(e));
+    char* const slab = c->lmem.slab.as<char>();
+    float** ptrs[kSlabFloatLayers] = {&c->L.elev, &c->L.slope, &c->L.step,     &c->L.rough,   &c->L.trav,     &c->L.footprint, &c->L.nx,
+                                      &c->L.ny,   &c->L.nz,    &c->L.slope_fp, &c->L.step_fp, &c->L.rough_fp, &c->L.step_height};
+    for (int k = 0; k < kSlabFloatLayers; ++k) *ptrs[k] = (float*)(slab + sp.layer_off(k));
+    // (the list of cells with an untraversable cell in their disc holds 32-bit entries: absent beyond them)
+    const bool have_list = sp.list_cap < ((size_t)1 << 32);
+    c->L.untrav = (uint8_t*)(slab + sp.mask.off);
+    c->L.block_flags = (int*)(slab + sp.fix_flags.off);
+    c->L.fp_blocked = have_list ? (unsigned*)(slab + sp.list.off) : nullptr;
+    c->L.fp_blocked_count = (unsigned*)(slab + sp.list_count.off);
+    c->L.fp_blocked_cap = sp.list_cap;
+    c->L.untrav_flags = (uint8_t*)(slab + sp.untrav_flags.off);
+    c->L.fp_scratch = have_list ? (unsigned*)(slab + sp.sum_scratch.off) : nullptr;  // (the sum kernel's, see Layers::fp_scratch)
+    c->face_flags = (uint8_t*)(slab + sp.face_flags.off);  // (te_face_flags.h, written by the upload's pass)
     c->face_crit = __builtin_nan("");
     c->layer_elems = elems;
-    // outputs read as NaN until computed, like GridMap::add()
-    HIP_TRY(hipMemsetAsync(slab, 0xFF, guard + 13 * lb + ub + fb, c->stream));
-    HIP_TRY(hipMemsetAsync(b + 13 * lb + ub + fb + qb + 256 + ufb + pcb + ffb, 0xFF, guard, c->stream));
-    HIP_TRY(hipMemsetAsync(c->face_flags, 0x01, ffb, c->stream));
-    HIP_TRY(hipMemsetAsync(c->L.untrav_flags, 0x01, ufb, c->stream));
+    // outputs read as NaN until computed, like GridMap::add(): the front guard, the layers, the mask and the fix-up flags ...
+    HIP_TRY(hipMemsetAsync(slab, 0xFF, sp.list.off, c->stream));
+    HIP_TRY(hipMemsetAsync(slab + sp.back_guard.off, 0xFF, sp.back_guard.bytes, c->stream));
+    // (the flag grids: 1 = "holds an untraversable cell" / "a vertical face", unknown until their kernels have written them)
+    HIP_TRY(hipMemsetAsync(c->face_flags, 0x01, sp.face_flags.bytes, c->stream));
+    HIP_TRY(hipMemsetAsync(c->L.untrav_flags, 0x01, sp.untrav_flags.bytes, c->stream));
     // the mask layer holds 0 / 1 only (k_fp_slide5 packs the byte as it is): "untraversable" until the mask kernel has
     // looked at the cell, as a byte of 0xFF would also say -- but 1 stays inside the packed word's flag bit
-    HIP_TRY(hipMemsetAsync(c->L.untrav, 0x01, ub, c->stream));
-    HIP_TRY(hipMemsetAsync(c->L.fp_blocked_count, 0, 256, c->stream));
+    HIP_TRY(hipMemsetAsync(c->L.untrav, 0x01, sp.mask.bytes, c->stream));
+    HIP_TRY(hipMemsetAsync(c->L.fp_blocked_count, 0, sp.list_count.bytes, c->stream));
     // the fix-up flags are zero between launches: k_normals_fixup clears every flag it consumes
-    HIP_TRY(hipMemsetAsync(c->L.block_flags, 0, fb, c->stream));
+    HIP_TRY(hipMemsetAsync(c->L.block_flags, 0, sp.fix_flags.bytes, c->stream));
   }
   c->geo.rows = rows;
   c->geo.cols = cols;
@@ -1235,15 +1182,7 @@ int te_run_filter(te_ctx* c, int filter, unsigned flags) {
   if (filter == TE_FILTER_NORMALS)
     if (int rc = refuse_rank_rule(c)) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  ensure_tie_scratch(c);
-  c->L.tie_scratch = c->tie_scratch;
-  // (the hints the normals kernel takes from the upload's count, as run_chain_locked sets them: never stale ones)
-  c->L.sparse_holes = sparse_holes(c) && ensure_hole_queue(c) ? 1 : 0;
-  c->L.hole_queue = c->hole_queue;
-  c->L.no_holes = c->invalid_cells == 0 ? 1 : 0;
-  c->L.skip_clean = c->L.sparse_holes && skip_clean_march(c) ? 1 : 0;
-  c->L.short_strips = short_strips(c) ? 1 : 0;
-  c->cp.rank_rule = c->opt_rank_rule;  // (TE_OPT_NORMALS_RANK_RULE: as in the chain)
+  set_launch_hints(c);  // (as in the chain: never stale ones)
   if (c->opt_rank_rule) flags |= TE_RUN_GENERIC_KERNELS;
   HIP_TRY(launch_filter(c->geo, c->cp, c->L, filter, flags, c->stream));
   // A single plugin's filter overwrites score layers from whatever inputs are resident (TE_FILTER_NORMALS also slope
@@ -1298,7 +1237,7 @@ int te_run_chain_region(te_ctx* c, unsigned flags, int map, int row0, int col0, 
   const ChainParams& q = c->cp;
   const bool bounded = !c->trav_external && !c->trav_ptr_out && q.w_scale >= 0.0f && q.w_slope >= 0.0f && q.w_step >= 0.0f && q.w_rough >= 0.0f;
   const double trav_cap = bounded ? (double)q.w_scale * ((double)q.w_slope + (double)q.w_step + (double)q.w_rough) : -1.0;
-  HIP_TRY(launch_footprint(c->geo, c->fp, c->L, usable_face_flags(c), c->d_spiral, c->fp_clip_table, (flags & TE_RUN_FOOTPRINT_MEMO) != 0, nullptr, trav_cap,
+  HIP_TRY(launch_footprint(c->geo, c->fp, c->L, usable_face_flags(c), c->cmem.spiral.as<unsigned>(), c->cmem.fp_clip_table.as<int>(), (flags & TE_RUN_FOOTPRINT_MEMO) != 0, nullptr, trav_cap,
                            c->stream, &changed));
   c->footprint_done = true;  // complete before, refreshed where it could change
   c->mask_done = mask_was_done;  // (likewise the mask -- unless a score layer was uploaded since it was built)

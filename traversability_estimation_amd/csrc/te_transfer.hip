@@ -57,21 +57,15 @@ int check_tile(te_ctx* c, const char* who, int map, int row0, int col0, int h, i
   return TE_OK;
 }
 
-// a staging slot of at least n floats with its two events; growing one waits for whatever still uses it
-int prepare_slot(te_ctx* c, te_ctx::TileSlot& sl, size_t n) {
+// a staging slot of at least n floats with its two events; growing one waits for whatever still uses it: `consumer` is
+// the stream the slot's `freed` event is recorded on, the last one to touch the buffer.  Draining it is enough (no
+// hipDeviceSynchronize): the consumer's copy waited for `ready`, which the producer's stream records behind its own copy,
+// so once the consumer has drained neither stream has work on the buffer left.
+int prepare_slot(te_ctx::TileSlot& sl, DevBuf& buf, size_t n, hipStream_t consumer) {
   if (!sl.ready) HIP_TRY(hipEventCreateWithFlags(&sl.ready, hipEventDisableTiming));
   if (!sl.freed) HIP_TRY(hipEventCreateWithFlags(&sl.freed, hipEventDisableTiming));
-  if (sl.cap < n) {
-    if (sl.buf) {
-      HIP_TRY(hipDeviceSynchronize());
-      HIP_TRY(hipFree(sl.buf));
-      sl.buf = nullptr;
-      sl.cap = 0;
-      sl.used = false;
-    }
-    HIP_TRY(hipMalloc((void**)&sl.buf, n * sizeof(float)));
-    sl.cap = n;
-  }
+  if (buf.bytes < n * sizeof(float)) sl.used = false;
+  HIP_TRY(buf.reserve(n * sizeof(float), consumer));
   return TE_OK;
 }
 
@@ -104,16 +98,18 @@ int te_upload_tile_async(te_ctx* c, const float* host_tile, int map, int row0, i
   HIP_TRY(hipSetDevice(c->device));
   if (const int rc = tile_streams(c)) return rc;
   te_ctx::TileSlot& sl = c->in_slot[c->in_next];
+  DevBuf& slot_buf = c->cmem.tile_in[c->in_next];
   c->in_next ^= 1;
-  if (const int rc = prepare_slot(c, sl, (size_t)h * w)) return rc;
+  if (const int rc = prepare_slot(sl, slot_buf, (size_t)h * w, c->stream)) return rc;
+  float* const buf = slot_buf.as<float>();
   // PCIe into the slot on the copy-in stream, once the compute stream has consumed what the slot held before
   if (sl.used) HIP_TRY(hipStreamWaitEvent(c->in_stream, sl.freed, 0));
-  HIP_TRY(hipMemcpyAsync(sl.buf, host_tile, (size_t)h * w * sizeof(float), hipMemcpyHostToDevice, c->in_stream));
+  HIP_TRY(hipMemcpyAsync(buf, host_tile, (size_t)h * w * sizeof(float), hipMemcpyHostToDevice, c->in_stream));
   HIP_TRY(hipEventRecord(sl.ready, c->in_stream));
   // into the layer on the compute stream: ordered after every launch already queued there (they may still read the cells)
   HIP_TRY(hipStreamWaitEvent(c->stream, sl.ready, 0));
   float* dst = c->L.elev + (size_t)map * c->geo.rows * c->geo.cols + (size_t)col0 * c->geo.rows + row0;
-  HIP_TRY(hipMemcpy2DAsync(dst, (size_t)c->geo.rows * sizeof(float), sl.buf, (size_t)h * sizeof(float), (size_t)h * sizeof(float),
+  HIP_TRY(hipMemcpy2DAsync(dst, (size_t)c->geo.rows * sizeof(float), buf, (size_t)h * sizeof(float), (size_t)h * sizeof(float),
                            (size_t)w, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(hipEventRecord(sl.freed, c->stream));
   sl.used = true;
@@ -133,17 +129,19 @@ int te_download_tile_async(te_ctx* c, int layer, int map, int row0, int col0, in
   HIP_TRY(hipSetDevice(c->device));
   if (const int rc = tile_streams(c)) return rc;
   te_ctx::TileSlot& sl = c->out_slot[c->out_next];
+  DevBuf& slot_buf = c->cmem.tile_out[c->out_next];
   c->out_next ^= 1;
-  if (const int rc = prepare_slot(c, sl, (size_t)h * w)) return rc;
+  if (const int rc = prepare_slot(sl, slot_buf, (size_t)h * w, c->out_stream)) return rc;
+  float* const buf = slot_buf.as<float>();
   // the rectangle as the launches queued so far leave it, copied aside on the compute stream (the next tick may
   // overwrite it), once the slot's previous content has crossed PCIe
   if (sl.used) HIP_TRY(hipStreamWaitEvent(c->stream, sl.freed, 0));
   const float* src = p + (size_t)map * c->geo.rows * c->geo.cols + (size_t)col0 * c->geo.rows + row0;
-  HIP_TRY(hipMemcpy2DAsync(sl.buf, (size_t)h * sizeof(float), src, (size_t)c->geo.rows * sizeof(float), (size_t)h * sizeof(float),
+  HIP_TRY(hipMemcpy2DAsync(buf, (size_t)h * sizeof(float), src, (size_t)c->geo.rows * sizeof(float), (size_t)h * sizeof(float),
                            (size_t)w, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(hipEventRecord(sl.ready, c->stream));
   HIP_TRY(hipStreamWaitEvent(c->out_stream, sl.ready, 0));
-  HIP_TRY(hipMemcpyAsync(host_tile, sl.buf, (size_t)h * w * sizeof(float), hipMemcpyDeviceToHost, c->out_stream));
+  HIP_TRY(hipMemcpyAsync(host_tile, buf, (size_t)h * w * sizeof(float), hipMemcpyDeviceToHost, c->out_stream));
   HIP_TRY(hipEventRecord(sl.freed, c->out_stream));
   sl.used = true;
   c->tiles_pending = true;
@@ -179,7 +177,7 @@ int te_set_layer_present(te_ctx* c, int layer, int present) {
   if (!c) return fail(TE_ERR_INVALID_ARG, "te_set_layer_present: NULL ctx");
   CtxLock lk(c);
   if (layer != TE_LAYER_ROBOT_SLOPE) return fail(TE_ERR_INVALID_ARG, "te_set_layer_present: only the optional input layer robot_slope can be declared present / absent");
-  if (present && !c->robot_slope) return fail(TE_ERR_NOT_READY, "te_set_layer_present: robot_slope was never uploaded nor handed out (te_device_ptr)");
+  if (present && !c->lmem.robot_slope.p) return fail(TE_ERR_NOT_READY, "te_set_layer_present: robot_slope was never uploaded nor handed out (te_device_ptr)");
   c->have_robot_slope = present != 0;
   return TE_OK;
 }
@@ -392,18 +390,10 @@ static int upload_image_checked(const char* who, te_ctx* c, const te_image_info*
   HIP_TRY(hipSetDevice(c->device));
   // the image as it is -- 1 .. 8 bytes per cell -- into the context's staging buffer, then one kernel into the layer
   const size_t bytes = img::payload_bytes(*info);
-  if (c->img_stage_bytes < bytes + img::kStagePad) {
-    if (c->img_stage) {
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      (void)hipFree(c->img_stage);
-      c->img_stage = nullptr;
-      c->img_stage_bytes = 0;
-    }
-    HIP_TRY(hipMalloc(&c->img_stage, bytes + img::kStagePad));
-    c->img_stage_bytes = bytes + img::kStagePad;
-  }
-  HIP_TRY(c->stager.upload(c->img_stage, pixels, bytes, c->stream));
-  HIP_TRY(img::launch_to_layer(c->img_stage, *info, p + (size_t)map * c->geo.rows * c->geo.cols, lower, upper,
+  DevBuf& stage = c->lmem.img_stage;
+  HIP_TRY(stage.reserve(bytes + img::kStagePad, c->stream));
+  HIP_TRY(c->stager.upload(stage.p, pixels, bytes, c->stream));
+  HIP_TRY(img::launch_to_layer(stage.p, *info, p + (size_t)map * c->geo.rows * c->geo.cols, lower, upper,
                                img::alpha_threshold_sample(alpha_threshold, info->bytes_per_channel), c->stream));
   if (layer == TE_LAYER_ELEVATION) {
     // (the count also waits for the copy and the kernel: the host buffer may be reused as soon as we return)
