@@ -50,6 +50,10 @@
  *                        <- the grid_map_visualization entries of traversability_estimation/config/visualization/
  *                           traversability.yaml (type occupancy_grid for the four score layers, type point_cloud for the
  *                           elevation): GridMapRosConverter::toOccupancyGrid / toPointCloud, converted on the device
+ *   te_submap_geometry / te_download_submap / te_download_submap_msg
+ *                        <- the get_traversability service, TraversabilityEstimation.cpp:297-316:
+ *                           GridMap::getSubmap(position, length) of the traversability map and toMessage(subMap, layers);
+ *                           the rectangle of the requested layers is packed on the device and crosses PCIe in one transfer
  *
  * Data contract (identical to grid_map::Matrix = Eigen::MatrixXf): float32, COLUMN-major,
  * element (row i, col j) of map m at ptr[m*rows*cols + j*rows + i]; invalid cell = non-finite.
@@ -615,6 +619,56 @@ int te_cloud_field(const void* msg, size_t len, int k, char* name, uint32_t* off
 /* The spans of the compaction (tests place holes across them): cells[0] = cells of one wavefront's ballot, cells[1] = cells
  * one workgroup counts, cells[2] = cells one scan workgroup's span covers. */
 int te_cloud_spans(size_t cells[3]);
+
+/* ---- submap requests: the data path behind the get_traversability service (TraversabilityEstimation.cpp:297-316) ----
+ * A planner names a position, a length and a list of layers; the node answers with GridMap::getSubmap(position, length) of the
+ * traversability map, serialised by toMessage(subMap, layers).  Only the rectangle of the named layers crosses PCIe.
+ *
+ * Semantics = GridMap::getSubmap / getSubmapInformation (RESTATED here: grid_map_core is not in the reference tree, so like the
+ * image and output routes this is a stated contract with no reference-held vector) for a map whose start
+ * index is (0, 0), which device layers always have.  IEEE double, grid_map's order of operations, per axis (len = cells * res):
+ *   - corner = position +- length / 2, bounded to the map by boundPositionToRange:
+ *         shifted = (corner - map_position) + len / 2;  eps = 10 * DBL_EPSILON, times |corner| when |corner| > 1
+ *         shifted <= 0 -> eps;  shifted >= len -> len - eps;  bounded = (shifted + map_position) - len / 2
+ *   - index = (int)(-(((bounded - len / 2) - map_position) / res)), truncated; row0 / col0 from the corner at + length / 2, the
+ *     last row / column from the one at - length / 2.  rows = last - first + 1, likewise cols.
+ *   - the submap's length = rows * res (cols * res); its position = ((map_position + (len / 2 - res / 2)) + res * (double)(-first)
+ *     + res / 2) - length / 2.
+ *   - ok = 0 (getSubmap returns false; the service answers isSuccess = false) when a bounded corner is still outside the map
+ *     (checkIfPositionWithinMap: -((p - map_position) - len / 2) in [0, len)), when the first index is no cell of the map, or
+ *     when the requested position lies outside the submap's own geometry -- a centre outside the map, for one.
+ *   - a request larger than the map is clamped to it; length 0 gives the one cell under the bounded corners.
+ * Arguments are checked first: a non-finite position or length, a negative length (and, in te_submap_geometry, rows or cols
+ * below 1, a resolution that is not positive and finite, a non-finite map position) give TE_ERR_INVALID_ARG. */
+typedef struct te_submap_info {
+  int32_t ok, row0, col0, rows, cols;          /* the rectangle in the map; everything but `ok` is 0 when ok == 0 */
+  double pos_x, pos_y, length_x, length_y;     /* the submap's own geometry */
+} te_submap_info;
+/* Host only, no context: the geometry of one request on a rows x cols map at (pos_x, pos_y). */
+int te_submap_geometry(int rows, int cols, double resolution, double pos_x, double pos_y, double req_x, double req_y,
+                       double req_len_x, double req_len_y, te_submap_info* out);
+/* The submap of n_layers (1 .. 16; an id may repeat) layers of map `map`: out[(k * cols + j) * rows + i] = layer k at
+ * (row0 + i, col0 + j), rows / cols / row0 / col0 those of *info -- the column-major submap matrices one after another, which
+ * is the payload toMessage carries for them.  ONE launch and ONE device -> host transfer, whatever n_layers is; `out` may be
+ * pageable or page-locked (te_pin_host).  Synchronous.
+ *   *info is filled whenever the arguments pass their checks.  info->ok == 0: TE_OK, nothing is written.
+ *   cap_floats below n_layers * rows * cols: TE_ERR_INVALID_ARG, *info filled (size the buffer from it), nothing is written.
+ *   TE_ERR_NOT_READY: no geometry; TE_ERR_INVALID_ARG: NULL, a layer id that is out of range or names a layer that does not
+ *   exist yet (as te_download_msg), a map index or n_layers out of range, the request checks above.
+ * A prefetch in flight on one of the layers is joined first.  The call reads the layers and changes nothing in the context:
+ * chain, footprint and mask results, present flags and parameters stay. */
+#define TE_SUBMAP_MAX_LAYERS 16
+int te_download_submap(te_ctx* ctx, int map, double req_x, double req_y, double req_len_x, double req_len_y, int n_layers,
+                       const int* layers, te_submap_info* info, float* out, size_t cap_floats);
+/* toMessage(subMap, layers) of map 0 as a serialised grid_map_msgs/GridMap, through the writer behind te_msg_write: resolution,
+ * lengths and position (pose x, y) are the submap's own, the start index is (0, 0); seq, stamp, frame_id, pose z and
+ * orientation come from `info_in` (its other fields are ignored); layer k is named names[k].  The packed cells land in `out`
+ * with one transfer and the header is written behind them: a call that fails on the device leaves no valid-looking message.
+ * *written = bytes needed even when TE_ERR_INVALID_ARG reports that `cap` is too small (out = NULL, cap = 0 sizes the buffer
+ * without touching the device); info->ok == 0: TE_OK, *written = 0, nothing is written. */
+int te_download_submap_msg(te_ctx* ctx, const te_msg_info* info_in, double req_x, double req_y, double req_len_x,
+                           double req_len_y, int n_layers, const int* layers, const char* const* names, int n_basic,
+                           const char* const* basic_names, te_submap_info* info, void* out, size_t cap, size_t* written);
 
 /* ---- gridMapFilters/MathExpressionFilter with ANY expression (robot_filter_parameter.yaml:29-33) ----
  * te_run_chain / TE_FILTER_COMBINE run the weighted sum of the three scores (te_params: w_scale, w_slope, w_step, w_rough) and

@@ -48,9 +48,10 @@ SYMBOLS = ["te_params_default", "te_params_validate", "te_device_count", "te_cre
            "te_image_parse", "te_upload_image", "te_upload_image_msg",
            "te_download_occupancy", "te_download_occupancy_msg", "te_occupancy_msg_write", "te_occupancy_parse",
            "te_download_cloud", "te_download_cloud_msg", "te_cloud_msg_write", "te_cloud_parse", "te_cloud_field", "te_cloud_spans",
+           "te_submap_geometry", "te_download_submap", "te_download_submap_msg",
            "te_expr_check", "te_run_expression", "te_time_expression_samples"]
 MSG_MAX_NAME = 64
-OCCUPANCY_MAX_LAYERS = CLOUD_MAX_LAYERS = 16
+OCCUPANCY_MAX_LAYERS = CLOUD_MAX_LAYERS = SUBMAP_MAX_LAYERS = 16
 POINTFIELD_FLOAT32 = 7
 
 
@@ -123,6 +124,12 @@ class TeCloudInfo(C.Structure):
                 ("height", C.c_uint32), ("width", C.c_uint32),
                 ("n_fields", C.c_uint32), ("point_step", C.c_uint32), ("row_step", C.c_uint32),
                 ("is_bigendian", C.c_int32), ("is_dense", C.c_int32)]
+
+
+class TeSubmapInfo(C.Structure):
+    """te_submap_info: what GridMap::getSubmap makes of a request -- the rectangle in the map and the submap's own geometry."""
+    _fields_ = [("ok", C.c_int32), ("row0", C.c_int32), ("col0", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("pos_x", C.c_double), ("pos_y", C.c_double), ("length_x", C.c_double), ("length_y", C.c_double)]
 
 
 # encoding name -> (channels, bytes per channel): the encodings te_image_parse accepts
@@ -252,6 +259,10 @@ def load():
         L.te_cloud_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(TeCloudInfo), szp]
         L.te_cloud_field.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_char_p, u32p, u32p, u32p]
         L.te_cloud_spans.argtypes = [szp]
+        smp = C.POINTER(TeSubmapInfo)
+        L.te_submap_geometry.argtypes = [C.c_int, C.c_int] + [C.c_double] * 7 + [smp]
+        L.te_download_submap.argtypes = [vp, C.c_int] + [C.c_double] * 4 + [C.c_int, ip, smp, vp, C.c_size_t]
+        L.te_download_submap_msg.argtypes = [vp, C.POINTER(TeMsgInfo)] + [C.c_double] * 4 + [C.c_int, ip, cpp, C.c_int, cpp, smp, vp, C.c_size_t, szp]
         L.te_expr_check.argtypes = [C.c_char_p, C.POINTER(TeExprInfo)]
         L.te_run_expression.argtypes = [vp, C.c_char_p, C.c_int]
         L.te_time_expression_samples.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
@@ -409,6 +420,15 @@ def cloud_spans():
     c = (C.c_size_t * 3)()
     _check(load().te_cloud_spans(c))
     return tuple(int(v) for v in c)
+
+
+def submap_geometry(rows, cols, res, pos, position, length):
+    """GridMap::getSubmap's geometry for a request (position, length) on a rows x cols map centred at `pos` (host only, no
+    context): a TeSubmapInfo -- ok, the rectangle row0 / col0 / rows / cols, the submap's position and length."""
+    info = TeSubmapInfo()
+    _check(load().te_submap_geometry(int(rows), int(cols), float(res), float(pos[0]), float(pos[1]), float(position[0]),
+                                     float(position[1]), float(length[0]), float(length[1]), C.byref(info)))
+    return info
 
 
 def _layer_ids(layers):
@@ -823,6 +843,42 @@ class Context:
         out = C.create_string_buffer(max(need.value, 1))
         _check(L.te_download_cloud_msg(*args, out, need.value, C.byref(need)))
         return out.raw[:need.value]
+
+    def download_submap(self, position, length, layers, map=0, out=None):
+        """GridMap::getSubmap(position, length) of `layers` (names or ids) of one map, packed on the device: returns (info,
+        {layer: array[h, w]}) -- views of one float32 buffer --, and (info, {}) when info.ok == 0.  out: a reusable (possibly
+        pinned) float32 buffer with room for the submap; without one the geometry call sizes a new buffer."""
+        ids, n = _layer_ids(layers)
+        info = TeSubmapInfo()
+        L = load()
+        if out is None:
+            L.te_download_submap(self._h, int(map), float(position[0]), float(position[1]), float(length[0]), float(length[1]), n, ids,
+                                 C.byref(info), None, 0)  # (the sizing call: fills info, or fails as the real one will)
+            out = np.empty(max(n * info.rows * info.cols, 1), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous
+        _check(L.te_download_submap(self._h, int(map), float(position[0]), float(position[1]), float(length[0]), float(length[1]), n, ids,
+                                    C.byref(info), C.c_void_p(out.ctypes.data), out.size))
+        if not info.ok:
+            return info, {}
+        h, w = info.rows, info.cols
+        packed = out.reshape(-1)[:n * w * h].reshape(n, w, h)
+        return info, {name: packed[k].T for k, name in enumerate(layers)}
+
+    def download_submap_msg(self, info, position, length, layers, basic_layers=()):
+        """toMessage(getSubmap(position, length), layers) of map 0: {message layer name: device layer} -> (TeSubmapInfo,
+        serialised grid_map_msgs/GridMap bytes); (info, b"") when the request fails (info.ok == 0).  seq, stamp, frame_id,
+        pose z and orientation come from `info` (a TeMsgInfo)."""
+        names = list(layers)
+        ids, n = _layer_ids(layers.values())
+        need = C.c_size_t()
+        sub = TeSubmapInfo()
+        L = load()
+        args = (self._h, C.byref(info), float(position[0]), float(position[1]), float(length[0]), float(length[1]), n, ids, _names(names),
+                len(basic_layers), _names(list(basic_layers)), C.byref(sub))
+        L.te_download_submap_msg(*args, None, 0, C.byref(need))
+        out = C.create_string_buffer(max(need.value, 1))
+        _check(L.te_download_submap_msg(*args, out, need.value, C.byref(need)))
+        return sub, out.raw[:need.value]
 
     def run_polygon_footprint(self, points_xy, yaw):
         """traversabilityFootprint(footprintYaw): fills the layers traversability_x / traversability_rot."""

@@ -1,5 +1,6 @@
-// te_out_kernels.h -- the launches of the two output conversions (te_occupancy.hip, te_cloud.hip) as the entry points and
-// tools/output_kernel_bench.hip call them: plain device pointers, one stream, no context.
+// te_out_kernels.h -- the launches of the two output conversions (te_occupancy.hip, te_cloud.hip) and of the submap pack
+// (te_submap.hip) as the entry points and tools/output_kernel_bench.hip / tools/submap_kernel_bench.hip call them: plain device
+// pointers, one stream, no context.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -44,4 +45,15 @@ hipError_t launch_scatter(const Spec& s, const Geo& g, size_t n, const unsigned 
                           hipStream_t stream);
 
 }  // namespace cloud
+
+namespace submap {
+
+struct Job {
+  const float* src[TE_SUBMAP_MAX_LAYERS];  // cell (row0, col0) of one map of a layer: the rectangle's first cell
+};
+// the h x w rectangles of layers 0 .. n_layers - 1 of `job` (columns `stride` floats apart) -> out[(k * w + j) * h + i]: the
+// column-major h x w matrices one after another; out: any float boundary, n_layers * w * h floats.  One launch.
+hipError_t launch(const Job& job, int n_layers, size_t stride, int h, int w, float* out, hipStream_t stream);
+
+}  // namespace submap
 }  // namespace te

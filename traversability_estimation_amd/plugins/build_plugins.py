@@ -13,6 +13,7 @@ PATHS_TEST = os.path.join(HERE, "plugin_paths_test")
 IMAGE_TEST = os.path.join(HERE, "plugin_image_test")
 OUTPUT_TEST = os.path.join(HERE, "plugin_output_test")
 EXPRESSION_TEST = os.path.join(HERE, "plugin_expression_test")
+SUBMAP_TEST = os.path.join(HERE, "plugin_submap_test")
 SRCS = ["src/DeviceMap.cpp", "src/SlopeFilter.cpp", "src/StepFilter.cpp", "src/RoughnessFilter.cpp",
         "src/FusedChainFilter.cpp", "src/SurfaceNormalsFilter.cpp", "src/TraversabilityMap.cpp", "stubs/pluginlib/registry.cpp"]
 
@@ -59,6 +60,13 @@ def build(verbose=False):
     # FusedChainFilter with an `expression` parameter (tests/test_plugins_expression.py)
     cmd = cmd[:cmd.index(OUTPUT_TEST)] + [EXPRESSION_TEST]
     cmd[cmd.index(os.path.join(HERE, "test", "plugin_output_test.cpp"))] = os.path.join(HERE, "test", "plugin_expression_test.cpp")
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    # TraversabilityMap::getTraversabilityMap(position, length, layers, message) (tests/test_plugins_submap.py)
+    # (the driver parses the message with te_msg_parse / te_msg_layer itself: it names libtravgpu.so on its own line)
+    cmd = cmd[:cmd.index("-o")] + ["-L" + PKG, "-ltravgpu", "-o", SUBMAP_TEST]
+    cmd[cmd.index(os.path.join(HERE, "test", "plugin_expression_test.cpp"))] = os.path.join(HERE, "test", "plugin_submap_test.cpp")
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

@@ -9,6 +9,7 @@
 #ifndef TRAVERSABILITY_ESTIMATION_GPU_TRAVERSABILITYMAP_HPP
 #define TRAVERSABILITY_ESTIMATION_GPU_TRAVERSABILITYMAP_HPP
 
+#include <cstdint>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -83,6 +84,14 @@ class TraversabilityMap {
   /*! GridMapRosConverter::toPointCloud(map, layers, pointLayer, cloud) on the device: only the cells whose point layer is
    *  finite cross PCIe (te_download_cloud).  pointLayer must be one of `layers`. */
   bool getPointCloud(const std::vector<std::string>& layers, const std::string& pointLayer, sensor_msgs::PointCloud2& cloud);
+  /*! The get_traversability service body (TraversabilityEstimation.cpp:297-316) on the device: `message` receives the ROS1
+   *  serialisation of the grid_map_msgs/GridMap that toMessage(getTraversabilityMap().getSubmap(position, length), layers)
+   *  gives -- the submap's own geometry, start index (0, 0) -- and only the rectangle of the named layers crosses PCIe
+   *  (te_download_submap_msg).  An empty `layers` names every layer getTraversabilityMap() would return, as the service does.
+   *  `header` (may be null) gives seq, stamp, frame_id, pose z and orientation.  Returns getSubmap's isSuccess: false with an
+   *  empty message and an empty error() for a request getSubmap refuses, false + error() for a layer that is not there. */
+  bool getTraversabilityMap(const grid_map::Position& position, const grid_map::Length& length, const std::vector<std::string>& layers,
+                            std::vector<uint8_t>& message, const te_msg_info* header = nullptr);
   bool traversabilityMapInitialized() const { return traversabilityMapInitialized_; }
   const std::string& error() const { return error_; }
 

@@ -424,6 +424,50 @@ bool TraversabilityMap::getPointCloud(const std::vector<std::string>& layers, co
   return true;
 }
 
+bool TraversabilityMap::getTraversabilityMap(const grid_map::Position& position, const grid_map::Length& length,
+                                             const std::vector<std::string>& layers, std::vector<uint8_t>& message, const te_msg_info* header) {
+  std::lock_guard<std::mutex> lock(mutex_);
+  message.clear();
+  error_.clear();
+  std::vector<std::string> names = layers;
+  if (names.empty())  // (:306-307: toMessage(subMap, response.map) takes every layer)
+    for (const char* name : {"elevation", "traversability_slope", "traversability_step", "traversability_roughness", "traversability",
+                             "traversability_footprint", "traversability_x", "traversability_rot"})
+      if (deviceLayer(name) >= 0) names.push_back(name);
+  std::vector<int> ids;
+  std::vector<const char*> cnames;
+  for (const std::string& name : names) {
+    ids.push_back(deviceLayer(name));
+    cnames.push_back(name.c_str());
+    if (ids.back() < 0) {
+      error_ = "getTraversabilityMap: no layer '" + name + "'";
+      return false;
+    }
+  }
+  if (!ctx_ || ids.empty()) {
+    error_ = "getTraversabilityMap: no map";
+    return false;
+  }
+  te_msg_info info = header ? *header : te_msg_info();
+  if (!header) info.pose[6] = 1.0;
+  te_submap_info sub;
+  size_t need = 0;
+  // the sizing call runs the geometry only: it reports the size with TE_ERR_INVALID_ARG (no room), and TE_OK without a size
+  // for a request getSubmap refuses (sub.ok == 0, the service's isSuccess = false)
+  const int rc = te_download_submap_msg(ctx_, &info, position.x(), position.y(), length.x(), length.y(), (int)ids.size(), ids.data(),
+                                        cnames.data(), 0, nullptr, &sub, nullptr, 0, &need);
+  if (need == 0) return rc == TE_OK ? false : check(rc);
+  message.resize(need);
+  if (!check(te_download_submap_msg(ctx_, &info, position.x(), position.y(), length.x(), length.y(), (int)ids.size(), ids.data(), cnames.data(), 0,
+                                    nullptr, &sub, message.data(), message.size(), &need)) ||
+      !sub.ok) {
+    message.clear();
+    return false;
+  }
+  message.resize(need);
+  return true;
+}
+
 grid_map::GridMap TraversabilityMap::getTraversabilityMap() {
   std::lock_guard<std::mutex> lock(mutex_);
   grid_map::GridMap map = geometry_;
