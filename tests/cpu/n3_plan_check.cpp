@@ -7,6 +7,7 @@
 // closed-form tail hold no lane whose disc leaves the map; short strips only shorten.  Exit code 0: all cases hold.
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #include "te_n3_plan.h"
@@ -88,7 +89,23 @@ static void check_case(const Case& c, bool short_strips) {
   }
 }
 
-int main() {
+// `n3_plan_check plan rows cols R slots maps short`: the plan of a whole-map launch, one line
+// "n_int <n> s_int <n> rows_int <n> rows_edge <n> fits <0|1>" (tests/test_conditioning_ref.py asks which blocks and strips
+// its fixtures get)
+static int print_plan(char** v) {
+  Case c{};
+  c.rows = std::atoi(v[0]), c.cols = std::atoi(v[1]), c.R = std::atoi(v[2]);
+  c.i_lo = 0, c.i_hi = c.rows, c.j_lo = 0, c.j_hi = c.cols;
+  c.slots = std::atoi(v[3]), c.maps = std::atoi(v[4]);
+  int nblocks = 0;
+  bool fits = false;
+  const Plan a = make(c, std::atoi(v[5]) != 0, &nblocks, &fits);
+  std::printf("n_int %d s_int %d rows_int %d rows_edge %d fits %d\n", a.n_int, a.s_int, a.rows_int, a.rows_edge, (int)fits);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc == 8 && std::string(argv[1]) == "plan") return print_plan(argv + 2);
   const Case cases[] = {
       {4096, 4096, 9, 0, 4096, 0, 4096, 11 * 256, 1},
       {4096, 4096, 9, 0, 4096, 0, 4096, 12 * 256, 1},
