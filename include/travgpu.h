@@ -185,7 +185,7 @@ int te_get_params(te_ctx* ctx, te_params* p);
 #define TE_OPT_GRAPH_REPLAY 4             /* whole-map launches as a captured hipGraph: 0 by size (the default: from 2^22 cells), 1 always, 2 never */
 #define TE_OPT_POLYGON_PER_CELL 3         /* polygon footprint layers: 1 evaluates every cell of every bounding box instead of the offset table */
 #define TE_OPT_BCAST_RCCL 5               /* te_bcast_params, set on the ROOT context: 0 RCCL only between different devices (the default), 1 also when all contexts share one device (a communicator of one rank) */
-#define TE_OPT_FP_ANY_REACH 7             /* circular footprint pass: 0 (default) by reach -- up to 20 cells the shape-specialised sum kernels, above 20 the route of any reach; 1 the route of any reach for every footprint */
+#define TE_OPT_FP_ANY_REACH 7             /* circular footprint pass: 0 (default) by reach -- up to 20 cells the shape-specialised sum kernels, above 20, and at any reach for a traversability layer without a known bound (te_run_footprint), the route of any reach; 1 the route of any reach for every footprint */
 #define TE_OPT_NORMALS_RANK_RULE 6        /* 1: NormalVectorsFilter as grid_map <= 1.6 had it (the filter that wrote TE/maps/elevation_map.bag): a disc whose scatter matrix is rank-deficient -- exactly planar -- gets UnitZ; runs the shape-generic kernels.  0 (default): the current area method */
 /* Filter discs (normals, roughness, step windows) of any radius, per context:
  *   0 (default) a disc above 32 cells, or with more than 32 offsets on its circle, is refused with TE_ERR_UNSUPPORTED;
@@ -218,8 +218,8 @@ int te_upload_tile(te_ctx* ctx, const float* host_tile, int map, int row0, int c
  * (e.g. a torch tensor filled on the same device); valid until te_set_geometry/te_destroy.
  * Writers order their work against the context themselves (te_sync, or the same device stream order).  Handing out
  * TE_LAYER_TRAVERSABILITY marks that layer as caller-writable until the next te_set_geometry: te_run_footprint and
- * region runs then no longer assume its values are bounded by the chain's weights (they use the double-precision
- * footprint kernel); te_run_chain with TE_RUN_FOOTPRINT rewrites every cell first and is unaffected. */
+ * region runs then no longer assume its values are bounded by the chain's weights (they sum it on the route of any
+ * reach, see te_run_footprint); te_run_chain with TE_RUN_FOOTPRINT rewrites every cell first and is unaffected. */
 int te_device_ptr(te_ctx* ctx, int layer, void** dptr, size_t* bytes);
 /* The optional input layer robot_slope (checkInclination, TraversabilityMap.cpp:748-762; it travels with the elevation
  * map when the caller has one) is present after an upload.  present = 0 declares it absent again -- an elevation map that
@@ -265,8 +265,9 @@ int te_run_chain(te_ctx* ctx, unsigned flags);
  * a reach of 17..20 cells, a map narrower than 64 cells) is served by the general kernel, which recomputes the footprint
  * layer of the WHOLE map `map` (no other map of the batch): cost O(map), not O(region); cells outside the region are
  * recomputed from unchanged inputs and keep their values to within the fixed-point kernels' rounding (< 1e-6).
- * A reach above 20 cells (or TE_OPT_FP_ANY_REACH = 1): the route of any reach recomputes the column prefix sums of the
- * whole map `map` (one streaming pass) and the footprint on the region grown by the reach only. */
+ * A reach above 20 cells, TE_OPT_FP_ANY_REACH = 1, or a traversability layer without a known bound (te_run_footprint):
+ * the route of any reach recomputes the column prefix sums of the whole map `map` (one streaming pass over its 5 bytes
+ * per cell, writing 12) and the footprint on the region grown by the reach only. */
 int te_run_chain_region(te_ctx* ctx, unsigned flags, int map, int row0, int col0, int h, int w);
 /* The h x w rectangle at (row0, col0) of a layer of map `map` into a packed column-major h x w host tile (the layout
  * te_upload_tile reads); returns when the tile is in host memory. */
@@ -280,6 +281,24 @@ int te_download_tile(te_ctx* ctx, int layer, int map, int row0, int col0, int h,
  * otherwise the runtime stages the copy itself and the call blocks for its duration. */
 int te_upload_tile_async(te_ctx* ctx, const float* host_tile, int map, int row0, int col0, int h, int w);
 int te_download_tile_async(te_ctx* ctx, int layer, int map, int row0, int col0, int h, int w, float* host_tile);
+/* The circular footprint pass over the resident layers (te_run_chain with TE_RUN_FOOTPRINT runs the same pass).
+ * Values of the traversability layer: the chain's own layer under weights w with w_scale * (w_slope + w_step + w_rough)
+ * and |fp_default| small enough -- the reference's weights are -- is summed by the shape-specialised kernels (fixed point
+ * within 1e-6 of the reference, or in double).  Every other layer -- written by te_upload_layer, te_run_expression or
+ * through te_device_ptr, combined per plugin, or combined with a negative weight, a large weight or beside a large
+ * fp_default -- has no known bound and is summed on the route of any reach: untraversable cells are counted in integers,
+ * exactly, whatever the values are, and the values of either sign are summed in double as differences of one running
+ * prefix sum per map column.  The error of a disc's sum is therefore NOT local to the disc: it is of the order of
+ * (2 * reach + 1) * 2^-52 * A, with A the sum of |values| (fp_default for non-finite ones, as in the reference) over the
+ * WHOLE column of the map (worst case: 7 roundings of 2^-53 * A more per 64 rows), and the mean carries that divided by
+ * the disc's cells plus float32 rounding.
+ * Supported and tested: |values| up to 1e6 on maps of a few thousand rows, held to 1e-5 * max(1, max |value| of the layer)
+ * (tests/test_gpu_footprint_values.py), and a magnitude ratio of 1e6 within one column, held to (2 * reach + 1) * 2^-48 * A on 96 rows.  Beyond
+ * that nothing is detected and no error is returned; precision degrades gradually by the same formula: a disc of small
+ * values in a column that also holds values 1e10 times larger loses about 1e-5 of its mean, and at a ratio of 2^52 (one
+ * cell of 1e20 above cells of 1) the small values vanish from the sums altogether.  Layers of such dynamic range must be
+ * rescaled or clamped by the caller.  That route takes 12 bytes of device memory per cell, allocated when such a layer is
+ * first summed (TE_ERR_UNSUPPORTED if they do not fit). */
 int te_run_footprint(te_ctx* ctx);
 /* Batched TraversabilityMap::checkFootprintPath for circular footprints (TraversabilityMap.cpp:320-342 ->
  * checkCircularFootprintPath :344-462) on the resident traversability_footprint layer of map `map`, which must be
@@ -719,7 +738,7 @@ int te_expr_check(const char* text, te_expr_info* info);
  *     footprint pass wrote them, traversability_x / _rot before te_run_polygon_footprint, robot_slope while absent.
  *   A failed call leaves every layer as it was.
  *   Afterwards the context is what te_upload_layer(TE_LAYER_TRAVERSABILITY, the same values) leaves: the layer counts as
- *     written from outside (te_run_footprint takes the double-precision kernel), footprint and mask results follow the upload
+ *     written from outside (te_run_footprint takes the route of any reach), footprint and mask results follow the upload
  *     path, the chain's state and te_get_params are untouched.  te_run_footprint and the path checks then read the new values;
  *     the next te_run_chain writes the weighted sum again.
  *   A prefetch in flight that writes a layer the text reads (or the traversability layer) is joined first.

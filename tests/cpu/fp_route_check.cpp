@@ -89,7 +89,15 @@ static int check(const FpRouteIn& in, const FpRoute& r, const char* ctx) {
   const int nbx_l = in.region ? (in.i1 - 1) / 64 - in.i0 / 64 + 1 : (in.rows + 63) / 64;
   const int H = in.region ? in.j1 - in.j0 : in.cols;
   const int nz = in.region ? 1 : in.batch;
-  req((r.route == kFpAny) == in.any, "the route of any reach exactly when asked for or above 20 cells");
+  // The double kernels pack the untraversable count into the disc sum (one double per cell, T' + kFpUOff * U): they are
+  // planned only under a bound that keeps the whole disc's |sum T'| -- and with it every |T'| -- below kFpUOff / 2.  The
+  // bound is restated here from the kernels' decoding, not taken from fp_packed_ok.
+  const double disc_cells = (double)in.npoints + (double)in.n_ties;
+  const bool packed_bound = in.tcap >= 0.0 && disc_cells * std::fmax(in.tcap, std::fabs(in.def)) < 0.5 * kFpUOff;
+  req(!in.any || r.route == kFpAny, "the route of any reach when asked for or above 20 cells");
+  if (r.route == kFpSlide3 || r.route == kFpGeneral)
+    req(packed_bound, "a kernel that packs the untraversable count into the sum only with npoints * cap < kFpUOff / 2");
+  if (r.route == kFpAny && !in.any) req(!fp_packed_ok(disc_cells, in.tcap, in.def), "the route of any reach only for want of that bound");
   if (r.route == kFpGeneral) req(in.reach >= 1 && in.reach <= 20, "k_fp_slide<R> is instantiated for reach 1 .. 20");
   if (r.route == kFpSlide5 || r.route == kFpSlide3) {
     req(in.n_ties == 0 && in.reach == in.R, "a tie-free disc");
@@ -176,6 +184,70 @@ int main(int argc, char** argv) {
     }());
     named("zero_rmin", base(9 * tf, 0.0, 4096, 4096));
     named("no_guard_rows", [&] { Case c = base(9 * tf, 6 * tf, 4096, 4096); c.guard_rows = false; return c; }());
+    // ---- the cases of tests/test_gpu_footprint_values.py (tests/footprint_value_cases.py holds the same inputs) ----
+    auto with = [&](Case c, double tcap, double def, bool opt_any = false) {
+      c.tcap = tcap;
+      c.def = def;
+      c.opt_any = opt_any;
+      return c;
+    };
+    // layers from outside (no bound): the inputs of k_fp_slide3 (tie-free 5 and 9) and of the general kernel (reach 18, a
+    // whole-cell tie radius, a 48-row map), with the default 0.3, with fp_default = 50 and with TE_OPT_FP_ANY_REACH
+    const struct { const char* name; double rmax, rmin; int rows, cols; } geos[] = {
+        {"r5", 5 * tf, 3 * tf, 96, 80},     {"r9", 9 * tf, 6 * tf, 96, 80},     {"reach18", 18.5, 12.0, 96, 80},
+        {"tie15", 15.0, 10.0, 96, 80},      {"rows48", 9 * tf, 6 * tf, 48, 80},
+    };
+    char name[96];
+    for (const auto& q : geos) {
+      snprintf(name, sizeof(name), "fv_ext_%s", q.name);
+      named(name, with(base(q.rmax, q.rmin, q.rows, q.cols), -1.0, 0.3));
+      snprintf(name, sizeof(name), "fv_ext_%s_def50", q.name);
+      named(name, with(base(q.rmax, q.rmin, q.rows, q.cols), -1.0, 50.0));
+      snprintf(name, sizeof(name), "fv_ext_%s_any", q.name);
+      named(name, with(base(q.rmax, q.rmin, q.rows, q.cols), -1.0, 0.3, true));
+    }
+    // layers the chain wrote with plain weights: the sum of the scores (w_scale 1, weights 1 1 1) on a tie-free footprint
+    // of 15 cells, weights 10 10 10 at 9 cells, a negative weight (no bound), a default of 50 under the default weights --
+    // and the default weights at the same footprints, which keep their fixed-point kernels
+    named("fv_w1111_r15", with(base(15 * tf, 10 * tf, 96, 80), 3.0, 0.3));
+    named("fv_w1111_r15_batch2", with(base(15 * tf, 10 * tf, 96, 80, 2), 3.0, 0.3));
+    named("fv_w1111_r15_region", [&] {  // te_run_chain_region(0, 21, 17, 31, 27): grown by 8 (the gap), 3 (the mask) and the reach
+      Case c = with(base(15 * tf, 10 * tf, 96, 80), 3.0, 0.3);
+      c.region = true;
+      c.i0 = 0;
+      c.i1 = 78;
+      c.j0 = 0;
+      c.j1 = 70;
+      return c;
+    }());
+    named("fv_w1_10_r9", with(base(9 * tf, 6 * tf, 96, 80), 30.0, 0.3));
+    named("fv_wneg_r9", with(base(9 * tf, 6 * tf, 96, 80), -1.0, 0.3));
+    named("fv_def50_chain_r5", with(base(5 * tf, 3 * tf, 96, 80), (double)(1.0f / 3.0f) * 3.0, 50.0));
+    named("fv_wdefault_r15", base(15 * tf, 10 * tf, 96, 80));
+    named("fv_wdefault_r9", base(9 * tf, 6 * tf, 96, 80));
+    // the boundary of the packed sums on a chain-written layer: the general kernel at reach 18 (1085 cells) with a bound
+    // just below and just above 2048 / 1085
+    named("fv_bound_below_reach18", with(base(18.5, 12.0, 96, 80), 1.88, 0.3));
+    named("fv_bound_above_reach18", with(base(18.5, 12.0, 96, 80), 1.89, 0.3));
+    // fixed point at saturation: w_scale (float) with weights 1 1 1 -- the largest that still gives k = 23 .. 17 and the first
+    // that gives 16 -- for k_fp_slide5 at its largest disc (Q = 250, 793 cells) and k_fp_slide4 at the radii 15 and 16; the
+    // default is the cap itself
+    const struct { const char* name; double rmax, rmin; float s17, s16; } sats[] = {
+        {"sat5", std::sqrt(250.0) * tf, 10 * tf, 0x1.b8c2a2p-2f, 0x1.b8c2a4p-2f},
+        {"sat4_15", 15.0, 10.0, 0x1.6057d4p+0f, 0x1.6057d6p+0f},
+        {"sat4_16", 16.0, 10.0, 0x1.4afd28p+0f, 0x1.4afd2ap+0f},
+    };
+    for (const auto& q : sats) {
+      for (int k = 23; k >= 16; --k) {
+        const float sc = k == 16 ? q.s16 : std::ldexp(q.s17, 17 - k);
+        const double tcap = (double)sc * 3.0;
+        snprintf(name, sizeof(name), "fv_%s_k%d", q.name, k);
+        named(name, with(base(q.rmax, q.rmin, 96, 80), tcap, tcap));
+      }
+      // the cap is the default: small weights (a layer below 0.3), fp_default at the k = 17 cap
+      snprintf(name, sizeof(name), "fv_%s_defcap", q.name);
+      named(name, with(base(q.rmax, q.rmin, 96, 80), (double)0.1f * 3.0, (double)q.s17 * 3.0));
+    }
     return 0;
   }
   if (argc == 4 && !strcmp(argv[1], "sweep")) {
@@ -235,6 +307,10 @@ int main(int argc, char** argv) {
     printf("%d cases, %d failed checks\n", n, failed);
     return failed != 0;
   }
-  fprintf(stderr, "usage: %s cases | sweep N SEED\n", argv[0]);
+  if (argc >= 2 && !strcmp(argv[1], "constants")) {  // what tests/footprint_value_cases.py restates, from the header itself
+    printf("kFpUOff %.17g\n", (double)kFpUOff);
+    return 0;
+  }
+  fprintf(stderr, "usage: %s cases | sweep N SEED | constants\n", argv[0]);
   return 2;
 }

@@ -3,13 +3,16 @@ is compiled from traversability_estimation_amd/csrc/te_fp_route.h -- the header 
 its inputs from te_fp_table.h, the tables the shim builds.  Every footprint row of DESIGN.md 4.7 is pinned by a named case
 here; a seeded sweep holds every route to what its kernels rely on (2R+1 <= 31 and a list that holds the reservations for
 k_fp_slide5, whole-cell ties for k_fp_slide4, k >= 17 for both, a map one wavefront wide and under 4 GiB, an instantiated
-shape).  A test that declines silently no longer sends a map to a slower kernel unnoticed: rows = 65 and 4033 did until
+shape, and for the two double kernels, which pack the untraversable count into the disc sum, a bound that keeps
+npoints * cap under kFpUOff / 2).  The cases of tests/test_gpu_footprint_values.py are pinned here too, with their k
+(tests/footprint_value_cases.py).  A test that declines silently no longer sends a map to a slower kernel unnoticed: rows = 65 and 4033 did until
 round 5."""
 import os
 import subprocess
 
 import pytest
 
+from tests import footprint_value_cases as fv
 from tests.conftest import ROOT
 
 # name: (route, k_fp_blocked follows)
@@ -17,8 +20,8 @@ CASES = {
     "cfg3": ("slide5", 1),                               # 4096^2, tie-free R = 9, the layer the chain wrote
     "cfg3_any_reach_option": ("any", 0),                 # TE_OPT_FP_ANY_REACH = 1
     "reference_045_at_003": ("slide4", 1),               # the reference's 0.45 m at 0.03 m: a whole-cell tie radius of 15 cells
-    "reference_045_at_003_uploaded": ("general", 0),     # ... on an uploaded layer (no bound: tcap < 0)
-    "tie_free_9_uploaded": ("slide3", 0),                # tie-free <= 16 on an uploaded layer
+    "reference_045_at_003_uploaded": ("any", 0),         # ... on an uploaded layer (no bound: tcap < 0): no packed sum
+    "tie_free_9_uploaded": ("any", 0),                   # tie-free <= 16 on an uploaded layer: likewise
     "tie_free_16": ("slide3", 0),                        # the tie-free 16-cell radius (2R+1 > 31)
     "reach_18": ("general", 0),                          # reach 17 .. 20
     "reach_20_tie": ("general", 0),
@@ -51,14 +54,42 @@ def exe(tmp_path_factory):
 def test_named_cases_take_their_rows_of_the_design(exe):
     r = subprocess.run([exe, "cases"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    got = {}
+    got, got_fv = {}, {}
     for line in r.stdout.split("\n"):
         if line:
             name, route, k, strip_rows, chunk, blocked = line.split()
-            got[name] = (route, int(blocked))
+            if name.startswith("fv_"):
+                got_fv[name] = (route, int(k))
+            else:
+                got[name] = (route, int(blocked))
             if route in ("slide4", "slide5"):
                 assert int(k) >= 17 and 1 <= int(strip_rows) <= 512 and int(chunk) in (64, 128, 256), line
     assert got == CASES
+    assert got_fv == fv.PLANNED  # the cases of tests/test_gpu_footprint_values.py: route and k
+
+
+def test_fixed_k_restatement_matches_the_harness(exe):
+    """fv.fp_fixed_k -- the three lines the GPU test takes its tolerance 2^-(k+1) from -- gives the k the harness prints,
+    at every saturation case: both sides of every step from 23 down to 16."""
+    r = subprocess.run([exe, "cases"], capture_output=True, text=True, timeout=120)
+    printed = {ln.split()[0]: (ln.split()[1], int(ln.split()[2])) for ln in r.stdout.split("\n") if ln.startswith("fv_sat")}
+    assert len(printed) == 27
+    for geo, (cells, limit, _, _) in fv.SAT.items():
+        for k in range(23, 15, -1):
+            tcap = fv.sat_scale(geo, k) * 3.0
+            assert fv.fp_fixed_k(cells, fv.fixed_cap(tcap, tcap), limit) == k, (geo, k)
+            route, kk = printed[f"fv_{geo}_k{k}"]
+            assert (kk == k) if k >= 17 else (kk == -1 and route not in ("slide4", "slide5")), (geo, k, route, kk)
+        assert fv.fp_fixed_k(cells, fv.fixed_cap(0.3, fv.sat_scale(geo, 17) * 3.0), limit) == 17 == printed[f"fv_{geo}_defcap"][1]
+    assert fv.disc_cells("sat5") == fv.SAT["sat5"][0] and fv.disc_cells("r15") == 709 and fv.disc_cells("reach18") == 1085
+
+
+def test_restated_constant_is_the_header_s(exe):
+    """fv.K_UOFF, from which the GPU test's boundary family takes its two constants, is te_fp_route.h's kFpUOff."""
+    r = subprocess.run([exe, "constants"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    printed = dict(ln.split() for ln in r.stdout.split("\n") if ln)
+    assert float(printed["kFpUOff"]) == fv.K_UOFF
 
 
 @pytest.mark.parametrize("seed", [1, 2])

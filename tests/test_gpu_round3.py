@@ -1,6 +1,6 @@
 """Round-3 kernels and entry points against the oracle, through the C-ABI:
-the fixed-point footprint kernel (k_fp_slide4) over footprint radii and obstacle densities, the double kernel it falls
-back to for a traversability layer that was not written by the chain, the step filter's nCells shortcut, and
+the fixed-point footprint kernel (k_fp_slide4) over footprint radii and obstacle densities, the route it leaves them
+for when the traversability layer was not written by the chain, the step filter's nCells shortcut, and
 te_run_chain_region refusing a footprint flag it does not implement."""
 import numpy as np
 import pytest
@@ -52,7 +52,7 @@ def test_fixed_point_footprint_over_radii(capi, oracle, fp_cells, off_cells, box
 
 def test_footprint_of_an_uploaded_traversability_layer(capi, oracle):
     """A traversability layer that does not come from the chain is not bounded by the weights: values above 1 (and
-    NaN) must go through the double kernel, same result as the oracle's isTraversable on that layer."""
+    NaN) must not go through the fixed-point kernels, same result as the oracle's isTraversable on that layer."""
     from traversability_estimation_amd import synth
     rows, cols, res = 200, 170, 0.05
     elev = obstacle_map(synth, rows, cols, 77, 8)
@@ -62,7 +62,8 @@ def test_footprint_of_an_uploaded_traversability_layer(capi, oracle):
     g = oracle.geom(rows, cols, res)
     layers = oracle.chain(g, op, elev)
     rng = np.random.default_rng(5)
-    # (values up to ~4: the double kernel keeps the untraversable count apart from sums below 2048, i.e. 8 per cell here)
+    # (values up to ~4; a layer from outside has no bound and takes the route of any reach, which counts untraversable cells
+    # in integers -- values far beyond: tests/test_gpu_footprint_values.py)
     t = (layers["traversability"].astype(np.float64) * 3.0 + rng.uniform(0.0, 1.0, size=rows * cols)).astype(np.float32)
     t[rng.random(rows * cols) < 0.01] = np.nan
     layers["traversability"] = t

@@ -119,11 +119,13 @@ struct te_ctx {
   unsigned long long pd_clock = 0;  // (lmem.pd_tables)
   bool combine_deferred = false;
   // the traversability layer was written from outside (upload, device pointer, a per-plugin combine of uploaded scores):
-  // its values are then not bounded by the weights, and the fixed-point footprint kernel must not be used
+  // its values are then not bounded by the weights, and neither the fixed-point footprint kernels nor the double kernels,
+  // which pack the untraversable count into the sum, may be used (te_fp_route.h: the route of any reach)
   bool trav_external = false;
   // te_device_ptr handed out the traversability layer: the caller may write it at any time from then on, so only a
   // footprint pass that runs right behind a chain that rewrote EVERY cell (te_run_chain with the footprint flag) may
-  // still assume the bound; te_run_footprint and region runs take the double kernel.  Reset with the layers.
+  // still assume the bound; te_run_footprint and region runs plan without one and take the route of any reach
+  // (te_fp_route.h).  Reset with the layers.
   bool trav_ptr_out = false;
   // te_set_option: choices between kernels that give identical results (tests reach both; never read from the environment)
   int opt_fb_walk = 0, opt_fb_blocks_per_cu = 0, opt_polygon_per_cell = 0, opt_graph = 0, opt_bcast_rccl = 0, opt_rank_rule = 0,

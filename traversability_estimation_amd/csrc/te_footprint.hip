@@ -856,10 +856,10 @@ struct SpiralArgs {
 };
 
 // Ring encoding: one double per cell, T' + kUOff * U with T' = traversability (NaN -> default) and
-// U = 1 for an untraversable cell.  T' is a float in (-kUOff/2, kUOff/2) (scores live in [0, 1]), so
-// both the per-cell value and the disc sum  sum(T') + kUOff * sum(U)  are exact in double and split
-// back exactly:  sum(U) = floor((S + kUOff/2) / kUOff).
-constexpr double kUOff = 4096.0;
+// U = 1 for an untraversable cell.  The route plan (te_fp_route.h, fp_packed_ok) sends a pass here only under a bound
+// that keeps every T' and every disc's sum(T') within (-kUOff/2, kUOff/2), so both the per-cell value and the disc sum
+// sum(T') + kUOff * sum(U)  are exact in double and split back exactly:  sum(U) = floor((S + kUOff/2) / kUOff).
+constexpr double kUOff = fast::kFpUOff;
 constexpr int kFpHead = 24;  // spiral entries every lane walks on its own before the wavefront takes the long walks over
 constexpr int kFpWaves = 2;  // waves per SIMD k_fp_slide is compiled for; the launcher fills exactly these slots
 
@@ -1404,7 +1404,7 @@ hipError_t launch_footprint(const Geo& g, const FootprintParams& p, const Layers
   const fast::FpRoute r = fast::plan_fp_route(in);
   bool launched = true;
   switch (r.route) {
-    case fast::kFpAny:  // a reach above 20 cells (or TE_OPT_FP_ANY_REACH)
+    case fast::kFpAny:  // a reach above 20 cells, TE_OPT_FP_ANY_REACH, or a layer without the bound the double kernels need
       return launch_footprint_any(g, p, L, rfp, stream);
     case fast::kFpSlide5:  // tie-free disc, layer bounded: the scatter-form sum on fixed point
       launched = fast::footprint_slide5(g, p, L, clip_table, r, stream, rfp);

@@ -22,7 +22,7 @@ namespace {
 
 constexpr int kF3Waves = 3;
 constexpr int kF3Head = 24;  // spiral entries every lane walks on its own before the wavefront takes the long walks over
-constexpr double kUOff3 = 4096.0;  // as in te_footprint.hip: sums of T' stay below it, so sum(T') and sum(U) split exactly
+constexpr double kUOff3 = kFpUOff;  // as in te_footprint.hip: the route plan keeps the sums of T' below half of it (fp_packed_ok), so sum(T') and sum(U) split exactly
 
 struct F3Args {
   const float* trav;

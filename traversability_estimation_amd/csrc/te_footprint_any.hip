@@ -3,8 +3,9 @@
 //
 // The shape-specialised sum kernels (te_footprint*.hip) hold the disc in an LDS ring or in compile-time run tables and
 // serve reaches up to 20 cells.  This route serves every reach, from the tables of te_fp_table.h (runs, ties, spiral order;
-// clipped to the map), and is what launch_footprint picks above 20 cells or with TE_OPT_FP_ANY_REACH = 1.  The mask kernel
-// (k_fp_mask) runs before it, unchanged.
+// clipped to the map), and is what launch_footprint picks above 20 cells, with TE_OPT_FP_ANY_REACH = 1, or at any reach for
+// a traversability layer without the bound the double kernels need (te_fp_route.h fp_packed_ok: a layer written from
+// outside, a large or negative weight, a large default).  The mask kernel (k_fp_mask) runs before it, unchanged.
 //
 //   k_fpa_prefix  column prefix sums along the contiguous i axis, per map and column: P[i] = sum of T' over rows < i in
 //                 double (T' = traversability, traversability_default where it is not finite, :719-724) and C[i] = the
@@ -16,8 +17,9 @@
 //                 order (:687-717): 0 when radiusMin is 0 or the cell lies within it; an untraversable cell in the rings
 //                 that lie within radiusMin is found from C in O(R) (inner disc); else the wavefront walks the spiral
 //                 table from the end of the inner disc, 64 entries per step, one disc at a time.
-// The untraversable count is exact (integers) whatever the disc's size or the values of the traversability layer, and the
-// sum is in double as the reference's is.
+// The untraversable count is exact (integers) whatever the disc's size or the values of the traversability layer.  The sum
+// is in double, but as differences of a prefix that runs down the WHOLE column: its error is about 2^-52 times the column's
+// sum of |T'| per run, not local to the disc (include/travgpu.h, te_run_footprint, states the range this supports).
 #include "te_internal.h"
 
 #include "te_fp_table.h"

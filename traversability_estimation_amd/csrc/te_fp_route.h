@@ -28,6 +28,12 @@
 namespace te {
 namespace fast {
 
+// The double kernels (k_fp_slide3, k_fp_slide<R>) store one double per cell, T' + kFpUOff * U (T': the traversability value or
+// the default, U: 1 for an untraversable cell), sum it over the disc and split the sum again: the count of untraversable
+// cells is floor((S + kFpUOff / 2) / kFpUOff), a single cell is untraversable when its value reaches kFpUOff / 2.  Exact,
+// and right, while every |T'| and every disc's |sum T'| stay below kFpUOff / 2 -- which only a bound on the layer can
+// promise (fp_packed_ok); without one the pass takes the route of any reach, which counts U in integers.
+constexpr double kFpUOff = 4096.0;
 constexpr int kF5Waves = 5;                 // waves per SIMD k_fp_slide5 is compiled for
 constexpr int kF5UBit = 27;                 // k_fp_slide5's untraversable flag: a disc's fixed-point T-sum stays below it
 constexpr int kF4Waves = 4;                 // waves per SIMD k_fp_slide4 is compiled for
@@ -46,6 +52,15 @@ inline int fp_fixed_k(double cells, double cap, double limit) {
   int k = 23;
   while (k >= 0 && cells * (cap * ldexp(1.0, k) + 1.0) >= limit) --k;
   return k;
+}
+
+// The bound the double kernels need: `cells` values (the whole disc, the cells on its circle included) of magnitude at most
+// max(tcap, |def|) sum to less than kFpUOff / 2.  tcap: the bound of the finite values of a layer the chain wrote with
+// non-negative weights (they lie in [0, tcap]), < 0: none known; def: the value that replaces NaN, of either sign.
+inline bool fp_packed_ok(double cells, double tcap, double def) {
+  if (!(tcap >= 0.0) || !(fabs(def) <= 1.7976931348623157e308)) return false;
+  const double cap = (tcap > fabs(def) ? tcap : fabs(def)) * (1.0 + 1e-6) + 1e-12;
+  return cells * cap < 0.5 * kFpUOff;
 }
 
 // Entries of the list beyond one per cell: every block of k_fp_slide4 may leave one chunk unfinished, and a launch has
@@ -81,7 +96,7 @@ struct FpRouteIn {
   bool has_list, has_scratch;  // Layers::fp_blocked + fp_blocked_count, Layers::fp_scratch
   size_t list_cap;             // Layers::fp_blocked_cap
   int cus;                     // compute units of the device
-  bool any;                    // FootprintParams::any: the route of any reach
+  bool any;                    // FootprintParams::any: the route of any reach (asked for, or a reach above 20 cells)
   // measurement switches of the lab build (TE_NO_F3 / F4 / F5, TE_F4_NO_TIES, TE_F5_WAVES, TE_F5_MAX_STRIP,
   // TE_F4_BLOCKS_PER_CU, TE_F4_MIN_STRIP); the defaults are the shipped library's
   bool no_f3 = false, no_f4 = false, no_f5 = false, f4_no_ties = false;
@@ -150,6 +165,10 @@ inline FpRoute plan_fp_route(const FpRouteIn& in) {
         return FpRoute{kFpSlide4, k, sr, chunk, in.rmin != 0.0};
     }
   }
+  // The double kernels pack the untraversable count into the sum (kFpUOff): only under a bound that keeps the two apart.
+  // Every other layer -- uploaded, written by an expression or through te_device_ptr, combined with a negative or a large
+  // weight, a large default -- takes the route of any reach, whose count is an integer of its own.
+  if (!fp_packed_ok((double)in.npoints + (double)in.n_ties, in.tcap, in.def)) return FpRoute{kFpAny};
   // k_fp_slide3<Q> (double): tie-free, the spiral within the kernel's table registers
   if (!in.no_f3 && tie_free && fp_f3_shape(in.Q) && in.n_spiral <= ((int)(3.2 * (in.R + 1) * (in.R + 1) / 64) + 1) * 64)
     return FpRoute{kFpSlide3};

@@ -125,7 +125,8 @@ struct FootprintParams {
   double rmin, rmax, def, max_gap, crit_step;
   int check_rough;
   int n_spiral;      // entries of the ordered spiral table
-  // the route of any reach (te_footprint_any.hip): above 20 cells, or every reach with TE_OPT_FP_ANY_REACH = 1.  Its
+  // the route of any reach (te_footprint_any.hip): above 20 cells, every reach with TE_OPT_FP_ANY_REACH = 1, or (any == 0,
+  // the buffers built all the same) a layer without the bound the double kernels need (te_fp_route.h).  Its
   // tables (te_fp_table.h, clipped to the map) and the prefix-sum scratch are device buffers of the context, allocated
   // when the tables are rebuilt; fp_disc and the shape-specialised tables are not built for a reach above 20 cells.
   int any;              // 1: this route serves the pass

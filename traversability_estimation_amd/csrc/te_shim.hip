@@ -411,11 +411,26 @@ void release_fp_any(te_ctx* c) {
   clear_fp_any_ptrs(c);
 }
 
-// (device memory for the route of any reach: the only way its tables can fail)
+// (device memory for the route of any reach: the only way its tables can fail).  The message names what sent the pass
+// there: the reach, the option, or -- up to 20 cells -- a traversability layer without the bound the double kernels need.
 static int fp_any_alloc(te_ctx* c, DevBuf& buf, size_t bytes, const char* what) {
   if (buf.reserve(bytes, c->stream) == hipSuccess) return TE_OK;
-  return fail(TE_ERR_UNSUPPORTED, "footprint radius %.3g m is %d cells: its %s (%zu bytes) do not fit in device memory", c->fp.rmax,
-              c->fp.reach, what, bytes);
+  if (c->fp.reach > 20)
+    return fail(TE_ERR_UNSUPPORTED, "footprint radius %.3g m is %d cells: its %s (%zu bytes) do not fit in device memory", c->fp.rmax,
+                c->fp.reach, what, bytes);
+  if (c->opt_fp_any)
+    return fail(TE_ERR_UNSUPPORTED, "footprint with TE_OPT_FP_ANY_REACH: the %s of the route of any reach (%zu bytes) do not fit in device memory",
+                what, bytes);
+  return fail(TE_ERR_UNSUPPORTED,
+              "footprint: the traversability layer has no known bound (written from outside, or a large or negative weight or "
+              "default) and is summed on the route of any reach, whose %s (%zu bytes) do not fit in device memory",
+              what, bytes);
+}
+
+// bound of the combined layer the chain writes (scores lie in [0, 1]); < 0: none, a weight is negative
+static double weights_cap(float w_scale, float w_slope, float w_step, float w_rough) {
+  if (!(w_scale >= 0.0f && w_slope >= 0.0f && w_step >= 0.0f && w_rough >= 0.0f)) return -1.0;
+  return (double)w_scale * ((double)w_slope + (double)w_step + (double)w_rough);
 }
 
 // The tables of the route of any reach (te_footprint_any.hip) on the device: run half-widths, those of the inner disc (the
@@ -467,6 +482,19 @@ int build_fp_any_tables(te_ctx* c, const FpTable& t) {
   f.any_psum = prefix.as<double>();
   f.any_pcnt = (unsigned*)(prefix.as<char>() + cells * sizeof(double));
   return TE_OK;
+}
+
+// A footprint pass over a layer bounded by trav_cap (< 0: no bound known) is about to be launched: if the plan will send it
+// to the route of any reach for want of a bound (te_fp_route.h), that route's tables and prefix sums exist afterwards.
+// Never allocates for a pass right behind a whole-map chain (the only captured one): its bound is the weights' own, and
+// rebuild_footprint_tables_impl has built the tables for it.
+int ensure_fp_any(te_ctx* c, double trav_cap) {
+  const FootprintParams& f = c->fp;
+  if (f.any || f.any_psum) return TE_OK;
+  if (fast::fp_packed_ok((double)f.fp_disc.npoints + (double)f.fp_disc.n_ties, trav_cap, f.def)) return TE_OK;
+  FpTable any;
+  build_fp_table(f.rmax, c->geo.res, c->geo.rows, c->geo.cols, &any);
+  return build_fp_any_tables(c, any);
 }
 
 // Discs of the three footprint checks, SpiralIterator order and clip table of the circular footprint pass.  A failure is
@@ -543,7 +571,11 @@ int rebuild_footprint_tables_impl(te_ctx* c) {
     }
     HIP_TRY(hipMemcpyAsync(fp_clip_table, ctab.data(), ctab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (f.any) return build_fp_any_tables(c, any);  // TE_OPT_FP_ANY_REACH
+    // TE_OPT_FP_ANY_REACH -- or a layer of the chain's own that lacks the bound the double kernels need (te_fp_route.h: a
+    // large or negative weight, a large default): such a pass takes the route of any reach, and a captured launch cannot
+    // allocate.  A layer from outside gets the tables when a pass first meets it (ensure_fp_any).
+    if (f.any || !fast::fp_packed_ok((double)d.npoints + (double)d.n_ties, weights_cap(p.w_scale, p.w_slope, p.w_step, p.w_rough), f.def))
+      return build_fp_any_tables(c, any);
     release_fp_any(c);
   }
   return TE_OK;
@@ -743,6 +775,7 @@ int run_footprint_locked(te_ctx* c, unsigned flags, bool fresh = false) {
   const ChainParams& q = c->cp;
   const bool bounded = !c->trav_external && (fresh || !c->trav_ptr_out) && q.w_scale >= 0.0f && q.w_slope >= 0.0f && q.w_step >= 0.0f && q.w_rough >= 0.0f;
   const double trav_cap = bounded ? (double)q.w_scale * ((double)q.w_slope + (double)q.w_step + (double)q.w_rough) : -1.0;
+  if (int rc = ensure_fp_any(c, trav_cap)) return rc;
   HIP_TRY(launch_footprint(c->geo, c->fp, c->L, usable_face_flags(c), c->cmem.spiral.as<unsigned>(), c->cmem.fp_clip_table.as<int>(), (flags & TE_RUN_FOOTPRINT_MEMO) != 0,
                            c->combine_deferred ? &c->cp : nullptr, trav_cap, c->stream));
   c->combine_deferred = false;
@@ -1237,6 +1270,7 @@ int te_run_chain_region(te_ctx* c, unsigned flags, int map, int row0, int col0, 
   const ChainParams& q = c->cp;
   const bool bounded = !c->trav_external && !c->trav_ptr_out && q.w_scale >= 0.0f && q.w_slope >= 0.0f && q.w_step >= 0.0f && q.w_rough >= 0.0f;
   const double trav_cap = bounded ? (double)q.w_scale * ((double)q.w_slope + (double)q.w_step + (double)q.w_rough) : -1.0;
+  if (int rc2 = ensure_fp_any(c, trav_cap)) return rc2;
   HIP_TRY(launch_footprint(c->geo, c->fp, c->L, usable_face_flags(c), c->cmem.spiral.as<unsigned>(), c->cmem.fp_clip_table.as<int>(), (flags & TE_RUN_FOOTPRINT_MEMO) != 0, nullptr, trav_cap,
                            c->stream, &changed));
   c->footprint_done = true;  // complete before, refreshed where it could change
