@@ -54,6 +54,9 @@
  *                        <- the get_traversability service, TraversabilityEstimation.cpp:297-316:
  *                           GridMap::getSubmap(position, length) of the traversability map and toMessage(subMap, layers);
  *                           the rectangle of the requested layers is packed on the device and crosses PCIe in one transfer
+ *   te_run_median_fill / te_download_fill_mask
+ *                        <- gridMapFilters/MedianFillFilter (grid_map_filters; not in the reference tree: restated, see below),
+ *                           the hole filling a grid_map pipeline puts in front of the chain
  *
  * Data contract (identical to grid_map::Matrix = Eigen::MatrixXf): float32, COLUMN-major,
  * element (row i, col j) of map m at ptr[m*rows*cols + j*rows + i]; invalid cell = non-finite.
@@ -201,6 +204,10 @@ int te_get_params(te_ctx* ctx, te_params* p);
  * of the elevation, a failed prefetch, or a te_set_params that changed fp_critical_step -- until the next whole upload);
  * 0: never.  The layers are identical either way. */
 #define TE_OPT_FACE_FLAGS 9
+/* te_run_median_fill: 0 (default) the kernel the plan names (csrc/te_median_plan.h: the tile kernel while the window radius is
+ * at most 15 cells, the general kernel above), 1 the tile kernel wherever its window fits, 2 the general kernel always.  The
+ * layers are identical either way, bit for bit. */
+#define TE_OPT_MEDIAN_ROUTE 10
 int te_set_option(te_ctx* ctx, int option, int value);
 /* The face flags a footprint run would be given now (tests, diagnostics): batch x ceil(cols / 4) x ceil(rows / 64) bytes, the
  * flag of 64 cells along the rows fastest; `bytes` must be exactly that.  TE_ERR_NOT_READY while they are unknown or
@@ -749,6 +756,65 @@ int te_run_expression(te_ctx* ctx, const char* text, int out_layer);
  * (after `warmup` untimed ones), like te_time_chain_samples.  text = NULL times te_run_filter(TE_FILTER_COMBINE) the same way: the
  * weighted sum's own kernel, the yardstick of tools/expr_bench.py. */
 int te_time_expression_samples(te_ctx* ctx, const char* text, int warmup, int iters, float* ms);
+
+/* ---- gridMapFilters/MedianFillFilter on the device: hole filling in front of the chain ----
+ * grid_map_filters is neither in the reference tree nor vendored: like the image, occupancy and submap routes this contract is
+ * RESTATED from memory of the filter shipped with the ROS Noetic grid_map, and nothing in it is pinned by a vector the
+ * reference holds.  The yardstick of the tests is the same contract in numpy (tests/ref_py/median_fill_ref.py).
+ *   1. window radius in cells  r = (size_t)(radius / resolution): a double division, truncated, no rounding fix
+ *      (0.15 / 0.05 = 2.9999999999999996 gives 2);
+ *   2. window                  the square [i - r, i + r] x [j - r, j + r], each bound clamped to the map (not a disc);
+ *   3. median(window)          over the FINITE values of the input layer in the window (+-inf is left out like NaN): none -> NaN,
+ *      otherwise the value at index n / 2 of the sorted values -- the upper median, the larger one for n = 2, what
+ *      std::nth_element(begin, begin + n / 2, end) leaves there.  The result is one of the inputs bit for bit (where a window
+ *      holds -0.0 and +0.0 around the median rank the sign of the zero is unspecified upstream; here -0.0 sorts below +0.0);
+ *   4. fill mask               V = the cells finite in the input; C = V after k = num_erode_dilation_iterations erosions and
+ *      then k dilations with a 3 x 3 square, where cells outside the map do not vote (an erosion keeps a cell whose in-map
+ *      neighbours are all set, a dilation sets a cell with any in-map neighbour set); shouldFill(c) = some cell of C lies in
+ *      c's window of radius r_fill.  With k = 0: "the window holds a finite value";
+ *   5. per cell, reading only the input layer as it was before the call:
+ *        input not finite and shouldFill                        -> median(r_fill)
+ *        input finite, filter_existing_values and shouldFill    -> median(r_existing)   (radius 0: the identity)
+ *        otherwise                                              -> the input value, bits unchanged (a NaN outside the mask stays);
+ *   6. not built: the reuse of a fill_mask layer kept from an earlier update, and the debug layers.  Every call computes its mask.
+ * Defaults as remembered from upstream: fill_hole_radius 0.05, filter_existing_values false, existing_value_radius 0.0,
+ * num_erode_dilation_iterations 4.  Validation as configure(): radii finite and >= 0, iterations >= 0 (TE_ERR_BAD_PARAM + message). */
+typedef struct te_median_fill_params {
+  uint32_t size; /* sizeof(te_median_fill_params) */
+  uint32_t abi_version;
+  double fill_hole_radius;
+  int32_t filter_existing_values;
+  int32_t _pad0;
+  double existing_value_radius;
+  int32_t num_erode_dilation_iterations;
+  int32_t _pad1;
+} te_median_fill_params;
+int te_median_fill_params_default(te_median_fill_params* p);
+int te_median_fill_params_validate(const te_median_fill_params* p);
+/* out_layer = MedianFillFilter(in_layer) for maps [map0, map0 + nmaps) of the batch; the other maps are untouched.  Any two float
+ * layers of the context; the same layer in and out (the elevation filled in place) behaves as if the input had been copied
+ * first -- the copy is taken from device memory on first use, TE_ERR_UNSUPPORTED if it does not fit.  Exact: the result is
+ * identical run after run and between the two kernels (TE_OPT_MEDIAN_ROUTE).  Asynchronous on the context's stream unless
+ * out_layer is the elevation.
+ *   TE_ERR_NOT_READY: no geometry; an input layer that does not exist yet (an elevation never uploaded, the layers
+ *     te_run_expression refuses to read).  TE_ERR_INVALID_ARG: NULL, a layer id out of range or without memory
+ *     (traversability_x before te_run_polygon_footprint), a map range outside the batch.  TE_ERR_BAD_PARAM: the parameters.
+ *     TE_ERR_UNSUPPORTED: the general kernel on a map of 2^32 cells or more.
+ *   Afterwards the context holds what an upload of the same values into out_layer leaves.  TE_LAYER_ELEVATION: the pass of
+ *     te_upload_elevation has run over the NEW contents -- invalid cells, their runs and the face flags are recounted, so a
+ *     completely filled map takes the hole-free normals kernel and one that keeps holes takes their march -- the layer counts
+ *     as uploaded, chain and footprint results as stale.  Any other layer: as te_upload_layer (traversability: no known bound;
+ *     robot_slope: present; a score layer: the footprint mask is stale).
+ *   A prefetch in flight that writes either layer is joined first. */
+int te_run_median_fill(te_ctx* ctx, const te_median_fill_params* p, int in_layer, int out_layer, int map0, int nmaps);
+/* shouldFill (4.) of the last te_run_median_fill that covered `map`: rows * cols bytes (exactly `bytes`) of 0 / 1, column-major
+ * like the layers.  TE_ERR_NOT_READY before any such call and after every te_set_geometry. */
+int te_download_fill_mask(te_ctx* ctx, int map, unsigned char* out, size_t bytes);
+/* Measurement aid (tools/median_fill_bench.py): `iters` launches, one HIP event pair each, ms[k] = device time of the k-th after
+ * `warmup` untimed ones.  p != NULL: te_run_median_fill(p, in_layer, out_layer) over the whole batch, without the recount that
+ * follows a fill of the elevation (the input must survive the repeats: in_layer != out_layer is required).  p == NULL: a device
+ * copy of in_layer into out_layer, the fill's floor. */
+int te_time_median_fill_samples(te_ctx* ctx, const te_median_fill_params* p, int in_layer, int out_layer, int warmup, int iters, float* ms);
 
 const char* te_last_error(void);
 const char* te_version(void);

@@ -31,6 +31,7 @@ RUN_NORMALS_ONLY = 0x20
 OPT_FP_BLOCKED_WALK, OPT_FP_BLOCKED_BLOCKS_PER_CU, OPT_POLYGON_PER_CELL, OPT_GRAPH_REPLAY, OPT_BCAST_RCCL, OPT_NORMALS_RANK_RULE = 1, 2, 3, 4, 5, 6
 OPT_FP_ANY_REACH = 7  # circular footprint: 0 routes by reach (above 20 cells: the route of any reach), 1 that route always
 OPT_FACE_FLAGS = 9  # mask kernel of the footprint pass: 1 (default) skips the step-check staging on tiles the upload found without a vertical face, 0 never (identical layers)
+OPT_MEDIAN_ROUTE = 10  # te_run_median_fill: 0 by plan, 1 the tile kernel wherever its window fits, 2 the general kernel always (identical layers)
 OPT_FILTER_ANY_RADIUS = 8  # filter discs: 0 up to 32 cells (TE_ERR_UNSUPPORTED above), 1 any radius, 2 the route of any radius for every disc
 
 # every symbol include/travgpu.h declares (tests/test_cabi.py checks the library exports them all)
@@ -49,7 +50,9 @@ SYMBOLS = ["te_params_default", "te_params_validate", "te_device_count", "te_cre
            "te_download_occupancy", "te_download_occupancy_msg", "te_occupancy_msg_write", "te_occupancy_parse",
            "te_download_cloud", "te_download_cloud_msg", "te_cloud_msg_write", "te_cloud_parse", "te_cloud_field", "te_cloud_spans",
            "te_submap_geometry", "te_download_submap", "te_download_submap_msg",
-           "te_expr_check", "te_run_expression", "te_time_expression_samples"]
+           "te_expr_check", "te_run_expression", "te_time_expression_samples",
+           "te_median_fill_params_default", "te_median_fill_params_validate", "te_run_median_fill", "te_download_fill_mask",
+           "te_time_median_fill_samples"]
 MSG_MAX_NAME = 64
 OCCUPANCY_MAX_LAYERS = CLOUD_MAX_LAYERS = SUBMAP_MAX_LAYERS = 16
 POINTFIELD_FLOAT32 = 7
@@ -140,6 +143,13 @@ IMAGE_ENCODINGS = {"mono8": (1, 1), "8UC1": (1, 1), "mono16": (1, 2), "16UC1": (
 
 class TeExprInfo(C.Structure):
     _fields_ = [("n_instructions", C.c_int32), ("layer_mask", C.c_uint32), ("n_reductions", C.c_int32), ("stack_depth", C.c_int32)]
+
+
+class TeMedianFillParams(C.Structure):
+    """te_median_fill_params: the settings of a gridMapFilters/MedianFillFilter entry."""
+    _fields_ = [("size", C.c_uint32), ("abi_version", C.c_uint32), ("fill_hole_radius", C.c_double),
+                ("filter_existing_values", C.c_int32), ("_pad0", C.c_int32), ("existing_value_radius", C.c_double),
+                ("num_erode_dilation_iterations", C.c_int32), ("_pad1", C.c_int32)]
 
 
 class TePathCheckStats(C.Structure):
@@ -266,6 +276,12 @@ def load():
         L.te_expr_check.argtypes = [C.c_char_p, C.POINTER(TeExprInfo)]
         L.te_run_expression.argtypes = [vp, C.c_char_p, C.c_int]
         L.te_time_expression_samples.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        mp = C.POINTER(TeMedianFillParams)
+        L.te_median_fill_params_default.argtypes = [mp]
+        L.te_median_fill_params_validate.argtypes = [mp]
+        L.te_run_median_fill.argtypes = [vp, mp, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.te_download_fill_mask.argtypes = [vp, C.c_int, C.POINTER(C.c_ubyte), C.c_size_t]
+        L.te_time_median_fill_samples.argtypes = [vp, mp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.te_last_error.restype = C.c_char_p
         L.te_version.restype = C.c_char_p
         _lib = L
@@ -284,6 +300,22 @@ def default_params(**over):
         if not hasattr(p, k):
             raise KeyError(k)
         setattr(p, k, v)
+    return p
+
+
+def default_median_fill_params(**over):
+    """te_median_fill_params_default (fill_hole_radius 0.05, no filtering of existing values, 4 opening iterations), then `over`."""
+    p = TeMedianFillParams()
+    _check(load().te_median_fill_params_default(C.byref(p)))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def validate_median_fill_params(p):
+    _check(load().te_median_fill_params_validate(C.byref(p)))
     return p
 
 
@@ -657,6 +689,26 @@ class Context:
         """te_run_expression: `out` = text over the resident layers (any MathExpressionFilter expression of the language in
         include/travgpu.h); asynchronous like run_chain.  The context is then what upload_layer(out, the same values) leaves."""
         _check(load().te_run_expression(self._h, str(text).encode(), LAYERS[out] if isinstance(out, str) else int(out)))
+
+    def run_median_fill(self, params=None, layer="elevation", out=None, map0=0, nmaps=None):
+        """gridMapFilters/MedianFillFilter on the device (te_run_median_fill): `out` (default: `layer`, in place) = the filled `layer`."""
+        p = default_median_fill_params() if params is None else params
+        lid = lambda name: LAYERS[name] if isinstance(name, str) else int(name)
+        nmaps = self.batch - map0 if nmaps is None else nmaps
+        _check(load().te_run_median_fill(self._h, C.byref(p), lid(layer), lid(layer if out is None else out), int(map0), int(nmaps)))
+
+    def download_fill_mask(self, map_index=0):
+        """(cols, rows) uint8: shouldFill of the last run_median_fill that covered the map."""
+        out = np.empty((self.cols, self.rows), np.uint8)
+        _check(load().te_download_fill_mask(self._h, int(map_index), out.ctypes.data_as(C.POINTER(C.c_ubyte)), out.size))
+        return out
+
+    def time_median_fill_samples(self, params, layer="elevation", out="traversability_roughness", warmup=3, iters=50):
+        """Device time of each of `iters` fills (params=None: device copies of the layer, the fill's floor), in ms."""
+        ms = (C.c_float * int(iters))()
+        _check(load().te_time_median_fill_samples(self._h, None if params is None else C.byref(params), LAYERS[layer], LAYERS[out],
+                                                  int(warmup), int(iters), ms))
+        return np.array(ms[:], dtype=np.float64)
 
     def time_expression_samples(self, text, warmup=3, iters=50):
         """Device ms of `iters` run_expression(text) launches, one event pair each; text=None times run_filter("combine")."""

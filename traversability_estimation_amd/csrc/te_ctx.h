@@ -84,6 +84,11 @@ struct te_ctx {
     // te_run_expression (te_expr.hip): the per-block partials of its reductions and, behind them, the folded results per
     // (map, reduction); grown
     te::DevBuf expr_scratch;
+    // te_run_median_fill (te_median.hip), each allocated when a call first needs it: the shouldFill mask of the last call,
+    // one byte per cell of the batch (te_download_fill_mask; which maps hold one: fill_mask_valid); the two scratch masks of
+    // its mask passes, behind each other; the copy of the input layer a call with in_layer == out_layer reads; the general
+    // route's counts and list
+    te::DevBuf median_mask, median_tmp, median_copy, median_any;
     // the circular footprint at any reach (te_footprint_any.hip): its tables and its prefix-sum scratch ([batch][cols][rows + 1]
     // doubles, then as many unsigned), allocated when the footprint tables are rebuilt for that route; c->fp.any_* point into them
     struct FpAny {
@@ -135,6 +140,10 @@ struct te_ctx {
   // uploaded by rebuild_tables (never inside a launch: whole-map launches are captured)
   int opt_filter_any = 0;
   te::DiscTable fa_host[4];
+  // TE_OPT_MEDIAN_ROUTE (te_median_plan.h), and per map of the batch whether lmem.median_mask holds the mask of a
+  // te_run_median_fill (empty: of none; cleared by every te_set_geometry)
+  int opt_median_route = 0;
+  std::vector<uint8_t> fill_mask_valid;
   // invalid cells of the elevation layer as of the last whole upload (-1: unknown -- tiles, device pointer): see sparse_holes()
   long long invalid_cells = -1;
   long long invalid_runs = -1;  // runs of invalid cells in memory order (k_count_invalid); meaningful with invalid_cells >= 0

@@ -1,0 +1,201 @@
+// te_median_api.hip -- C-ABI of te_run_median_fill / te_download_fill_mask (include/travgpu.h: MedianFillFilter on the device).
+// The plan: te_median_plan.h; the selection: te_median.h; the kernels: te_median.hip.  The context: te_ctx.h.
+#include "te_ctx.h"
+#include "te_median_launch.h"
+
+using namespace te;
+using namespace te::shim;
+
+namespace {
+
+// the layers a call may read: as te_run_expression sees them, and an elevation that was uploaded
+int input_layer(const char* who, te_ctx* c, int id, const float** out) {
+  constexpr unsigned optional = bit(TE_LAYER_NORMAL_X) | bit(TE_LAYER_NORMAL_Y) | bit(TE_LAYER_NORMAL_Z) | bit(TE_LAYER_SLOPE_FOOTPRINT) |
+                                bit(TE_LAYER_STEP_FOOTPRINT) | bit(TE_LAYER_ROUGHNESS_FOOTPRINT) | bit(TE_LAYER_TRAVERSABILITY_X) |
+                                bit(TE_LAYER_TRAVERSABILITY_ROT);
+  if (id < 0 || id >= TE_LAYER_COUNT) return fail(TE_ERR_INVALID_ARG, "%s: bad input layer %d", who, id);
+  const float* ptr = layer_ptr(c, id);
+  const bool written = id == TE_LAYER_TRAVERSABILITY_X || id == TE_LAYER_TRAVERSABILITY_ROT || (c->layers_written & bit(id));
+  const bool absent = !ptr || ((bit(id) & optional) && !written) || (id == TE_LAYER_ROBOT_SLOPE && !c->have_robot_slope) ||
+                      (id == TE_LAYER_ELEVATION && !c->have_elev);
+  if (absent) return fail(TE_ERR_NOT_READY, "%s: the input layer %d does not exist yet", who, id);
+  *out = ptr;
+  return TE_OK;
+}
+
+int reserve(const char* who, DevBuf& b, size_t bytes, hipStream_t stream, const char* what) {
+  const hipError_t e = b.reserve(bytes, stream);
+  if (e != hipSuccess) return fail(TE_ERR_UNSUPPORTED, "%s: %s (%zu bytes) does not fit in device memory: %s", who, what, bytes, hipGetErrorString(e));
+  return TE_OK;
+}
+
+struct Call {
+  median::Args a;
+  median::Plan plan;
+};
+
+// checks, scratch and plan of one call; caller holds the lock and has made the device current.  With in_layer == out_layer
+// the kernels read a copy of the input, queued here.
+int prepare(const char* who, te_ctx* c, const te_median_fill_params* p, int in_layer, int out_layer, int map0, int nmaps, Call* call) {
+  if (!c->have_geo) return fail(TE_ERR_NOT_READY, "%s: geometry not set", who);
+  if (out_layer < 0 || out_layer >= TE_LAYER_COUNT) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
+  if (map0 < 0 || nmaps <= 0 || map0 > c->geo.batch - nmaps) return fail(TE_ERR_INVALID_ARG, "%s: maps [%d,%d) of batch %d", who, map0, map0 + nmaps, c->geo.batch);
+  const float* in = nullptr;
+  if (const int rc = input_layer(who, c, in_layer, &in)) return rc;
+  if (out_layer != TE_LAYER_ROBOT_SLOPE && !layer_ptr(c, out_layer))
+    return fail(TE_ERR_INVALID_ARG, "%s: the output layer %d has no memory yet", who, out_layer);
+  if (in_layer != out_layer)
+    if (const int rc = ensure_input_layer(c, out_layer)) return rc;  // (robot_slope exists from its first write on)
+  float* const out = layer_ptr(c, out_layer);
+
+  const int rows = c->geo.rows, cols = c->geo.cols;
+  const size_t cells = (size_t)rows * cols, total = cells * (size_t)nmaps;
+  const int r_fill = median::radius_cells(p->fill_hole_radius, c->geo.res, rows, cols);
+  int r_exist = -1;
+  if (p->filter_existing_values) {
+    r_exist = median::radius_cells(p->existing_value_radius, c->geo.res, rows, cols);
+    if (r_exist == 0) r_exist = -1;  // the median of a finite cell's window of one cell is the cell
+  }
+  const median::Plan plan = median::plan(rows, cols, nmaps, std::max(r_fill, r_exist), c->opt_median_route);
+  if (plan.route == median::kRouteAny && cells >= ((size_t)1 << 32))
+    return fail(TE_ERR_UNSUPPORTED, "%s: a window radius of %d cells takes the general kernel, which lists cells in 32 bits: %zu cells per map are too many", who, plan.r, cells);
+
+  te_ctx::LayerMem& m = c->lmem;
+  const float* in_first = in + cells * map0;  // the first map of the call
+  const size_t batch_cells = cells * (size_t)c->geo.batch;
+  if (const int rc = reserve(who, m.median_mask, batch_cells, c->stream, "the fill mask")) return rc;
+  if (const int rc = reserve(who, m.median_tmp, 2 * batch_cells, c->stream, "the scratch masks")) return rc;
+  if (plan.route == median::kRouteAny)
+    if (const int rc = reserve(who, m.median_any, (median::any_blocks(cells) + 1 + cells) * sizeof(unsigned), c->stream, "the list of cells")) return rc;
+  if (in_layer == out_layer) {
+    if (const int rc = reserve(who, m.median_copy, c->layer_elems * sizeof(float), c->stream, "the copy of the input layer")) return rc;
+    HIP_TRY(hipMemcpyAsync(m.median_copy.p, in_first, total * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    in_first = m.median_copy.as<float>();
+  }
+  median::Args& a = call->a;
+  a.in = in_first;
+  a.out = out + cells * map0;
+  a.mask = m.median_mask.as<uint8_t>() + cells * map0;
+  a.tmp[0] = m.median_tmp.as<uint8_t>();
+  a.tmp[1] = m.median_tmp.as<uint8_t>() + batch_cells;
+  a.any_counts = m.median_any.as<unsigned>();
+  a.any_list = a.any_counts ? a.any_counts + median::any_blocks(cells) + 1 : nullptr;
+  a.rows = rows;
+  a.cols = cols;
+  a.nmaps = nmaps;
+  a.r_fill = r_fill;
+  a.r_exist = r_exist;
+  a.iterations = p->num_erode_dilation_iterations;
+  call->plan = plan;
+  return TE_OK;
+}
+
+// the context's facts about a layer the fill has written: those of an upload of the same values (te_upload_elevation /
+// te_upload_layer); caller holds the lock
+int note_written(te_ctx* c, int out_layer) {
+  if (out_layer == TE_LAYER_ELEVATION) {
+    c->chain_done = false;
+    c->footprint_done = false;
+    c->mask_done = false;
+    // the pass of an elevation upload over the whole layer: invalid cells, their runs, the face flags (it waits for the fill)
+    if (const int rc = count_invalid_elevation(c)) return rc;
+    c->have_elev = true;
+  }
+  if (out_layer == TE_LAYER_ROBOT_SLOPE) c->have_robot_slope = true;
+  if (out_layer == TE_LAYER_TRAVERSABILITY) c->trav_external = c->trav_ptr_out = true;
+  if (out_layer == TE_LAYER_SLOPE || out_layer == TE_LAYER_STEP || out_layer == TE_LAYER_ROUGHNESS) c->mask_done = false;  // (the mask reads them)
+  return TE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int te_median_fill_params_default(te_median_fill_params* p) {
+  if (!p) return fail(TE_ERR_INVALID_ARG, "te_median_fill_params_default: NULL");
+  memset(p, 0, sizeof(*p));
+  p->size = (uint32_t)sizeof(te_median_fill_params);
+  p->abi_version = TE_ABI_VERSION;
+  // grid_map_filters MedianFillFilter::configure(), as remembered (travgpu.h)
+  p->fill_hole_radius = 0.05;
+  p->filter_existing_values = 0;
+  p->existing_value_radius = 0.0;
+  p->num_erode_dilation_iterations = 4;
+  return TE_OK;
+}
+
+int te_median_fill_params_validate(const te_median_fill_params* p) {
+  if (!p) return fail(TE_ERR_INVALID_ARG, "te_median_fill_params: NULL");
+  if (p->size != sizeof(te_median_fill_params) || p->abi_version != TE_ABI_VERSION)
+    return fail(TE_ERR_INVALID_ARG, "te_median_fill_params: size/abi mismatch (got %u/%u, want %zu/%d)", p->size, p->abi_version, sizeof(te_median_fill_params),
+                TE_ABI_VERSION);
+  if (!(p->fill_hole_radius >= 0.0) || !isfinite(p->fill_hole_radius)) return fail(TE_ERR_BAD_PARAM, "MedianFillFilter: fill_hole_radius must be finite and not negative");
+  if (!(p->existing_value_radius >= 0.0) || !isfinite(p->existing_value_radius))
+    return fail(TE_ERR_BAD_PARAM, "MedianFillFilter: existing_value_radius must be finite and not negative");
+  if (p->num_erode_dilation_iterations < 0) return fail(TE_ERR_BAD_PARAM, "MedianFillFilter: num_erode_dilation_iterations must not be negative");
+  return TE_OK;
+}
+
+int te_run_median_fill(te_ctx* c, const te_median_fill_params* p, int in_layer, int out_layer, int map0, int nmaps) {
+  if (!c || !p) return fail(TE_ERR_INVALID_ARG, "te_run_median_fill: NULL");
+  if (const int rc = te_median_fill_params_validate(p)) return rc;
+  TraceRange tr("te_run_median_fill");
+  CtxLock lk(c, /*beside_prefetch*/ true, bit(in_layer) | bit(out_layer));
+  Call call;
+  if (c->have_geo) HIP_TRY(hipSetDevice(c->device));
+  if (const int rc = prepare("te_run_median_fill", c, p, in_layer, out_layer, map0, nmaps, &call)) return rc;
+  HIP_TRY(median::launch(call.a, call.plan, c->stream));
+  if (c->fill_mask_valid.size() != (size_t)c->geo.batch) c->fill_mask_valid.assign((size_t)c->geo.batch, 0);
+  for (int m = map0; m < map0 + nmaps; ++m) c->fill_mask_valid[(size_t)m] = 1;
+  return note_written(c, out_layer);
+}
+
+int te_download_fill_mask(te_ctx* c, int map, unsigned char* out, size_t bytes) {
+  if (!c || !out) return fail(TE_ERR_INVALID_ARG, "te_download_fill_mask: NULL");
+  CtxLock lk(c);
+  if (!c->have_geo) return fail(TE_ERR_NOT_READY, "te_download_fill_mask: geometry not set");
+  if (map < 0 || map >= c->geo.batch) return fail(TE_ERR_INVALID_ARG, "te_download_fill_mask: map %d of batch %d", map, c->geo.batch);
+  if (c->fill_mask_valid.size() != (size_t)c->geo.batch || !c->fill_mask_valid[(size_t)map] || !c->lmem.median_mask.p)
+    return fail(TE_ERR_NOT_READY, "te_download_fill_mask: no te_run_median_fill has covered map %d under this geometry", map);
+  const size_t cells = (size_t)c->geo.rows * c->geo.cols;
+  if (bytes != cells) return fail(TE_ERR_INVALID_ARG, "te_download_fill_mask: %zu bytes given, the mask is %zu", bytes, cells);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(out, c->lmem.median_mask.as<uint8_t>() + cells * (size_t)map, cells, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return TE_OK;
+}
+
+int te_time_median_fill_samples(te_ctx* c, const te_median_fill_params* p, int in_layer, int out_layer, int warmup, int iters, float* ms) {
+  if (!c || !ms || iters <= 0 || warmup < 0) return fail(TE_ERR_INVALID_ARG, "te_time_median_fill_samples: bad argument");
+  if (in_layer == out_layer) return fail(TE_ERR_INVALID_ARG, "te_time_median_fill_samples: the input layer must survive the repeats (in_layer == out_layer)");
+  te_median_fill_params q;
+  te_median_fill_params_default(&q);
+  if (p) {
+    if (const int rc = te_median_fill_params_validate(p)) return rc;
+    q = *p;
+  }
+  CtxLock lk(c);
+  if (c->have_geo) HIP_TRY(hipSetDevice(c->device));
+  Call call;
+  if (const int rc = prepare("te_time_median_fill_samples", c, &q, in_layer, out_layer, 0, c->have_geo ? c->geo.batch : 1, &call)) return rc;
+  const size_t bytes = (size_t)c->geo.rows * c->geo.cols * (size_t)c->geo.batch * sizeof(float);
+  for (int k = -warmup; k < iters; ++k) {
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    if (p)
+      HIP_TRY(median::launch(call.a, call.plan, c->stream));
+    else
+      HIP_TRY(hipMemcpyAsync(call.a.out, call.a.in, bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(hipEventSynchronize(c->ev1));
+    float t = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&t, c->ev0, c->ev1));
+    if (k >= 0) ms[k] = t;
+  }
+  // out_layer now holds the fill (or the copy): the facts of an upload of those values
+  if (p) {
+    c->fill_mask_valid.assign((size_t)c->geo.batch, 1);
+  }
+  return note_written(c, out_layer);
+}
+
+}  // extern "C"

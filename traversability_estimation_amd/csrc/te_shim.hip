@@ -670,6 +670,7 @@ void free_layers(te_ctx* c) {
   clear_fp_any_ptrs(c);
   c->face_crit = __builtin_nan("");
   c->elev_ptr_out = false;
+  c->fill_mask_valid.clear();  // (lmem.median_mask is gone)
   guard_cache_generation().fetch_add(1, std::memory_order_acq_rel);  // (layer_has_guard_rows: verdicts about freed memory)
   c->layers_written = 0;
   c->have_robot_slope = false;
@@ -1097,6 +1098,10 @@ int te_set_option(te_ctx* c, int option, int value) {
       if (value < 0 || value > 1) return fail(TE_ERR_INVALID_ARG, "te_set_option: TE_OPT_FACE_FLAGS takes 0 (never passed to the mask kernel) or 1 (passed when known)");
       c->opt_face_flags = value;  // (identical layers either way: nothing computed so far is invalidated)
       break;
+    case TE_OPT_MEDIAN_ROUTE:
+      if (value < 0 || value > 2) return fail(TE_ERR_INVALID_ARG, "te_set_option: TE_OPT_MEDIAN_ROUTE takes 0 (by plan), 1 (the tile kernel wherever its window fits), 2 (the general kernel)");
+      c->opt_median_route = value;
+      return TE_OK;  // (read by te_run_median_fill alone, which is never captured; identical layers either way)
     case TE_OPT_NORMALS_RANK_RULE:
       c->opt_rank_rule = value != 0;
       c->chain_done = false;
@@ -1195,6 +1200,7 @@ int te_set_geometry(te_ctx* c, int rows, int cols, int batch, double res, double
   c->chain_done = false;
   c->footprint_done = false;
   c->mask_done = false;
+  c->fill_mask_valid.clear();  // (te_download_fill_mask: the mask of a fill under another geometry is not this map's)
   return rebuild_tables(c);
 }
 

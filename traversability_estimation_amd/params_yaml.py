@@ -212,3 +212,49 @@ def params_and_expression_from_yaml(capi, filter_yaml, footprint_yaml=None, robo
     capi.validate_params(p)
     capi.expr_check(text)
     return p, (capi.RUN_KEEP_NORMALS if keep else 0), text
+
+
+MEDIAN_FILL_TYPE = "gridMapFilters/MedianFillFilter"
+_MEDIAN_FILL_KEYS = {"input_layer", "output_layer", "fill_hole_radius", "filter_existing_values", "existing_value_radius",
+                     "num_erode_dilation_iterations", "fill_mask_layer", "debug"}
+
+
+def median_fill_from_yaml(path_or_dict, resolution=None):
+    """The settings of a `gridMapFilters/MedianFillFilter` entry -- the hole filling a grid_map pipeline puts in front of the
+    chain -- or None when the file has none.  Looked for in every filter list of the document (a list of entries with `type`),
+    `traversability_map_filters` among them; more than one entry is refused, and so is a key the filter does not have.  Keys
+    and defaults as remembered from grid_map_filters (include/travgpu.h states the contract): fill_hole_radius 0.05,
+    filter_existing_values false, existing_value_radius 0.0, num_erode_dilation_iterations 4; input_layer is required,
+    output_layer defaults to it.  `fill_mask_layer` and `debug` are accepted and dropped: every call computes its mask, and
+    the debug layers are not built.  With `resolution` the two radii also come in cells (`fill_hole_cells`,
+    `existing_value_cells`: int(radius / resolution), the filter's own truncation).
+    The dict's four parameters are the fields of capi.default_median_fill_params(**...)."""
+    doc = path_or_dict if isinstance(path_or_dict, (dict, list)) else _load(path_or_dict)
+    lists = [doc] if isinstance(doc, list) else [v for v in (doc or {}).values() if isinstance(v, list)]
+    found = [f for lst in lists for f in lst if isinstance(f, dict) and str(f.get("type")) == MEDIAN_FILL_TYPE]
+    if not found:
+        return None
+    if len(found) > 1:
+        raise ParamsYamlError(f"{len(found)} MedianFillFilter entries: one fill in front of the chain is what is built")
+    prm = found[0].get("params") or {}
+    unknown = set(prm) - _MEDIAN_FILL_KEYS
+    if unknown:
+        raise ParamsYamlError(f"MedianFillFilter: unknown parameter(s) {sorted(unknown)}")
+    if "input_layer" not in prm:
+        raise ParamsYamlError("MedianFillFilter did not find param input_layer")
+    out = {"input_layer": str(prm["input_layer"]), "output_layer": str(prm.get("output_layer", prm["input_layer"])),
+           "fill_hole_radius": float(prm.get("fill_hole_radius", 0.05)),
+           "filter_existing_values": 1 if prm.get("filter_existing_values", False) else 0,
+           "existing_value_radius": float(prm.get("existing_value_radius", 0.0)),
+           "num_erode_dilation_iterations": int(prm.get("num_erode_dilation_iterations", 4))}
+    for k in ("fill_hole_radius", "existing_value_radius"):
+        if not (np.isfinite(out[k]) and out[k] >= 0.0):
+            raise ParamsYamlError(f"MedianFillFilter: {k} must be finite and not negative (got {out[k]})")
+    if out["num_erode_dilation_iterations"] < 0:
+        raise ParamsYamlError("MedianFillFilter: num_erode_dilation_iterations must not be negative")
+    if resolution is not None:
+        if not (np.isfinite(resolution) and resolution > 0.0):
+            raise ParamsYamlError(f"resolution must be positive (got {resolution})")
+        out["fill_hole_cells"] = int(out["fill_hole_radius"] / resolution)
+        out["existing_value_cells"] = int(out["existing_value_radius"] / resolution)
+    return out

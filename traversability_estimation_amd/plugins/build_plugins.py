@@ -14,8 +14,9 @@ IMAGE_TEST = os.path.join(HERE, "plugin_image_test")
 OUTPUT_TEST = os.path.join(HERE, "plugin_output_test")
 EXPRESSION_TEST = os.path.join(HERE, "plugin_expression_test")
 SUBMAP_TEST = os.path.join(HERE, "plugin_submap_test")
+MEDIAN_TEST = os.path.join(HERE, "plugin_median_test")
 SRCS = ["src/DeviceMap.cpp", "src/SlopeFilter.cpp", "src/StepFilter.cpp", "src/RoughnessFilter.cpp",
-        "src/FusedChainFilter.cpp", "src/SurfaceNormalsFilter.cpp", "src/TraversabilityMap.cpp", "stubs/pluginlib/registry.cpp"]
+        "src/FusedChainFilter.cpp", "src/SurfaceNormalsFilter.cpp", "src/MedianFillFilter.cpp", "src/TraversabilityMap.cpp", "stubs/pluginlib/registry.cpp"]
 
 
 def build(verbose=False):
@@ -67,6 +68,12 @@ def build(verbose=False):
     # (the driver parses the message with te_msg_parse / te_msg_layer itself: it names libtravgpu.so on its own line)
     cmd = cmd[:cmd.index("-o")] + ["-L" + PKG, "-ltravgpu", "-o", SUBMAP_TEST]
     cmd[cmd.index(os.path.join(HERE, "test", "plugin_expression_test.cpp"))] = os.path.join(HERE, "test", "plugin_submap_test.cpp")
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    # traversabilityFilters/MedianFillFilter and TraversabilityMap::setFillHoles (tests/test_plugins_median.py)
+    cmd = cmd[:cmd.index("-o")] + ["-o", MEDIAN_TEST]
+    cmd[cmd.index(os.path.join(HERE, "test", "plugin_submap_test.cpp"))] = os.path.join(HERE, "test", "plugin_median_test.cpp")
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

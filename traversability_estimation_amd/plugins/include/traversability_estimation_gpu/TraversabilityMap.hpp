@@ -53,6 +53,11 @@ class TraversabilityMap {
                              double minHeight, double maxHeight);
   /*! computeTraversability (:202-237): the filter chain; false if no elevation map has been set. */
   bool computeTraversability();
+  /*! Hole filling in front of the chain (gridMapFilters/MedianFillFilter on the device, te_run_median_fill): with parameters
+   *  set, computeTraversability() first fills the resident elevation layer in place -- once per elevation map -- and the chain
+   *  then sees a layer without the holes that had observed neighbours.  NULL switches it off again (the default).  false (and
+   *  nothing changed) for parameters te_median_fill_params_validate refuses. */
+  bool setFillHoles(const te_median_fill_params* params);
   /*! traversabilityFootprint(radius, offset) (:307-318): layer traversability_footprint. */
   bool traversabilityFootprint(const double& radius, const double& offset);
   /*! traversabilityFootprint(footprintYaw) (:239-305): layers traversability_x / traversability_rot. */
@@ -102,6 +107,8 @@ class TraversabilityMap {
   mutable std::mutex mutex_;
   te_ctx* ctx_;
   te_params params_;
+  te_median_fill_params fillParams_;
+  bool fillHoles_, elevationFilled_;  // setFillHoles; the resident elevation has been filled with fillParams_
   std::vector<geometry_msgs::Point32> footprintPoints_;
   grid_map::GridMap geometry_;  // geometry and start index of the last elevation map (no layers)
   bool elevationMapInitialized_, traversabilityMapInitialized_, footprintLayer_, polygonLayers_;

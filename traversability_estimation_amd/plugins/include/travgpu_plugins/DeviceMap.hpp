@@ -48,6 +48,8 @@ class DeviceMap {
   bool runChain(unsigned flags);
   /*! traversability = text over the resident layers (te_run_expression), behind runChain. */
   bool runExpression(const std::string& text);
+  /*! out_layer = MedianFillFilter(in_layer) on the device (te_run_median_fill); what a plugin uploaded into out_layer is gone. */
+  bool runMedianFill(const te_median_fill_params& params, int in_layer, int out_layer);
   bool download(grid_map::GridMap& map, const std::string& layer, int te_layer);
   const std::string& error() const { return error_; }
 

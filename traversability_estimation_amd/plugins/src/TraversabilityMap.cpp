@@ -22,6 +22,8 @@ TraversabilityMap::TraversabilityMap(int device)
       footprintOffset_(-1.0),
       circularFootprintOffset_(0.15) {
   te_params_default(&params_);
+  te_median_fill_params_default(&fillParams_);
+  fillHoles_ = elevationFilled_ = false;
   // (the reference's filters take any radius: TE_OPT_FILTER_ANY_RADIUS = 1)
   if (check(te_create(device, &ctx_))) {
     if (check(te_set_option(ctx_, TE_OPT_FILTER_ANY_RADIUS, 1))) {
@@ -89,6 +91,7 @@ bool TraversabilityMap::setElevationMap(const grid_map::GridMap& elevationMap) {
   geometry_.setGeometry(elevationMap.getLength(), elevationMap.getResolution(), elevationMap.getPosition());
   geometry_.setStartIndex(start);
   elevationMapInitialized_ = true;
+  elevationFilled_ = false;
   traversabilityMapInitialized_ = false;
   footprintLayer_ = polygonLayers_ = false;
   return true;
@@ -133,8 +136,22 @@ bool TraversabilityMap::setElevationFromImage(const sensor_msgs::Image& image, d
   length(1) = resolution * info.width;
   geometry_.setGeometry(length, resolution, position);
   elevationMapInitialized_ = true;
+  elevationFilled_ = false;
   traversabilityMapInitialized_ = false;
   footprintLayer_ = polygonLayers_ = false;
+  return true;
+}
+
+bool TraversabilityMap::setFillHoles(const te_median_fill_params* params) {
+  std::lock_guard<std::mutex> lock(mutex_);
+  if (!params) {
+    fillHoles_ = false;
+    return true;
+  }
+  if (!check(te_median_fill_params_validate(params))) return false;
+  fillParams_ = *params;
+  fillHoles_ = true;
+  // (an elevation filled under other parameters stays as it is until the next elevation map: the fill reads its own output)
   return true;
 }
 
@@ -143,6 +160,14 @@ bool TraversabilityMap::computeTraversability() {
   if (!elevationMapInitialized_) {  // :228-231
     ROS_ERROR("Traversability Estimation: Elevation map is not initialized!");
     return false;
+  }
+  if (fillHoles_ && !elevationFilled_) {
+    if (!check(te_run_median_fill(ctx_, &fillParams_, TE_LAYER_ELEVATION, TE_LAYER_ELEVATION, 0, 1))) {
+      ROS_ERROR("Traversability Estimation: Could not fill the holes of the elevation map! No traversability computed!");
+      traversabilityMapInitialized_ = false;
+      return false;
+    }
+    elevationFilled_ = true;
   }
   if (!check(te_run_chain(ctx_, 0))) {  // :214-218
     ROS_ERROR("Traversability Estimation: Could not update the filter chain! No traversability computed!");

@@ -47,6 +47,12 @@ class FilterBase {
     value = it->second.i;
     return true;
   }
+  bool getParam(const std::string& name, bool& value) const {  // (a YAML true / false; the stand-in's map holds it as a number)
+    ParamMap::const_iterator it = params_.find(name);
+    if (it == params_.end() || it->second.kind == ParamValue::kString) return false;
+    value = it->second.d != 0.0;
+    return true;
+  }
   bool getParam(const std::string& name, std::string& value) const {
     ParamMap::const_iterator it = params_.find(name);
     if (it == params_.end() || it->second.kind != ParamValue::kString) return false;
