@@ -28,6 +28,7 @@
 #include <vector>
 
 #include <cstdlib>
+#include "te_ctx_state.h"
 #include "te_devbuf.h"
 #include "te_disc_table.h"
 #include "te_internal.h"
@@ -59,7 +60,9 @@ struct te_ctx {
   hipStream_t aux_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   te_params params;
-  bool have_params = false, have_geo = false, have_elev = false, chain_done = false, footprint_done = false;
+  bool have_params = false, have_geo = false;
+  // which cached results still describe the resident layers: every fact and every transition in te_ctx_state.h
+  te::CtxState st;
   // te_check_footprint_paths_radius (te_path_discs.hip): the spiral table of one radius class on the device, by (radius,
   // offset, resolution, map size)
   struct PdTable {
@@ -109,29 +112,14 @@ struct te_ctx {
     te::DevBuf tile_in[2], tile_out[2];  // the device staging of in_slot / out_slot; grown
   } cmem;
   float* poly_rot = nullptr;  // (derived: lmem.poly)
-  bool have_robot_slope = false, check_inclination = false;  // footprint/check_robot_inclination (:114)
+  bool check_inclination = false;  // footprint/check_robot_inclination (:114)
   std::vector<unsigned> poly_stream_host;  // stays alive until the asynchronous upload has been consumed
   te::Geo geo;
   te::ChainParams cp;
   te::FootprintParams fp;
   te::Layers L;
   size_t layer_elems = 0;
-  // mask_done: the untraversable mask (L.untrav) is complete for the scores and the three parameters it reads (fp_max_gap,
-  // fp_critical_step, fp_check_roughness).  Set by every footprint pass and by te_check_footprint_paths_radius, which builds
-  // the mask on its own when it is not; cleared wherever footprint_done is cleared -- except that te_set_params keeps it
-  // when nothing the mask reads changed -- and by an upload of a score layer (which leaves footprint_done as it was).
-  bool mask_done = false;
   unsigned long long pd_clock = 0;  // (lmem.pd_tables)
-  bool combine_deferred = false;
-  // the traversability layer was written from outside (upload, device pointer, a per-plugin combine of uploaded scores):
-  // its values are then not bounded by the weights, and neither the fixed-point footprint kernels nor the double kernels,
-  // which pack the untraversable count into the sum, may be used (te_fp_route.h: the route of any reach)
-  bool trav_external = false;
-  // te_device_ptr handed out the traversability layer: the caller may write it at any time from then on, so only a
-  // footprint pass that runs right behind a chain that rewrote EVERY cell (te_run_chain with the footprint flag) may
-  // still assume the bound; te_run_footprint and region runs plan without one and take the route of any reach
-  // (te_fp_route.h).  Reset with the layers.
-  bool trav_ptr_out = false;
   // te_set_option: choices between kernels that give identical results (tests reach both; never read from the environment)
   int opt_fb_walk = 0, opt_fb_blocks_per_cu = 0, opt_polygon_per_cell = 0, opt_graph = 0, opt_bcast_rccl = 0, opt_rank_rule = 0,
       opt_fp_any = 0;
@@ -144,17 +132,8 @@ struct te_ctx {
   // te_run_median_fill (empty: of none; cleared by every te_set_geometry)
   int opt_median_route = 0;
   std::vector<uint8_t> fill_mask_valid;
-  // invalid cells of the elevation layer as of the last whole upload (-1: unknown -- tiles, device pointer): see sparse_holes()
-  long long invalid_cells = -1;
-  long long invalid_runs = -1;  // runs of invalid cells in memory order (k_count_invalid); meaningful with invalid_cells >= 0
-  // face flags (te_face_flags.h): built by the same pass over the whole elevation layer, for the fp_critical_step held then.
-  // face_crit: that value; NaN: unknown -- whatever makes invalid_cells unknown (tiles, the
-  // device pointer, a failed prefetch), or a te_set_params that changed fp_critical_step.  The bytes live in the slab.
+  // face flags (te_face_flags.h): the bytes live in the slab; what they describe: te::CtxState::face_crit
   uint8_t* face_flags = nullptr;
-  double face_crit = __builtin_nan("");
-  // te_device_ptr handed out the elevation layer: the caller may write it at any time from then on, behind any later upload's
-  // pass -- the flags are never passed again until the layers are allocated anew (te_set_geometry with another shape)
-  bool elev_ptr_out = false;
   int opt_face_flags = 1;  // TE_OPT_FACE_FLAGS
   bool tables_ready = false;
   // the circular-footprint tables are built separately: a footprint whose tables do not fit in device memory must not
@@ -178,11 +157,6 @@ struct te_ctx {
   int in_next = 0, out_next = 0;
   bool tiles_pending = false;  // te_sync has copy streams to wait for
   te::HostStager stager;           // whole-layer transfers through pageable host buffers (te_stage.hip)
-  // bit TE_LAYER_* of the optional layers that hold values: surface_normal_* (a whole-map chain with TE_RUN_KEEP_NORMALS or
-  // TE_FILTER_NORMALS sets them, a whole-map chain without the flag clears them like the DeletionFilter), the three memo layers
-  // (a whole-map footprint pass with TE_RUN_FOOTPRINT_MEMO), and any layer an upload or te_device_ptr touched (ensure_input_layer).
-  // Read by te_run_expression only; cleared with the layers.
-  unsigned layers_written = 0;
   // te_prefetch_layers: whole-layer uploads on a thread of their own, through a second staging ring and the second copy
   // pool, beside whatever the caller does meanwhile (a filter on other layers, the download of its output)
   te::HostStager prefetcher;
@@ -215,8 +189,9 @@ struct CtxLock {
     if (!beside_prefetch || (touches & c->prefetch_mask)) finish_prefetch_locked(c);
   }
 };
-constexpr unsigned bit(int layer) { return (layer >= 0 && layer < 32) ? 1u << layer : 0u; }
-// counts the invalid cells of the whole elevation layer on the context's stream, builds its face flags and waits for the result
+constexpr unsigned bit(int layer) { return layer_bit(layer); }
+// counts the invalid cells of the whole elevation layer on the context's stream, builds its face flags, waits for the result
+// and records it in c->st (unknown from the start of the call until it has succeeded)
 int count_invalid_elevation(te_ctx* c);
 // the face flags a mask launch may read now (nullptr: unknown, or switched off)
 const uint8_t* usable_face_flags(const te_ctx* c);

@@ -24,7 +24,7 @@ int make_args(const char* who, te_ctx* c, const expr::Program& p, expr::Args& a)
   for (int k = 0; k < p.n_layers; ++k) {
     const int id = p.layer_id[k];
     const float* ptr = layer_ptr(c, id);
-    const bool absent = !ptr || (bit(id) & optional & ~c->layers_written) || (id == TE_LAYER_ROBOT_SLOPE && !c->have_robot_slope);
+    const bool absent = !ptr || (bit(id) & optional & ~c->st.layers_written()) || (id == TE_LAYER_ROBOT_SLOPE && !c->st.have_robot_slope());
     if (absent) {
       int n = 0;
       const expr::LayerName* names = expr::layer_names(&n);
@@ -79,8 +79,7 @@ int te_run_expression(te_ctx* c, const char* text, int out_layer) {
   HIP_TRY(hipSetDevice(c->device));
   if (const int rc = launch_locked(c, p, a)) return rc;
   // as te_upload_layer(TE_LAYER_TRAVERSABILITY) leaves it: the values are not bounded by the weights
-  c->trav_external = c->trav_ptr_out = true;
-  c->layers_written |= bit(TE_LAYER_TRAVERSABILITY);
+  c->st.expression_wrote_traversability();
   return TE_OK;
 }
 

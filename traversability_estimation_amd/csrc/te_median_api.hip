@@ -15,9 +15,9 @@ int input_layer(const char* who, te_ctx* c, int id, const float** out) {
                                 bit(TE_LAYER_TRAVERSABILITY_ROT);
   if (id < 0 || id >= TE_LAYER_COUNT) return fail(TE_ERR_INVALID_ARG, "%s: bad input layer %d", who, id);
   const float* ptr = layer_ptr(c, id);
-  const bool written = id == TE_LAYER_TRAVERSABILITY_X || id == TE_LAYER_TRAVERSABILITY_ROT || (c->layers_written & bit(id));
-  const bool absent = !ptr || ((bit(id) & optional) && !written) || (id == TE_LAYER_ROBOT_SLOPE && !c->have_robot_slope) ||
-                      (id == TE_LAYER_ELEVATION && !c->have_elev);
+  const bool written = id == TE_LAYER_TRAVERSABILITY_X || id == TE_LAYER_TRAVERSABILITY_ROT || (c->st.layers_written() & bit(id));
+  const bool absent = !ptr || ((bit(id) & optional) && !written) || (id == TE_LAYER_ROBOT_SLOPE && !c->st.have_robot_slope()) ||
+                      (id == TE_LAYER_ELEVATION && !c->st.have_elev());
   if (absent) return fail(TE_ERR_NOT_READY, "%s: the input layer %d does not exist yet", who, id);
   *out = ptr;
   return TE_OK;
@@ -94,16 +94,11 @@ int prepare(const char* who, te_ctx* c, const te_median_fill_params* p, int in_l
 // te_upload_layer); caller holds the lock
 int note_written(te_ctx* c, int out_layer) {
   if (out_layer == TE_LAYER_ELEVATION) {
-    c->chain_done = false;
-    c->footprint_done = false;
-    c->mask_done = false;
+    c->st.elevation_replaced();
     // the pass of an elevation upload over the whole layer: invalid cells, their runs, the face flags (it waits for the fill)
-    if (const int rc = count_invalid_elevation(c)) return rc;
-    c->have_elev = true;
+    return count_invalid_elevation(c);
   }
-  if (out_layer == TE_LAYER_ROBOT_SLOPE) c->have_robot_slope = true;
-  if (out_layer == TE_LAYER_TRAVERSABILITY) c->trav_external = c->trav_ptr_out = true;
-  if (out_layer == TE_LAYER_SLOPE || out_layer == TE_LAYER_STEP || out_layer == TE_LAYER_ROUGHNESS) c->mask_done = false;  // (the mask reads them)
+  c->st.layer_written(out_layer, CtxState::kUploaded);
   return TE_OK;
 }
 

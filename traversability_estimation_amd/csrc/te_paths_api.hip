@@ -71,10 +71,10 @@ int te_check_footprint_paths_radius(te_ctx* c, int map, int n_paths, const int* 
     if (!isfinite(radius[k]) || radius[k] < 0.0)
       return fail(TE_ERR_INVALID_ARG, "te_check_footprint_paths_radius: radius[%d] = %g (a footprint radius is finite and not negative)", k, radius[k]);
   CtxLock lk(c);
-  if (!c->have_geo || !c->chain_done || !c->tables_ready)
+  if (!c->have_geo || !c->st.chain_done() || !c->tables_ready)
     return fail(TE_ERR_NOT_READY, "te_check_footprint_paths_radius: run the filter chain first (it produces the layers the discs read)");
   if (map < 0 || map >= c->geo.batch) return fail(TE_ERR_INVALID_ARG, "te_check_footprint_paths_radius: map %d of %d", map, c->geo.batch);
-  if (c->check_inclination && !c->have_robot_slope)
+  if (c->check_inclination && !c->st.have_robot_slope())
     return fail(TE_ERR_NOT_READY, "te_check_footprint_paths_radius: check_robot_inclination is set but the layer robot_slope was never uploaded");
   if (stats) stats->n_visits = stats->n_discs = stats->n_radius_classes = 0;
   if (n_paths == 0) return TE_OK;
@@ -142,12 +142,9 @@ int te_check_footprint_paths_radius(te_ctx* c, int map, int n_paths, const int* 
   if (e == hipSuccess) e = hipMemsetAsync(s.keys, 0xFF, p_keys.bytes(), c->stream);  // pv::kEmptyKey
   if (e == hipSuccess) e = hipMemsetAsync(s.counters, 0, p_cnt.bytes(), c->stream);
   // the untraversable mask: built on the first call after the scores (or one of the three parameters it reads) changed
-  if (e == hipSuccess && !c->mask_done) {
-    e = launch_footprint_mask(g, c->fp, c->L, usable_face_flags(c), c->combine_deferred ? &c->cp : nullptr, c->stream);
-    if (e == hipSuccess) {
-      c->combine_deferred = false;
-      c->mask_done = true;
-    }
+  if (e == hipSuccess && !c->st.mask_done()) {
+    e = launch_footprint_mask(g, c->fp, c->L, usable_face_flags(c), c->st.combine_deferred() ? &c->cp : nullptr, c->stream);
+    if (e == hipSuccess) c->st.mask_built();
   }
   const size_t per = (size_t)g.rows * g.cols;
   if (e == hipSuccess)
@@ -182,10 +179,10 @@ int te_check_footprint_paths(te_ctx* c, int map, int n_paths, const int* pose_of
   if (!c || n_paths < 0 || (n_paths > 0 && (!pose_offset || !pose_xy || !is_safe || !traversability || !status)))
     return fail(TE_ERR_INVALID_ARG, "te_check_footprint_paths: NULL argument");
   CtxLock lk(c);
-  if (!c->have_geo || !c->footprint_done)
+  if (!c->have_geo || !c->st.footprint_done())
     return fail(TE_ERR_NOT_READY, "te_check_footprint_paths: run the chain with the footprint pass first");
   if (map < 0 || map >= c->geo.batch) return fail(TE_ERR_INVALID_ARG, "te_check_footprint_paths: map %d of %d", map, c->geo.batch);
-  if (c->check_inclination && !c->have_robot_slope)
+  if (c->check_inclination && !c->st.have_robot_slope())
     return fail(TE_ERR_NOT_READY, "te_check_footprint_paths: check_robot_inclination is set but the layer robot_slope was never uploaded");
   if (n_paths == 0) return TE_OK;
   const int n_poses = pose_offset[n_paths];
@@ -233,7 +230,7 @@ namespace {
 // batched checkInclination on the resident robot_slope layer of map `map`; c->mu held
 int check_inclination_locked(te_ctx* c, int map, int n, const double* start_end_xy, unsigned char* ok, int* status,
                              const char* who) {
-  if (!c->have_geo || !c->have_robot_slope) return fail(TE_ERR_NOT_READY, "%s: upload the layer robot_slope first", who);
+  if (!c->have_geo || !c->st.have_robot_slope()) return fail(TE_ERR_NOT_READY, "%s: upload the layer robot_slope first", who);
   if (map < 0 || map >= c->geo.batch) return fail(TE_ERR_INVALID_ARG, "%s: map %d of %d", who, map, c->geo.batch);
   if (n == 0) return TE_OK;
   HIP_TRY(hipSetDevice(c->device));
@@ -270,7 +267,7 @@ int te_run_polygon_footprint(te_ctx* c, int n_points, const double* points_xy, d
   for (int k = 0; k < 2 * n_points; ++k)
     if (!isfinite(points_xy[k])) return fail(TE_ERR_INVALID_ARG, "te_run_polygon_footprint: footprint point %d is not finite", k / 2);
   CtxLock lk(c);
-  if (!c->have_geo || !c->footprint_done)
+  if (!c->have_geo || !c->st.footprint_done())
     return fail(TE_ERR_NOT_READY, "te_run_polygon_footprint: run the chain with the footprint pass first (it marks the untraversable cells)");
   if (c->geo.cols > 65535) return fail(TE_ERR_UNSUPPORTED, "te_run_polygon_footprint: more than 65535 columns");
   HIP_TRY(hipSetDevice(c->device));
@@ -347,7 +344,7 @@ int te_polygons_traversable(te_ctx* c, int map, int n_polygons, const int* verte
   if (!c || n_polygons < 0 || (n_polygons > 0 && (!vertex_offset || !vertex_xy || !is_traversable || !traversability)))
     return fail(TE_ERR_INVALID_ARG, "te_polygons_traversable: NULL argument");
   CtxLock lk(c);
-  if (!c->have_geo || !c->footprint_done)
+  if (!c->have_geo || !c->st.footprint_done())
     return fail(TE_ERR_NOT_READY, "te_polygons_traversable: run the chain with the footprint pass first (it marks the untraversable cells)");
   if (map < 0 || map >= c->geo.batch) return fail(TE_ERR_INVALID_ARG, "te_polygons_traversable: map %d of %d", map, c->geo.batch);
   if (n_polygons == 0) return TE_OK;
@@ -370,7 +367,7 @@ int te_polygon_untraversable_hull(te_ctx* c, int map, int n_vertices, const doub
   for (long k = 0; k < 2L * n_vertices; ++k)
     if (!isfinite(vertex_xy[k])) return fail(TE_ERR_INVALID_ARG, "te_polygon_untraversable_hull: vertex %ld is not finite", k / 2);
   CtxLock lk(c);
-  if (!c->have_geo || !c->footprint_done)
+  if (!c->have_geo || !c->st.footprint_done())
     return fail(TE_ERR_NOT_READY, "te_polygon_untraversable_hull: run the chain with the footprint pass first (it marks the untraversable cells)");
   if (map < 0 || map >= c->geo.batch) return fail(TE_ERR_INVALID_ARG, "te_polygon_untraversable_hull: map %d of %d", map, c->geo.batch);
   *n_hull = 0;
@@ -411,10 +408,10 @@ int te_check_polygon_footprint_paths(te_ctx* c, int map, int n_paths, const int*
   for (int k = 0; k < 3 * n_points; ++k)
     if (!isfinite(points_xyz[k])) return fail(TE_ERR_INVALID_ARG, "te_check_polygon_footprint_paths: footprint point %d is not finite", k / 3);
   CtxLock lk(c);
-  if (!c->have_geo || !c->footprint_done)
+  if (!c->have_geo || !c->st.footprint_done())
     return fail(TE_ERR_NOT_READY, "te_check_polygon_footprint_paths: run the chain with the footprint pass first (it marks the untraversable cells)");
   if (map < 0 || map >= c->geo.batch) return fail(TE_ERR_INVALID_ARG, "te_check_polygon_footprint_paths: map %d of %d", map, c->geo.batch);
-  if (c->check_inclination && !c->have_robot_slope)
+  if (c->check_inclination && !c->st.have_robot_slope())
     return fail(TE_ERR_NOT_READY, "te_check_polygon_footprint_paths: check_robot_inclination is set but the layer robot_slope was never uploaded");
   if (n_paths == 0) return TE_OK;
   if (pose_offset[0] != 0) return fail(TE_ERR_INVALID_ARG, "te_check_polygon_footprint_paths: bad pose offsets");

@@ -255,32 +255,13 @@ void finish_prefetch_locked(te_ctx* c) {
   c->prefetch_mask = 0;
   c->prefetch_elev = false;
   const bool ok = c->prefetch_rc.load() == TE_OK;
-  if (mask & (1u << TE_LAYER_ELEVATION)) {
-    // whatever was computed from the previous elevation no longer describes the layer, arrived or torn
-    c->chain_done = false;
-    c->footprint_done = false;
-    c->mask_done = false;
-    c->invalid_cells = -1;
-    c->invalid_runs = -1;
-    c->face_crit = __builtin_nan("");  // (a failed or partial prefetch leaves the face flags unknown as well)
-    if (ok) {
-      c->have_elev = true;
-      // the invalid cells are counted like te_upload_elevation counts them (the count picks the normals kernel's march and
-      // strip height); a failure leaves the count unknown, which every kernel serves
-      if (hipSetDevice(c->device) != hipSuccess || count_invalid_elevation(c) != TE_OK) {
-        (void)hipGetLastError();
-        c->invalid_cells = -1;
-        c->face_crit = __builtin_nan("");
-      }
-    } else {
-      c->have_elev = false;  // partly overwritten: the next chain needs a complete upload
-    }
+  c->st.prefetch_joined(mask, ok);
+  // an arrived elevation: the invalid cells are counted like te_upload_elevation counts them (the count picks the normals
+  // kernel's march and strip height); a failure leaves the count unknown, which every kernel serves
+  if (ok && (mask & bit(TE_LAYER_ELEVATION)) && (hipSetDevice(c->device) != hipSuccess || count_invalid_elevation(c) != TE_OK)) {
+    (void)hipGetLastError();
+    c->st.count_unknown();
   }
-  if (ok) {  // (what an arrived layer changes for the later calls: only once it HAS arrived)
-    if (mask & (1u << TE_LAYER_ROBOT_SLOPE)) c->have_robot_slope = true;
-    if (mask & (1u << TE_LAYER_TRAVERSABILITY)) c->trav_external = c->trav_ptr_out = true;
-  }
-  if (mask & (bit(TE_LAYER_SLOPE) | bit(TE_LAYER_STEP) | bit(TE_LAYER_ROUGHNESS))) c->mask_done = false;
 }
 // layers TE_FILTER_* reads and writes (travgpu.h: TE_FILTER_* table)
 unsigned filter_layers(int filter) {
@@ -303,8 +284,7 @@ namespace shim {
 // counts the invalid cells of the whole elevation layer on the context's stream, builds the layer's face flags for the
 // fp_critical_step held (te_face_flags.h) and waits for the result
 int count_invalid_elevation(te_ctx* c) {
-  c->invalid_cells = -1;
-  c->face_crit = __builtin_nan("");
+  c->st.count_unknown();
   HIP_TRY(c->cmem.count.once(2 * sizeof(unsigned long long)));
   unsigned long long* const d_count = c->cmem.count.as<unsigned long long>();
   HIP_TRY(hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned long long), c->stream));
@@ -317,18 +297,14 @@ int count_invalid_elevation(te_ctx* c) {
   unsigned long long h[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(h, d_count, sizeof(h), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->invalid_cells = (long long)h[0];
-  c->invalid_runs = (long long)h[1];
-  if (with_flags) c->face_crit = crit;
+  c->st.elevation_counted((long long)h[0], (long long)h[1], with_flags ? crit : __builtin_nan(""));
   return TE_OK;
 }
 
 // the face flags a mask launch may read: built for the elevation that is resident and for the critical step of the footprint
 // parameters in force (NaN -- unknown -- compares false)
 const uint8_t* usable_face_flags(const te_ctx* c) {
-  return (c->opt_face_flags && c->face_flags && !c->elev_ptr_out && c->face_crit == c->fp.crit_step && c->face_crit == c->params.fp_critical_step)
-             ? c->face_flags
-             : nullptr;
+  return (c->opt_face_flags && c->face_flags && c->st.face_flags_for(c->fp.crit_step, c->params.fp_critical_step)) ? c->face_flags : nullptr;
 }
 
 // few invalid cells, scattered: at most 2 per mille (0.1 % speckle: the sparse march is 1.4x faster than the dense one,
@@ -337,7 +313,7 @@ const uint8_t* usable_face_flags(const te_ctx* c) {
 // cells uploaded later -- tiles are not counted -- is then in safe hands.)
 // Which march serves the invalid cells of the resident elevation layer: te_hole_routing.h (plain functions of the upload's
 // two counts, shared with the CPU test); the lab switches stay here.
-HoleCounts hole_counts(const te_ctx* c) { return HoleCounts{(long long)c->layer_elems, c->invalid_cells, c->invalid_runs}; }
+HoleCounts hole_counts(const te_ctx* c) { return c->st.hole_counts((long long)c->layer_elems); }
 bool clustered_holes(const te_ctx* c) { return holes_clustered(hole_counts(c)); }
 bool sparse_holes(const te_ctx* c) {
   static const int force = lab_int("TE_N3_HOLES", 0);  // measurement aid: 1 sparse, 2 dense
@@ -352,7 +328,7 @@ bool skip_clean_march(const te_ctx* c) {
 }
 bool short_strips(const te_ctx* c) {
   static const int force = lab_int("TE_N3_SHORT_STRIPS", -1);  // measurement aid: 0 never, 1 whenever invalid cells were counted
-  if (force >= 0) return force == 1 && c->invalid_cells > 0 && !sparse_holes(c);
+  if (force >= 0) return force == 1 && c->st.invalid_cells() > 0 && !sparse_holes(c);
   return clustered_holes(c) && !sparse_holes(c);
 }
 
@@ -369,16 +345,39 @@ void ensure_tie_scratch(te_ctx* c) {
   if (hipSetDevice(c->device) == hipSuccess) (void)c->lmem.tie_scratch.once(c->layer_elems * sizeof(float));
 }
 
-// What a launch of the filters takes from the context beside its parameters: the hints the normals kernel takes from the
-// upload's count, TE_OPT_NORMALS_RANK_RULE, and the two scratch buffers with the pointers derived from them (allocated on
-// first need, outside any capture; a failed allocation leaves the pointer null and the kernels that need none serve)
-void set_launch_hints(te_ctx* c) {
-  c->L.sparse_holes = sparse_holes(c) && ensure_hole_queue(c) ? 1 : 0;
-  c->L.no_holes = c->invalid_cells == 0 ? 1 : 0;
-  c->L.skip_clean = c->L.sparse_holes && skip_clean_march(c) ? 1 : 0;
-  c->L.short_strips = short_strips(c) ? 1 : 0;
-  c->L.hole_queue = c->cmem.hole_queue.as<char>();
+// What picks the kernel variants of a whole-map launch beside its flags: the march k_normals3 runs, from the upload's count,
+// and whether the mask kernel is given the face flags.  A captured launch bakes them in, so they are decided in ONE place:
+// set_launch_hints hands them to the kernels and run_whole_locked packs its graph key from the same struct.
+struct LaunchHints {
+  bool sparse_holes, no_holes, skip_clean, short_strips, face_flags;
+  // the upper bits of the graph key, above the TE_RUN_* bits (the face flags matter to a launch with the footprint pass)
+  unsigned key_bits(unsigned flags) const {
+    return (sparse_holes ? 0x80000000u : 0u) | (no_holes ? 0x40000000u : 0u) | (skip_clean ? 0x20000000u : 0u) | (short_strips ? 0x10000000u : 0u) |
+           (((flags & TE_RUN_FOOTPRINT) && face_flags) ? 0x08000000u : 0u);
+  }
+};
+// ... with the two scratch buffers the variants need, allocated on first need and outside any capture (run_whole_locked asks
+// before it captures); a failed allocation leaves the pointer null and the kernels that need none serve
+LaunchHints launch_hints(te_ctx* c) {
+  LaunchHints h;
+  h.sparse_holes = sparse_holes(c) && ensure_hole_queue(c);
+  h.no_holes = c->st.invalid_cells() == 0;
+  h.skip_clean = h.sparse_holes && skip_clean_march(c);
+  h.short_strips = short_strips(c);
+  h.face_flags = usable_face_flags(c) != nullptr;
   ensure_tie_scratch(c);
+  return h;
+}
+
+// What a launch of the filters takes from the context beside its parameters: the hints, TE_OPT_NORMALS_RANK_RULE, and the
+// pointers derived from the two scratch buffers
+void set_launch_hints(te_ctx* c) {
+  const LaunchHints h = launch_hints(c);
+  c->L.sparse_holes = h.sparse_holes ? 1 : 0;
+  c->L.no_holes = h.no_holes ? 1 : 0;
+  c->L.skip_clean = h.skip_clean ? 1 : 0;
+  c->L.short_strips = h.short_strips ? 1 : 0;
+  c->L.hole_queue = c->cmem.hole_queue.as<char>();
   c->L.tie_scratch = c->lmem.tie_scratch.as<float>();
   c->cp.rank_rule = c->opt_rank_rule;
 }
@@ -425,12 +424,6 @@ static int fp_any_alloc(te_ctx* c, DevBuf& buf, size_t bytes, const char* what) 
               "footprint: the traversability layer has no known bound (written from outside, or a large or negative weight or "
               "default) and is summed on the route of any reach, whose %s (%zu bytes) do not fit in device memory",
               what, bytes);
-}
-
-// bound of the combined layer the chain writes (scores lie in [0, 1]); < 0: none, a weight is negative
-static double weights_cap(float w_scale, float w_slope, float w_step, float w_rough) {
-  if (!(w_scale >= 0.0f && w_slope >= 0.0f && w_step >= 0.0f && w_rough >= 0.0f)) return -1.0;
-  return (double)w_scale * ((double)w_slope + (double)w_step + (double)w_rough);
 }
 
 // The tables of the route of any reach (te_footprint_any.hip) on the device: run half-widths, those of the inner disc (the
@@ -668,18 +661,10 @@ void free_layers(te_ctx* c) {
   c->face_flags = nullptr;
   c->poly_rot = nullptr;
   clear_fp_any_ptrs(c);
-  c->face_crit = __builtin_nan("");
-  c->elev_ptr_out = false;
   c->fill_mask_valid.clear();  // (lmem.median_mask is gone)
   guard_cache_generation().fetch_add(1, std::memory_order_acq_rel);  // (layer_has_guard_rows: verdicts about freed memory)
-  c->layers_written = 0;
-  c->have_robot_slope = false;
   c->layer_elems = 0;
-  c->trav_ptr_out = false;
-  c->have_elev = false;
-  c->chain_done = false;
-  c->footprint_done = false;
-  c->mask_done = false;
+  c->st.layers_freed();
 }
 
 float* layer_ptr(te_ctx* c, int layer) {
@@ -705,7 +690,7 @@ float* layer_ptr(te_ctx* c, int layer) {
 
 // the optional input layer robot_slope exists from its first upload on (every cell NaN = not valid until written)
 int ensure_input_layer(te_ctx* c, int layer) {
-  c->layers_written |= bit(layer);  // (every upload route and te_device_ptr pass here before they write: te_ctx.h)
+  c->st.layer_touched(layer);
   DevBuf& rs = c->lmem.robot_slope;
   if (layer != TE_LAYER_ROBOT_SLOPE || rs.p) return TE_OK;
   HIP_TRY(hipSetDevice(c->device));
@@ -718,23 +703,13 @@ int ensure_input_layer(te_ctx* c, int layer) {
   return TE_OK;
 }
 
-// te_ctx::layers_written: a whole-map chain leaves the normal layers with TE_RUN_KEEP_NORMALS and drops them without
-constexpr unsigned kNormalLayers = bit(TE_LAYER_NORMAL_X) | bit(TE_LAYER_NORMAL_Y) | bit(TE_LAYER_NORMAL_Z);
-constexpr unsigned kMemoLayers = bit(TE_LAYER_SLOPE_FOOTPRINT) | bit(TE_LAYER_STEP_FOOTPRINT) | bit(TE_LAYER_ROUGHNESS_FOOTPRINT);
-static void note_normals_kept(te_ctx* c, unsigned flags) {
-  if (flags & (TE_RUN_KEEP_NORMALS | TE_RUN_NORMALS_ONLY))
-    c->layers_written |= kNormalLayers;
-  else
-    c->layers_written &= ~kNormalLayers;
-}
-
 int run_chain_locked(te_ctx* c, unsigned flags, const Region& r) {
   if (!c->have_params || !c->have_geo) return fail(TE_ERR_NOT_READY, "te_run_chain: set params and geometry first");
   if (!c->tables_ready) {
     int rc = rebuild_tables(c);
     if (rc) return rc;
   }
-  if (!c->have_elev) return fail(TE_ERR_NOT_READY, "te_run_chain: no elevation uploaded");
+  if (!c->st.have_elev()) return fail(TE_ERR_NOT_READY, "te_run_chain: no elevation uploaded");
   if (int rc = refuse_rank_rule(c)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   // Two streams (step filter || normals kernel) pay from about 2^21 cells: below that the launch is a handful of
@@ -749,8 +724,8 @@ int run_chain_locked(te_ctx* c, unsigned flags, const Region& r) {
   // never be written)
   if ((flags & TE_RUN_FOOTPRINT) && !c->fp_tables_ready)
     return fail(c->fp_tables_rc ? c->fp_tables_rc : TE_ERR_NOT_READY, "%s", c->fp_tables_err[0] ? c->fp_tables_err : "footprint tables not built");
-  c->combine_deferred = (r.map < 0) && !(flags & TE_RUN_SEQUENTIAL) && (flags & TE_RUN_FOOTPRINT);
-  if (c->combine_deferred) flags |= kDeferCombine;
+  const bool whole = r.map < 0;
+  if (c->st.chain_launching(whole, flags)) flags |= kDeferCombine;
   c->L.ev_fork = c->ev_fork;
   c->L.ev_join = c->ev_join;
   c->L.fb_walk = c->opt_fb_walk;
@@ -758,31 +733,25 @@ int run_chain_locked(te_ctx* c, unsigned flags, const Region& r) {
   set_launch_hints(c);  // (run_whole_locked allocates their buffers before it captures)
   if (c->opt_rank_rule) flags |= TE_RUN_GENERIC_KERNELS;  // (the rule lives in the generic normals kernel only)
   HIP_TRY(launch_chain(c->geo, c->cp, c->L, r, flags, c->stream));
-  c->chain_done = true;
-  c->footprint_done = false;  // the layers the footprint pass reads have changed
-  c->mask_done = false;
-  if (r.map < 0) c->trav_external = false;  // every cell of the combined layer now comes from the chain
-  if (r.map < 0) note_normals_kept(c, flags);
+  c->st.chain_launched(whole, flags);
   return TE_OK;
 }
 
+// bound of the combined layer for a footprint pass that is about to run (te_ctx_state.h: trav_cap); < 0: none
+static double trav_cap_now(const te_ctx* c, bool fresh) { return c->st.trav_cap(c->cp.w_scale, c->cp.w_slope, c->cp.w_step, c->cp.w_rough, fresh); }
+
 // fresh: called right behind a whole-map chain in the same entry point (the combined layer is the chain's, cell for cell)
 int run_footprint_locked(te_ctx* c, unsigned flags, bool fresh = false) {
-  if (!c->chain_done || !c->tables_ready)
+  if (!c->st.chain_done() || !c->tables_ready)
     return fail(TE_ERR_NOT_READY, "te_run_footprint: run the filter chain first (it produces the layers the footprint reads)");
   if (!c->fp_tables_ready) return fail(c->fp_tables_rc ? c->fp_tables_rc : TE_ERR_NOT_READY, "%s", c->fp_tables_err);
   HIP_TRY(hipSetDevice(c->device));
-  // bound of the combined layer, if the chain wrote it: scores lie in [0, 1], so w_scale * (w_slope + w_step + w_rough)
-  const ChainParams& q = c->cp;
-  const bool bounded = !c->trav_external && (fresh || !c->trav_ptr_out) && q.w_scale >= 0.0f && q.w_slope >= 0.0f && q.w_step >= 0.0f && q.w_rough >= 0.0f;
-  const double trav_cap = bounded ? (double)q.w_scale * ((double)q.w_slope + (double)q.w_step + (double)q.w_rough) : -1.0;
+  const double trav_cap = trav_cap_now(c, fresh);
+  const bool memo = (flags & TE_RUN_FOOTPRINT_MEMO) != 0;
   if (int rc = ensure_fp_any(c, trav_cap)) return rc;
-  HIP_TRY(launch_footprint(c->geo, c->fp, c->L, usable_face_flags(c), c->cmem.spiral.as<unsigned>(), c->cmem.fp_clip_table.as<int>(), (flags & TE_RUN_FOOTPRINT_MEMO) != 0,
-                           c->combine_deferred ? &c->cp : nullptr, trav_cap, c->stream));
-  c->combine_deferred = false;
-  c->footprint_done = true;
-  c->mask_done = true;
-  if (flags & TE_RUN_FOOTPRINT_MEMO) c->layers_written |= kMemoLayers;
+  HIP_TRY(launch_footprint(c->geo, c->fp, c->L, usable_face_flags(c), c->cmem.spiral.as<unsigned>(), c->cmem.fp_clip_table.as<int>(), memo,
+                           c->st.combine_deferred() ? &c->cp : nullptr, trav_cap, c->stream));
+  c->st.footprint_launched(memo);
   return TE_OK;
 }
 
@@ -799,7 +768,7 @@ int run_whole_locked(te_ctx* c, unsigned flags) {
   flags &= TE_RUN_KEEP_NORMALS | TE_RUN_FOOTPRINT | TE_RUN_GENERIC_KERNELS | TE_RUN_FOOTPRINT_MEMO | TE_RUN_SEQUENTIAL | TE_RUN_NORMALS_ONLY;
   if (c->opt_rank_rule) flags |= TE_RUN_GENERIC_KERNELS;
   if (flags & TE_RUN_NORMALS_ONLY) flags &= ~(TE_RUN_FOOTPRINT | TE_RUN_FOOTPRINT_MEMO);
-  if (!no_graph && large && !(flags & TE_RUN_NORMALS_ONLY) && c->graph_ok && c->have_params && c->have_geo && c->have_elev) {
+  if (!no_graph && large && !(flags & TE_RUN_NORMALS_ONLY) && c->graph_ok && c->have_params && c->have_geo && c->st.have_elev()) {
     if (!c->tables_ready) {
       int rc = rebuild_tables(c);
       if (rc) return rc;
@@ -808,9 +777,8 @@ int run_whole_locked(te_ctx* c, unsigned flags) {
     HIP_TRY(hipSetDevice(c->device));
     int slot = -1;
     // (the captured launches bake in which k_normals3 variant runs, and whether the mask kernel is given the face flags: the
-    // hints are part of the key)
-    ensure_tie_scratch(c);
-    const unsigned key = flags | (((flags & TE_RUN_FOOTPRINT) && usable_face_flags(c)) ? 0x08000000u : 0u) | (sparse_holes(c) && ensure_hole_queue(c) ? 0x80000000u : 0u) | (c->invalid_cells == 0 ? 0x40000000u : 0u) | (skip_clean_march(c) ? 0x20000000u : 0u) | (short_strips(c) ? 0x10000000u : 0u);
+    // hints are part of the key; asking for them here allocates their buffers before the capture)
+    const unsigned key = flags | launch_hints(c).key_bits(flags);
     for (int k = 0; k < te_ctx::kGraphs; ++k)
       if (c->graph_exec[k] && c->graph_flags[k] == key) slot = k;
     if (slot < 0) {
@@ -840,13 +808,7 @@ int run_whole_locked(te_ctx* c, unsigned flags) {
     if (slot >= 0) {
       TraceRange tr("te_run_chain: graph replay (chain + footprint kernels)");
       HIP_TRY(hipGraphLaunch(c->graph_exec[slot], c->stream));
-      c->trav_external = false;  // (as run_chain_locked: every cell of the combined layer now comes from the chain)
-      c->chain_done = true;
-      c->footprint_done = (flags & TE_RUN_FOOTPRINT) != 0;
-      c->mask_done = c->footprint_done;
-      c->combine_deferred = false;
-      note_normals_kept(c, flags);
-      if ((flags & TE_RUN_FOOTPRINT) && (flags & TE_RUN_FOOTPRINT_MEMO)) c->layers_written |= kMemoLayers;
+      c->st.graph_replayed(flags);
       return TE_OK;
     }
   }
@@ -1035,13 +997,11 @@ int te_set_params(te_ctx* c, const te_params* p) {
   }
   // the filter layers stay valid when only the footprint part (fp_*, the tail of the struct) changed:
   // traversabilityFootprint(radius, offset) is called with a new radius on an unchanged map
-  if (memcmp(&old, p, offsetof(te_params, fp_radius)) != 0) c->chain_done = false;
-  // ... and the untraversable mask with them, unless one of the three parameters it reads changed (te_ctx.h: mask_done)
-  c->mask_done = c->mask_done && c->chain_done && old.fp_max_gap == p->fp_max_gap &&
-                      old.fp_critical_step == p->fp_critical_step && old.fp_check_roughness == p->fp_check_roughness;
-  c->footprint_done = false;
-  // the face flags were built for the critical step held at upload (te_face_flags.h): unknown until the next whole upload
-  if (!(old.fp_critical_step == p->fp_critical_step)) c->face_crit = __builtin_nan("");
+  // ... and the untraversable mask with them, unless one of the three parameters it reads changed; the face flags were built
+  // for the critical step held at upload (te_face_flags.h): unknown until the next whole upload
+  const bool crit_same = old.fp_critical_step == p->fp_critical_step;
+  c->st.params_changed(memcmp(&old, p, offsetof(te_params, fp_radius)) != 0,
+                       !(old.fp_max_gap == p->fp_max_gap && crit_same && old.fp_check_roughness == p->fp_check_roughness), !crit_same);
   return TE_OK;
 }
 
@@ -1071,7 +1031,7 @@ int te_set_option(te_ctx* c, int option, int value) {
       if (value < 0 || value > 1) return fail(TE_ERR_INVALID_ARG, "te_set_option: TE_OPT_FP_ANY_REACH takes 0 (by reach) or 1 (every reach)");
       if (c->opt_fp_any != value) {
         c->opt_fp_any = value;
-        c->footprint_done = false;
+        c->st.footprint_option_changed();
         if (c->tables_ready) rebuild_footprint_tables(c);
       }
       break;
@@ -1089,9 +1049,7 @@ int te_set_option(te_ctx* c, int option, int value) {
             return rc;
           }
         }
-        c->chain_done = false;
-        c->footprint_done = false;
-        c->mask_done = false;
+        c->st.filter_option_changed();
       }
       break;
     case TE_OPT_FACE_FLAGS:
@@ -1104,9 +1062,7 @@ int te_set_option(te_ctx* c, int option, int value) {
       return TE_OK;  // (read by te_run_median_fill alone, which is never captured; identical layers either way)
     case TE_OPT_NORMALS_RANK_RULE:
       c->opt_rank_rule = value != 0;
-      c->chain_done = false;
-      c->footprint_done = false;
-      c->mask_done = false;
+      c->st.filter_option_changed();
       break;
     default:
       return fail(TE_ERR_INVALID_ARG, "te_set_option: unknown option %d", option);
@@ -1118,7 +1074,7 @@ int te_set_option(te_ctx* c, int option, int value) {
 int te_download_face_flags(te_ctx* c, unsigned char* out, size_t bytes) {
   if (!c || !out) return fail(TE_ERR_INVALID_ARG, "te_download_face_flags: NULL");
   CtxLock lk(c);
-  const uint8_t* f = c->have_geo && c->have_elev ? usable_face_flags(c) : nullptr;
+  const uint8_t* f = c->have_geo && c->st.have_elev() ? usable_face_flags(c) : nullptr;
   if (!f) return fail(TE_ERR_NOT_READY, "te_download_face_flags: the face flags of the elevation layer are unknown or switched off");
   const size_t n = face_flag_bytes(c->geo.rows, c->geo.cols, c->geo.batch);
   if (bytes != n) return fail(TE_ERR_INVALID_ARG, "te_download_face_flags: %zu bytes given, the flags are %zu", bytes, n);
@@ -1171,7 +1127,6 @@ int te_set_geometry(te_ctx* c, int rows, int cols, int batch, double res, double
     c->L.untrav_flags = (uint8_t*)(slab + sp.untrav_flags.off);
     c->L.fp_scratch = have_list ? (unsigned*)(slab + sp.sum_scratch.off) : nullptr;  // (the sum kernel's, see Layers::fp_scratch)
     c->face_flags = (uint8_t*)(slab + sp.face_flags.off);  // (te_face_flags.h, written by the upload's pass)
-    c->face_crit = __builtin_nan("");
     c->layer_elems = elems;
     // outputs read as NaN until computed, like GridMap::add(): the front guard, the layers, the mask and the fix-up flags ...
     HIP_TRY(hipMemsetAsync(slab, 0xFF, sp.list.off, c->stream));
@@ -1197,9 +1152,7 @@ int te_set_geometry(te_ctx* c, int rows, int cols, int batch, double res, double
   c->geo.ax = pos_x + (0.5 * c->geo.len_x - 0.5 * res);
   c->geo.ay = pos_y + (0.5 * c->geo.len_y - 0.5 * res);
   c->have_geo = true;
-  c->chain_done = false;
-  c->footprint_done = false;
-  c->mask_done = false;
+  c->st.geometry_set();
   c->fill_mask_valid.clear();  // (te_download_fill_mask: the mask of a fill under another geometry is not this map's)
   return rebuild_tables(c);
 }
@@ -1216,7 +1169,7 @@ int te_run_filter(te_ctx* c, int filter, unsigned flags) {
     if (rc) return rc;
   }
   if (filter < TE_FILTER_SLOPE || filter > TE_FILTER_NORMALS) return fail(TE_ERR_INVALID_ARG, "te_run_filter: bad filter %d", filter);
-  if ((filter == TE_FILTER_STEP || filter == TE_FILTER_ROUGHNESS || filter == TE_FILTER_NORMALS) && !c->have_elev)
+  if ((filter == TE_FILTER_STEP || filter == TE_FILTER_ROUGHNESS || filter == TE_FILTER_NORMALS) && !c->st.have_elev())
     return fail(TE_ERR_NOT_READY, "te_run_filter: no elevation uploaded");
   if (filter == TE_FILTER_NORMALS)
     if (int rc = refuse_rank_rule(c)) return rc;
@@ -1224,14 +1177,7 @@ int te_run_filter(te_ctx* c, int filter, unsigned flags) {
   set_launch_hints(c);  // (as in the chain: never stale ones)
   if (c->opt_rank_rule) flags |= TE_RUN_GENERIC_KERNELS;
   HIP_TRY(launch_filter(c->geo, c->cp, c->L, filter, flags, c->stream));
-  // A single plugin's filter overwrites score layers from whatever inputs are resident (TE_FILTER_NORMALS also slope
-  // and roughness, with the normals radius): the layers no longer form one chain result, so region re-filters, the
-  // footprint pass and the path checks must not build on them.
-  c->chain_done = false;
-  c->footprint_done = false;
-  c->mask_done = false;
-  c->trav_external = true;
-  if (filter == TE_FILTER_NORMALS) c->layers_written |= kNormalLayers;
+  c->st.filter_ran(filter);
   return TE_OK;
 }
 
@@ -1251,10 +1197,10 @@ int te_run_chain_region(te_ctx* c, unsigned flags, int map, int row0, int col0, 
   if (map < 0 || map >= c->geo.batch || row0 < 0 || col0 < 0 || h <= 0 || w <= 0 || row0 + h > c->geo.rows ||
       col0 + w > c->geo.cols)
     return fail(TE_ERR_INVALID_ARG, "te_run_chain_region: rectangle outside the map");
-  if (!c->chain_done) return fail(TE_ERR_NOT_READY, "te_run_chain_region: run the full chain once first");
+  if (!c->st.chain_done()) return fail(TE_ERR_NOT_READY, "te_run_chain_region: run the full chain once first");
   const Region r = {map, row0, col0, row0 + h, col0 + w};
   const bool want_fp = (flags & (TE_RUN_FOOTPRINT | TE_RUN_FOOTPRINT_MEMO)) != 0;
-  const bool fp_was_done = c->footprint_done, mask_was_done = c->mask_done;
+  const bool fp_was_done = c->st.footprint_done(), mask_was_done = c->st.mask_done();
   if (want_fp && !fp_was_done)
     return fail(TE_ERR_NOT_READY, "te_run_chain_region: the footprint flag refreshes a complete traversability_footprint layer; run the "
                                   "whole-map footprint pass once first (te_run_chain with TE_RUN_FOOTPRINT, or te_run_footprint)");
@@ -1273,14 +1219,11 @@ int te_run_chain_region(te_ctx* c, unsigned flags, int map, int row0, int col0, 
   changed.j0 = r.j0 - grow < 0 ? 0 : r.j0 - grow;
   changed.i1 = r.i1 + grow > c->geo.rows ? c->geo.rows : r.i1 + grow;
   changed.j1 = r.j1 + grow > c->geo.cols ? c->geo.cols : r.j1 + grow;
-  const ChainParams& q = c->cp;
-  const bool bounded = !c->trav_external && !c->trav_ptr_out && q.w_scale >= 0.0f && q.w_slope >= 0.0f && q.w_step >= 0.0f && q.w_rough >= 0.0f;
-  const double trav_cap = bounded ? (double)q.w_scale * ((double)q.w_slope + (double)q.w_step + (double)q.w_rough) : -1.0;
+  const double trav_cap = trav_cap_now(c, /*fresh*/ false);
   if (int rc2 = ensure_fp_any(c, trav_cap)) return rc2;
   HIP_TRY(launch_footprint(c->geo, c->fp, c->L, usable_face_flags(c), c->cmem.spiral.as<unsigned>(), c->cmem.fp_clip_table.as<int>(), (flags & TE_RUN_FOOTPRINT_MEMO) != 0, nullptr, trav_cap,
                            c->stream, &changed));
-  c->footprint_done = true;  // complete before, refreshed where it could change
-  c->mask_done = mask_was_done;  // (likewise the mask -- unless a score layer was uploaded since it was built)
+  c->st.region_footprint_refreshed(mask_was_done);
   return TE_OK;
 }
 

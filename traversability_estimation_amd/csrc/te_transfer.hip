@@ -19,13 +19,9 @@ int te_upload_elevation(te_ctx* c, const float* host, int map0, int nmaps) {
   HIP_TRY(hipSetDevice(c->device));
   const size_t per = (size_t)c->geo.rows * c->geo.cols;
   HIP_TRY(c->stager.upload(c->L.elev + per * map0, host, per * nmaps * sizeof(float), c->stream));
+  c->st.elevation_replaced();
   // (the count also waits for the copy: the host buffer may be reused as soon as we return)
-  if (const int rc = count_invalid_elevation(c)) return rc;
-  c->have_elev = true;
-  c->chain_done = false;
-  c->footprint_done = false;
-  c->mask_done = false;
-  return TE_OK;
+  return count_invalid_elevation(c);
 }
 
 int te_upload_tile(te_ctx* c, const float* host_tile, int map, int row0, int col0, int h, int w) {
@@ -42,9 +38,7 @@ int te_upload_tile(te_ctx* c, const float* host_tile, int map, int row0, int col
   HIP_TRY(hipMemcpy2DAsync(dst, (size_t)c->geo.rows * sizeof(float), host_tile, (size_t)h * sizeof(float),
                            (size_t)h * sizeof(float), (size_t)w, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->have_elev = true;
-  c->invalid_cells = -1;  // tiles are not counted: the count of the last whole upload says nothing about them (dense march)
-  c->face_crit = __builtin_nan("");  // ... and neither do its face flags (te_face_flags.h): unknown until the next whole upload
+  c->st.elevation_tile_written();
   return TE_OK;
 }
 
@@ -114,9 +108,7 @@ int te_upload_tile_async(te_ctx* c, const float* host_tile, int map, int row0, i
   HIP_TRY(hipEventRecord(sl.freed, c->stream));
   sl.used = true;
   c->tiles_pending = true;
-  c->have_elev = true;
-  c->invalid_cells = -1;  // (as te_upload_tile)
-  c->face_crit = __builtin_nan("");
+  c->st.elevation_tile_written();
   return TE_OK;
 }
 
@@ -159,17 +151,8 @@ int te_device_ptr(te_ctx* c, int layer, void** dptr, size_t* bytes) {
   if (!p) return fail(TE_ERR_INVALID_ARG, "te_device_ptr: bad layer %d", layer);
   *dptr = p;
   if (bytes) *bytes = c->layer_elems * sizeof(float);
-  if (layer == TE_LAYER_TRAVERSABILITY) c->trav_external = c->trav_ptr_out = true;
-  if (layer == TE_LAYER_SLOPE || layer == TE_LAYER_STEP || layer == TE_LAYER_ROUGHNESS) c->mask_done = false;  // (the mask reads them)
-  if (layer == TE_LAYER_ELEVATION) {  // caller fills the elevation in place (zero-copy producer)
-    c->invalid_cells = -1;
-    c->face_crit = __builtin_nan("");  // (the face flags describe the last whole upload ...
-    c->elev_ptr_out = true;            // ... and a write through the pointer behind a later one would go unseen: te_ctx.h)
-    c->have_elev = true;
-    c->chain_done = false;
-    c->footprint_done = false;
-    c->mask_done = false;
-  }
+  if (layer == TE_LAYER_ELEVATION) c->st.elevation_pointer_out();  // caller fills the elevation in place (zero-copy producer)
+  c->st.layer_written(layer, CtxState::kPointerOut);
   return TE_OK;
 }
 
@@ -178,7 +161,7 @@ int te_set_layer_present(te_ctx* c, int layer, int present) {
   CtxLock lk(c);
   if (layer != TE_LAYER_ROBOT_SLOPE) return fail(TE_ERR_INVALID_ARG, "te_set_layer_present: only the optional input layer robot_slope can be declared present / absent");
   if (present && !c->lmem.robot_slope.p) return fail(TE_ERR_NOT_READY, "te_set_layer_present: robot_slope was never uploaded nor handed out (te_device_ptr)");
-  c->have_robot_slope = present != 0;
+  c->st.robot_slope_present(present != 0);
   return TE_OK;
 }
 
@@ -196,9 +179,7 @@ int te_upload_layer(te_ctx* c, int layer, const float* host, int map0, int nmaps
   const size_t per = (size_t)c->geo.rows * c->geo.cols;
   HIP_TRY(c->stager.upload(p + per * map0, host, per * nmaps * sizeof(float), c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (layer == TE_LAYER_ROBOT_SLOPE) c->have_robot_slope = true;
-  if (layer == TE_LAYER_TRAVERSABILITY) c->trav_external = c->trav_ptr_out = true;
-  if (layer == TE_LAYER_SLOPE || layer == TE_LAYER_STEP || layer == TE_LAYER_ROUGHNESS) c->mask_done = false;  // (the mask reads them)
+  c->st.layer_written(layer, CtxState::kUploaded);
   return TE_OK;
 }
 
@@ -255,15 +236,10 @@ static int upload_layer_circular_checked(te_ctx* c, int layer, const float* host
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(copy_circular(c, p + (size_t)map * c->geo.rows * c->geo.cols, const_cast<float*>(host), start_row, start_col, true));
   if (layer == TE_LAYER_ELEVATION) {
-    if (const int rc = count_invalid_elevation(c)) return rc;
-    c->have_elev = true;
-    c->chain_done = false;
-    c->footprint_done = false;
-    c->mask_done = false;
+    c->st.elevation_replaced();
+    return count_invalid_elevation(c);
   }
-  if (layer == TE_LAYER_ROBOT_SLOPE) c->have_robot_slope = true;
-  if (layer == TE_LAYER_TRAVERSABILITY) c->trav_external = c->trav_ptr_out = true;
-  if (layer == TE_LAYER_SLOPE || layer == TE_LAYER_STEP || layer == TE_LAYER_ROUGHNESS) c->mask_done = false;  // (the mask reads them)
+  c->st.layer_written(layer, CtxState::kUploaded);
   return TE_OK;
 }
 
@@ -396,18 +372,12 @@ static int upload_image_checked(const char* who, te_ctx* c, const te_image_info*
   HIP_TRY(img::launch_to_layer(stage.p, *info, p + (size_t)map * c->geo.rows * c->geo.cols, lower, upper,
                                img::alpha_threshold_sample(alpha_threshold, info->bytes_per_channel), c->stream));
   if (layer == TE_LAYER_ELEVATION) {
+    c->st.elevation_replaced();
     // (the count also waits for the copy and the kernel: the host buffer may be reused as soon as we return)
-    if (const int rc = count_invalid_elevation(c)) return rc;
-    c->have_elev = true;
-    c->chain_done = false;
-    c->footprint_done = false;
-    c->mask_done = false;
-  } else {
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    return count_invalid_elevation(c);
   }
-  if (layer == TE_LAYER_ROBOT_SLOPE) c->have_robot_slope = true;
-  if (layer == TE_LAYER_TRAVERSABILITY) c->trav_external = c->trav_ptr_out = true;
-  if (layer == TE_LAYER_SLOPE || layer == TE_LAYER_STEP || layer == TE_LAYER_ROUGHNESS) c->mask_done = false;  // (the mask reads them)
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->st.layer_written(layer, CtxState::kUploaded);
   return TE_OK;
 }
 
