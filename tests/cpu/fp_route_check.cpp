@@ -1,5 +1,5 @@
 // fp_route_check.cpp -- the route of the circular footprint pass from the header launch_footprint routes
-// with (te_fp_route.h), on the disc and the spiral of te_fp_table.h (the tables the shim builds).  tests/test_fp_route.py.
+// with (te_fp_route.h), on the disc of te_disc.h and the spiral of te_fp_table.h (the tables the shim builds).  tests/test_fp_route.py.
 //   fp_route_check cases         one line per named case: "name route k strip_rows chunk blocked"
 //   fp_route_check sweep N SEED  N seeded cases; every route is held to what its kernels rely on: "N cases, F failed checks"
 #include <cmath>
@@ -8,6 +8,7 @@
 #include <cstring>
 #include <random>
 
+#include "te_disc.h"
 #include "te_fp_route.h"
 #include "te_fp_table.h"
 
@@ -29,7 +30,7 @@ struct Case {
   double list_scale = 1.0;  // the list the shim allocates (cells + fp_list_slack), or less
 };
 
-// the route's inputs as launch_footprint fills them, the disc and the spiral from te_fp_table.h
+// the route's inputs as launch_footprint fills them: the disc and its tie summary from te_disc.h, the spiral from te_fp_table.h
 static FpRouteIn inputs(const Case& c) {
   const double res = 0.05;
   FpTable t;
@@ -52,6 +53,16 @@ static FpRouteIn inputs(const Case& c) {
     const int di = t.ties[2 * k], dj = t.ties[2 * k + 1];
     in.ties_on_circle = in.ties_on_circle && di * di + dj * dj == in.reach * in.reach;
     in.n_gen += di != 0 && dj != 0;
+  }
+  // Above 32 cells build_disc refuses and the shim builds no fp_disc (the route of any reach serves the pass); the cases here
+  // reach further and keep the values derived from the table above.  Every other case takes them as launch_footprint does:
+  Disc d;
+  if (build_disc(c.rmax_cells * res, res, &d) == kDiscOk) {
+    in.R = d.R;
+    in.Q = d.Q;
+    in.npoints = d.npoints;
+    in.n_ties = d.n_ties;
+    tie_summary(d, in.reach, &in.ties_on_circle, &in.n_gen);
   }
   in.n_spiral = (int)t.spiral.size();
   in.rmin = c.rmin_cells * res;

@@ -1,7 +1,7 @@
 """te_disc_table.h on the CPU: the filter discs of any radius (te_filter_any.hip).  The table is the disc the oracle's
 CircleIterator visits -- runs counted inside the map, tie offsets decided per centre with isInside's own formula -- at
 several centres and map origins for radii of 0.3 to 125 cells, and it is build_disc's disc for every radius build_disc
-accepts (a sweep in tests/cpu/disc_table_check.cpp)."""
+(te_disc.h, the function the library ships) accepts (a sweep in tests/cpu/disc_table_check.cpp)."""
 import os
 import subprocess
 

@@ -47,7 +47,7 @@ def params(oracle):
 
 
 def tie_offsets(radius, res):
-    """build_disc (te_shim.hip): the offsets whose squared norm equals (radius / res)^2 to within 1e-9 relative."""
+    """build_disc (te_disc.h): the offsets whose squared norm equals (radius / res)^2 to within 1e-9 relative."""
     q = (radius / res) * (radius / res)
     tol = 1e-9 * max(q, 1.0)
     lim = int(np.floor(np.sqrt(q + tol))) + 1

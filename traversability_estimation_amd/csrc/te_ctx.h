@@ -3,6 +3,8 @@
 //   te_transfer.hip  uploads / downloads: whole layers, tiles, circular-buffer order, GridMap messages, prefetch, pinning
 //   te_paths_api.hip path checks, inclination, polygon footprint layers (N2, N3)
 //   te_multi.hip     the batch axis over several contexts / devices (te_shard_range, te_bcast_params over RCCL, *_multi)
+// The tables the shim uploads are built by plain C++ headers the CPU checks compile too: te_disc.h (discs, tie circle, clip
+// table), te_disc_table.h (discs of any radius), te_fp_table.h (footprint spiral and inner rings).
 // No CPU fallback of any kind: without a gfx950 device te_create() fails with TE_ERR_NO_DEVICE.
 //
 // Device memory: every allocation the context keeps is a DevBuf (te_devbuf.h) declared in one of two groups, and the group

@@ -1,7 +1,7 @@
 // te_disc_table.h -- host table of a filter disc of any radius (te_filter_any.hip).
 //
 // The disc {(di, dj): di^2 + dj^2 <= (radius / res)^2} of the normals, roughness and step windows, in the form build_disc
-// (te_shim.hip) gives it, without its bounds (kMaxRadiusCells rows, kMaxTies offsets on the circle):
+// (te_disc.h) gives it, without its bounds (kMaxRadiusCells rows, kMaxTies offsets on the circle):
 //   - the row runs: column offset dj (|dj| <= R) holds di in [-hw[|dj|], hw[|dj|]];
 //   - the tie offsets: squared norm equal to (radius / res)^2 to within 1e-9 relative; CircleIterator decides them per
 //     centre from rounded double positions, the kernels with the same formula -- any number of them;
@@ -73,7 +73,7 @@ inline void build_disc_table(double radius, double res, DiscTable* t) {
   if (t->R >= 0 && t->hw[0] > t->reach) t->reach = t->hw[0];
 }
 
-// same_disc (te_shim.hip) for tables: the same cells, and the same per-centre test of the ties
+// same_disc (te_disc.h) for tables: the same cells, and the same per-centre test of the ties
 inline bool same_disc_table(const DiscTable& a, const DiscTable& b) {
   if (a.R != b.R || a.hw != b.hw || a.ties.size() != b.ties.size()) return false;
   if (!a.ties.empty() && a.r2 != b.r2) return false;

@@ -15,6 +15,7 @@
 //             double, so the result equals the reference's spiral-order sum bit for bit); otherwise the
 //             lane walks the host-built spiral table (SpiralIterator order) over the rows already staged
 //             in LDS until the first untraversable cell, exactly like isTraversable().
+#include "te_fp_table.h"
 #include "te_internal.h"
 
 #include <cstdlib>
@@ -1231,7 +1232,7 @@ bool footprint_slide_general(const Geo& g, const FootprintParams& p, const Layer
   a.rmin = p.rmin;
   a.rmax = p.rmax;
   a.def = p.def;
-  a.inner_q = fast::footprint_inner_q(g.res, p.rmin, p.rmax);
+  a.inner_q = footprint_inner_q(g.res, p.rmin, p.rmax);
   {  // one round of resident waves (kFpWaves per SIMD): as many strips as fit
     const int nbx = (g.rows + kLanes - 1) / kLanes;
     const int Rk = p.reach;
@@ -1366,12 +1367,7 @@ hipError_t launch_footprint(const Geo& g, const FootprintParams& p, const Layers
   in.Q = d.Q;
   in.npoints = d.npoints;
   in.n_ties = d.n_ties;
-  in.ties_on_circle = true;
-  in.n_gen = 0;
-  for (int t = 0; t < d.n_ties; ++t) {
-    in.ties_on_circle = in.ties_on_circle && (int)d.tie_di[t] * d.tie_di[t] + (int)d.tie_dj[t] * d.tie_dj[t] == p.reach * p.reach;
-    in.n_gen += (d.tie_di[t] != 0 && d.tie_dj[t] != 0) ? 1 : 0;
-  }
+  tie_summary(d, p.reach, &in.ties_on_circle, &in.n_gen);
   in.reach = p.reach;
   in.n_spiral = p.n_spiral;
   in.rmin = p.rmin;

@@ -10,6 +10,7 @@
 // that is what counts on gfx950): ring of exactly 2R+2 rows addressed through rotating chunk base registers with
 // immediate offsets (no scalar ring bookkeeping: the old kernel issued 65 scalar instructions per row), one running
 // scalar row pointer per layer, 11-12 single-wave blocks per CU instead of 8.
+#include "te_fp_table.h"
 #include "te_internal.h"
 #include "te_march.h"
 
@@ -403,15 +404,6 @@ bool f3_launch_part2(int Q, const void* args, int batch, hipStream_t s);
 bool f3_launch_part3(int Q, const void* args, int batch, hipStream_t s);
 bool f3_launch_part4(int Q, const void* args, int batch, hipStream_t s);
 #endif
-
-// Largest di^2 + dj^2 of the spiral rings that lie within the inner radius (ring * res <= rmin, getCurrentRadius()'s
-// integer norm) and that SpiralIterator takes without its circle test (all but the two outermost); -1: no such ring.
-int footprint_inner_q(double res, double rmin, double rmax) {
-  const int nrings = (int)ceil(rmax / res);
-  int d = -1;
-  while (d + 1 <= nrings - 2 && (double)(d + 1) * res <= rmin) ++d;
-  return d < 0 ? -1 : (d + 1) * (d + 1) - 1;
-}
 
 // The sliding-sum kernel of the footprint pass for a tie-free disc on its route (plan_fp_route); false: the shape is not
 // instantiated.

@@ -80,7 +80,7 @@ inline size_t fp_list_slack(int rows, int cols, int batch, int cus) {
 enum FpRouteKind { kFpSlide5, kFpSlide4, kFpSlide3, kFpGeneral, kFpAny };
 
 struct FpRouteIn {
-  // the footprint disc (build_disc) and its spiral
+  // the footprint disc (build_disc and tie_summary of te_disc.h) and its spiral
   int R, Q, npoints, n_ties;
   bool ties_on_circle;  // every tie offset has the squared norm reach^2 (a whole-cell radius)
   int n_gen;            // tie offsets with both parts non-zero

@@ -8,6 +8,7 @@
 
 #include <vector>
 
+#include "te_disc.h"
 #include "te_face_flags.h"
 #include "te_fp_route.h"
 #include "te_slab.h"
@@ -43,12 +44,10 @@ class TraceRange {
 };
 bool trace_available();
 
-constexpr int kMaxRadiusCells = 32;  // largest stencil radius (in cells) a launch supports
 // The marching kernels of te_march5.h load the rows above / below a map unconditionally (and stage them as "nothing
 // there"): up to the stencil radius above the first row, and the radius plus the prefetch distance below the last.  The
 // context's slab therefore starts and ends with this many rows of slack (kSlabGuardRows of te_slab.h, the plan of the slab).
 static_assert(kSlabGuardRows == kMaxRadiusCells + 16, "te_slab.h: the guard rows cover the largest radius and the prefetch distance");
-constexpr int kMaxTies = 32;         // offsets lying exactly on the circle (tie radii)
 constexpr int kMaxSpiral = 4096;     // ordered offsets of the footprint spiral
 
 // Map geometry as the kernels need it.  Device layout of every layer: [batch][cols][rows] float32,
@@ -58,27 +57,6 @@ struct Geo {
   double res;
   double ax, ay;  // position of cell 0: pos + (0.5*len - 0.5*res); x(i) = ax + res*(-i)
   double len_x, len_y, pos_x, pos_y;
-};
-
-// A disc {(di,dj): di^2+dj^2 <= (radius/res)^2} as row runs: for column offset dj (|dj|<=R) the cells
-// di in [-hw[|dj|], hw[|dj|]].  Offsets whose squared norm equals (radius/res)^2 up to rounding are
-// NOT in the runs: whether CircleIterator keeps them depends on the double rounding of the cell
-// positions, so they are listed in `tie_*` and tested per cell with the reference's own formula.
-struct Disc {
-  int R;                         // largest |offset| in the runs (-1: empty disc)
-  int hw[kMaxRadiusCells + 1];   // -1 where the run is empty
-  int n_ties;
-  int8_t tie_di[kMaxTies], tie_dj[kMaxTies];
-  double r2;                     // radius*radius (double, as CircleIterator computes it)
-  int reach;                     // max(R, max |tie offset|)
-  int npoints;                   // number of cells in the runs (full disc, away from borders)
-  int Q;                         // tie-free discs: largest a^2+b^2 <= (radius/res)^2 (names the shape); -1 with ties
-  // TE_OPT_FILTER_ANY_RADIUS: a disc the fixed arrays above do not hold (or every disc under option 2) takes the kernels of
-  // te_filter_any.hip.  Its runs and ties are in the device table `tab` (te_disc_table.h: hw[0 .. R], then n_ties (di, dj)
-  // int32 pairs); hw[] holds -1 and Q is -1, and every other kernel's route refuses the disc.
-  int any;
-  int any_hw0;                   // (host copy of tab[0]: the widest run)
-  const int* tab;
 };
 
 struct ChainParams {
@@ -404,7 +382,6 @@ bool normals_fast(const Geo& g, const ChainParams& p, const Layers& L, bool keep
 // te_slide_normals.hip: RoughnessFilter alone with the normals of the layers (false: shape / map not taken)
 bool roughness_given_fast(const Geo& g, const ChainParams& p, const Layers& L, const Region& r, int* block_flags, FastGrid* fg, hipStream_t s);
 // te_normals3.hip: the cells whose disc lies inside the map (false: shape / region not taken)
-int footprint_inner_q(double res, double rmin, double rmax);  // te_footprint3.hip
 bool normals_fast3(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, const Region& r, int* block_flags,
                    FastGrid* fg, hipStream_t s);
 // te_normals_small.hip: discs that reach at most two cells (the one-cell tie radius of the default parameters on a 0.05 m
@@ -434,7 +411,6 @@ constexpr int kFpClipInts = 6 * 41 * 41;  // one clip table of the footprint dis
                                            // radius: the disc with the cells on its circle (k_fp_slide4<Q, true>)
 // the second half of a fixed-point pass (FpRoute::blocked): the listed cells, after every launch of the pass
 void footprint_blocked4(const Geo& g, const FootprintParams& p, const Layers& L, const unsigned* ptab, hipStream_t s);
-void build_clip_table(const Disc& d, int Rk, int* out);  // (2*Rk+1)^2 * 6 ints, clip codes relative to radius Rk
 }  // namespace fast
 
 }  // namespace te

@@ -22,65 +22,12 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-// Build the row-run table of the disc {di^2+dj^2 <= (radius/res)^2}.  Offsets whose squared norm
-// equals (radius/res)^2 to within 1e-9 relative are "ties": the reference decides them per cell
-// from rounded double positions, so the kernels test them with the same formula.
-int build_disc(double radius, double res, Disc* d, const char* what) {
-  memset(d, 0, sizeof(*d));
-  d->r2 = radius * radius;
-  const double q = (radius / res) * (radius / res);
-  const double tol = 1e-9 * (q > 1.0 ? q : 1.0);
-  const double rmax = sqrt(q + tol);
-  if (!(rmax < (double)kMaxRadiusCells + 0.5))
-    return fail(TE_ERR_UNSUPPORTED, "%s radius %.6g m is %.2f cells; this build supports up to %d", what, radius,
-                radius / res, kMaxRadiusCells);
-  const int lim = (int)floor(rmax) + 1;
-  d->R = -1;
-  d->reach = 0;
-  d->npoints = 0;
-  for (int b = 0; b <= kMaxRadiusCells; ++b) d->hw[b] = -1;
-  for (int b = 0; b <= lim && b <= kMaxRadiusCells; ++b) {
-    int hw = -1;
-    for (int a = 0; a <= lim; ++a) {
-      const double m = (double)(a * a + b * b);
-      if (fabs(m - q) <= tol) {
-        // tie: all sign combinations, each listed once
-        for (int sa = -1; sa <= 1; sa += 2)
-          for (int sb = -1; sb <= 1; sb += 2) {
-            if ((a == 0 && sa < 0) || (b == 0 && sb < 0)) continue;
-            if (d->n_ties >= kMaxTies) return fail(TE_ERR_UNSUPPORTED, "%s radius: too many tie offsets", what);
-            d->tie_di[d->n_ties] = (int8_t)(sa * a);
-            d->tie_dj[d->n_ties] = (int8_t)(sb * b);
-            d->n_ties++;
-            const int mx = a > b ? a : b;
-            if (mx > d->reach) d->reach = mx;
-          }
-      } else if (m < q) {
-        hw = a;
-      }
-    }
-    d->hw[b] = hw;
-    if (hw >= 0) {
-      d->R = b;
-      d->npoints += (b == 0 ? 1 : 2) * (2 * hw + 1);
-    }
-  }
-  // rows are nested (hw non-increasing) and a tie at (a,b) always sits right after the run end, so
-  // runs never skip an interior cell.
-  if (d->R > d->reach) d->reach = d->R;
-  if (d->hw[0] > d->reach) d->reach = d->hw[0];
-  // the shape is named by the largest sum of two squares not above q (only meaningful without ties)
-  d->Q = -1;
-  if (d->n_ties == 0) {
-    int best = -1;
-    for (int a = 0; a <= lim; ++a)
-      for (int b = 0; b <= lim; ++b) {
-        const int m = a * a + b * b;
-        if ((double)m < q && m > best) best = m;
-      }
-    d->Q = best;  // -1: radius below zero cells cannot happen (m = 0 < q unless q == 0, which is a tie)
-  }
-  return TE_OK;
+// build_disc (te_disc.h) for the window `what`, its refusals as the error of the entry point
+int named_disc(double radius, double res, Disc* d, const char* what) {
+  const DiscStatus st = build_disc(radius, res, d);
+  if (st == kDiscTooLarge)
+    return fail(TE_ERR_UNSUPPORTED, "%s radius %.6g m is %.2f cells; this build supports up to %d", what, radius, radius / res, kMaxRadiusCells);
+  return st == kDiscTooManyTies ? fail(TE_ERR_UNSUPPORTED, "%s radius: too many tie offsets", what) : TE_OK;
 }
 
 // A filter disc: build_disc's fixed arrays, or under TE_OPT_FILTER_ANY_RADIUS the table of any radius (te_disc_table.h) --
@@ -90,7 +37,7 @@ int filter_disc(te_ctx* c, double radius, Disc* d, DiscTable* t, const char* wha
   if (c->opt_filter_any != 2) {
     char before[sizeof(g_err)];
     memcpy(before, g_err, sizeof(before));
-    const int rc = build_disc(radius, c->geo.res, d, what);
+    const int rc = named_disc(radius, c->geo.res, d, what);
     if (rc == TE_OK || c->opt_filter_any == 0) return rc;
     memcpy(g_err, before, sizeof(before));  // (the refusal is not an error under option 1)
   }
@@ -131,14 +78,6 @@ int upload_any_discs(te_ctx* c) {
   for (int k = 0; k < 4; ++k)  // (every Disc::tab is derived again: the buffer may have moved)
     if (ds[k]->any) ds[k]->tab = c->cmem.fa_tab.as<const int>() + off[k];
   return TE_OK;
-}
-
-bool same_disc(const Disc& a, const Disc& b) {
-  if (a.R != b.R || a.n_ties != b.n_ties) return false;
-  for (int k = 0; k <= kMaxRadiusCells; ++k)
-    if (a.hw[k] != b.hw[k]) return false;
-  if (a.n_ties && a.r2 != b.r2) return false;
-  return true;
 }
 
 }  // namespace shim
@@ -427,33 +366,15 @@ static int fp_any_alloc(te_ctx* c, DevBuf& buf, size_t bytes, const char* what) 
 }
 
 // The tables of the route of any reach (te_footprint_any.hip) on the device: run half-widths, those of the inner disc (the
-// rings within radiusMin that the SpiralIterator takes whole, fast::footprint_inner_q), the tie offsets, the spiral; and
+// rings within radiusMin that the SpiralIterator takes whole, fp_inner_rings of te_fp_table.h), the tie offsets, the spiral; and
 // the prefix-sum scratch of the maps.  Allocated here and never inside a launch (whole-map launches are captured).
 int build_fp_any_tables(te_ctx* c, const FpTable& t) {
   FootprintParams& f = c->fp;
   const Geo& g = c->geo;
   std::vector<int32_t> ints(t.hw.begin(), t.hw.end());
   f.any_R = t.R;
-  f.any_inner_R = -1;
-  f.any_k_inner = 0;
-  const int inner_q = fast::footprint_inner_q(g.res, f.rmin, f.rmax);
-  if (inner_q >= 0) {  // cells with di^2 + dj^2 <= inner_q: rings 0 .. d with (d + 1)^2 = inner_q + 1
-    auto isqrt = [](long long v) {
-      long long r = (long long)sqrt((double)v);
-      while (r * r > v) --r;
-      while ((r + 1) * (r + 1) <= v) ++r;
-      return r;
-    };
-    const long long d = isqrt((long long)inner_q + 1) - 1;
-    for (long long b = 0; b <= isqrt(inner_q) && b < g.cols; ++b) {
-      const long long a = isqrt((long long)inner_q - b * b);
-      ints.push_back((int32_t)(a > g.rows - 1 ? g.rows - 1 : a));
-      f.any_inner_R = (int)b;
-    }
-    while (f.any_k_inner < (int)t.spiral.size() && t.spiral[f.any_k_inner].ring <= d) ++f.any_k_inner;
-    for (size_t k = f.any_k_inner; k < t.spiral.size(); ++k)
-      if (t.spiral[k].ring <= d) return fail(TE_ERR_UNSUPPORTED, "footprint: the inner rings are not a prefix of the spiral");
-  }
+  if (!fp_inner_rings(t, footprint_inner_q(g.res, f.rmin, f.rmax), g.rows, g.cols, &ints, &f.any_inner_R, &f.any_k_inner))
+    return fail(TE_ERR_UNSUPPORTED, "footprint: the inner rings are not a prefix of the spiral");
   ints.insert(ints.end(), t.ties.begin(), t.ties.end());
   f.any_n_ties = (int)t.ties.size() / 2;
   f.any_n_spiral = (int)t.spiral.size();
@@ -499,8 +420,8 @@ int rebuild_footprint_tables_impl(te_ctx* c) {
   // ---- circular footprint: discs of the three checks, spiral order, clip table ----------------------
   {
     FootprintParams& f = c->fp;
-    if ((rc = build_disc(3.0 * res, res, &f.slope_disc, "footprint slope window"))) return rc;   // TraversabilityMap.cpp:871
-    if ((rc = build_disc(2.5 * res, res, &f.step_disc, "footprint step window"))) return rc;     // :798
+    if ((rc = named_disc(3.0 * res, res, &f.slope_disc, "footprint slope window"))) return rc;   // TraversabilityMap.cpp:871
+    if ((rc = named_disc(2.5 * res, res, &f.step_disc, "footprint step window"))) return rc;     // :798
     f.rmin = p.fp_radius;
     f.rmax = p.fp_radius + p.fp_offset;  // :312 isTraversable(center, radius + offset, ..., radius)
     f.def = p.fp_default;
@@ -525,7 +446,7 @@ int rebuild_footprint_tables_impl(te_ctx* c) {
       f.n_spiral = 0;
       return build_fp_any_tables(c, any);
     }
-    if ((rc = build_disc(f.rmax, res, &f.fp_disc, "footprint"))) return rc;
+    if ((rc = named_disc(f.rmax, res, &f.fp_disc, "footprint"))) return rc;
     const Disc& d = f.fp_disc;
     // the same spiral unclipped (the kernels clip it per centre), one packed word per entry: the kernels' spiral walks read
     // it with scalar loads, eight entries at a time
@@ -538,29 +459,20 @@ int rebuild_footprint_tables_impl(te_ctx* c) {
     std::vector<uint32_t> packed(f.n_spiral);
     for (int k = 0; k < f.n_spiral; ++k) packed[k] = fp_pack(sp.spiral[k]);
     std::vector<int> ctab((size_t)(2 * f.reach + 1) * (2 * f.reach + 1) * 6);
-    fast::build_clip_table(d, f.reach, ctab.data());
+    build_clip_table(d, f.reach, ctab.data());
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(c->cmem.spiral.once(sizeof(uint32_t) * kMaxSpiral));
     HIP_TRY(hipMemcpyAsync(c->cmem.spiral.p, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c->cmem.fp_clip_table.once(sizeof(int) * (2 * fast::kFpClipInts + kMaxTies)));
     int* const fp_clip_table = c->cmem.fp_clip_table.as<int>();
     std::vector<int> ctab_full;
-    int gen_tab[kMaxTies];
-    if (d.n_ties) {  // the disc with the cells on its circle (fixed-point sliding sum of a tie radius, te_footprint4.hip)
-      Disc full = d;
-      for (int t = 0; t < d.n_ties; ++t) {
-        const int ai = abs((int)d.tie_di[t]), aj = abs((int)d.tie_dj[t]);
-        if (full.hw[aj] < ai) full.hw[aj] = ai;
-        if (full.R < aj) full.R = aj;
-      }
+    TieCircle tc;
+    if (d.n_ties) {  // the disc with the cells on its circle (fixed-point sliding sum of a tie radius, te_footprint4.hip) ...
+      build_tie_circle(d, &tc);  // ... and the offsets on the circle with both parts non-zero, packed, behind it
       ctab_full.resize(ctab.size());
-      fast::build_clip_table(full, f.reach, ctab_full.data());
+      build_clip_table(tc.full, f.reach, ctab_full.data());
       HIP_TRY(hipMemcpyAsync(fp_clip_table + fast::kFpClipInts, ctab_full.data(), ctab_full.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-      // ... and the offsets on the circle with both parts non-zero, packed (the kernel handles (+-R, 0) and (0, +-R) itself)
-      int n_gen = 0;
-      for (int t = 0; t < d.n_ties; ++t)
-        if (d.tie_di[t] != 0 && d.tie_dj[t] != 0) gen_tab[n_gen++] = ((int)d.tie_di[t] & 0xff) | (((int)d.tie_dj[t] & 0xff) << 8);
-      if (n_gen) HIP_TRY(hipMemcpyAsync(fp_clip_table + 2 * fast::kFpClipInts, gen_tab, n_gen * sizeof(int), hipMemcpyHostToDevice, c->stream));
+      if (tc.n_gen) HIP_TRY(hipMemcpyAsync(fp_clip_table + 2 * fast::kFpClipInts, tc.gen, tc.n_gen * sizeof(int), hipMemcpyHostToDevice, c->stream));
     }
     HIP_TRY(hipMemcpyAsync(fp_clip_table, ctab.data(), ctab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -621,28 +533,15 @@ int rebuild_tables(te_ctx* c) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(c->cmem.clip_table.once(sizeof(int) * (2 * fast::kClipInts + kMaxTies)));
     int* const clip_table = c->cmem.clip_table.as<int>();
-    std::vector<int> tab, tab_full;
-    int gen_tab[kMaxTies];
-    if (dn.n_ties == 0) {
-      const int R = dn.R;
-      tab.resize((size_t)(2 * R + 1) * (2 * R + 1) * 6);
-      fast::build_clip_table(dn, R, tab.data());
-      HIP_TRY(hipMemcpyAsync(clip_table, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    } else {
-      Disc full = dn;
-      int n_gen = 0;
-      for (int t = 0; t < dn.n_ties; ++t) {
-        const int ai = abs((int)dn.tie_di[t]), aj = abs((int)dn.tie_dj[t]);
-        if (full.hw[aj] < ai) full.hw[aj] = ai;
-        if (full.R < aj) full.R = aj;
-        if (dn.tie_di[t] != 0 && dn.tie_dj[t] != 0) gen_tab[n_gen++] = ((int)dn.tie_di[t] & 0xff) | (((int)dn.tie_dj[t] & 0xff) << 8);
-      }
-      const int R = dn.reach;
-      tab_full.resize((size_t)(2 * R + 1) * (2 * R + 1) * 6);
-      fast::build_clip_table(full, R, tab_full.data());
-      HIP_TRY(hipMemcpyAsync(clip_table + fast::kClipInts, tab_full.data(), tab_full.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-      if (n_gen) HIP_TRY(hipMemcpyAsync(clip_table + 2 * fast::kClipInts, gen_tab, n_gen * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    }
+    // tie-free: the disc's table at R = dn.R, first; a tie radius: the full table at R = dn.reach, second, and no first one
+    const bool ties = dn.n_ties != 0;
+    const int R = ties ? dn.reach : dn.R;
+    TieCircle tc;
+    if (ties) build_tie_circle(dn, &tc);
+    std::vector<int> tab((size_t)(2 * R + 1) * (2 * R + 1) * 6);
+    build_clip_table(ties ? tc.full : dn, R, tab.data());
+    HIP_TRY(hipMemcpyAsync(clip_table + (ties ? fast::kClipInts : 0), tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (ties && tc.n_gen) HIP_TRY(hipMemcpyAsync(clip_table + 2 * fast::kClipInts, tc.gen, tc.n_gen * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
   c->L.clip_table = c->cmem.clip_table.as<int>();

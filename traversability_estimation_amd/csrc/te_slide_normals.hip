@@ -678,32 +678,6 @@ bool roughness_given_fast(const Geo& g, const ChainParams& p, const Layers& L, c
   }
 }
 
-// Host side: x/y moments of the disc clipped to di in [lo_i, hi_i], dj in [lo_j, hi_j] for every clip
-// code (kx, ky) in [-R, R]^2 (see k_normals_slide).  out must hold (2R+1)^2 * 6 ints.
-void build_clip_table(const Disc& d, int R, int* out) {
-  for (int ky = -R; ky <= R; ++ky)
-    for (int kx = -R; kx <= R; ++kx) {
-      const int lo_i = kx > 0 ? -R + kx : -R, hi_i = kx < 0 ? R + kx : R;
-      const int lo_j = ky > 0 ? -R + ky : -R, hi_j = ky < 0 ? R + ky : R;
-      int n = 0, si = 0, sj = 0, sii = 0, sij = 0, sjj = 0;
-      for (int dj = lo_j; dj <= hi_j; ++dj) {
-        const int adj = dj < 0 ? -dj : dj;
-        const int hw = adj <= d.R ? d.hw[adj] : -1;
-        for (int di = -hw; di <= hw; ++di) {
-          if (di < lo_i || di > hi_i) continue;
-          ++n;
-          si += di;
-          sj += dj;
-          sii += di * di;
-          sij += di * dj;
-          sjj += dj * dj;
-        }
-      }
-      int* e = out + ((ky + R) * (2 * R + 1) + (kx + R)) * 6;
-      e[0] = n; e[1] = si; e[2] = sj; e[3] = sii; e[4] = sij; e[5] = sjj;
-    }
-}
-
 int normals_fast_max_blocks(const Geo& g) {
   const int ntiles = ((g.rows + kLanes - 1) / kLanes) * ((g.cols + 15) / 16) * g.batch;  // one flag per 64x16 tile ...
   // ... at (t % groups) * kFixTiles + t / groups; a region run has the tile count of its region, so the largest need of
