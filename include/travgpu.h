@@ -57,6 +57,9 @@
  *   te_run_median_fill / te_download_fill_mask
  *                        <- gridMapFilters/MedianFillFilter (grid_map_filters; not in the reference tree: restated, see below),
  *                           the hole filling a grid_map pipeline puts in front of the chain
+ *   te_run_radius_filter / te_radius_filter_stats
+ *                        <- gridMapFilters/MeanInRadiusFilter and MinInRadiusFilter (grid_map_filters; restated, see below):
+ *                           the radial blur between the fill and the normals, and the conservative lower surface
  *
  * Data contract (identical to grid_map::Matrix = Eigen::MatrixXf): float32, COLUMN-major,
  * element (row i, col j) of map m at ptr[m*rows*cols + j*rows + i]; invalid cell = non-finite.
@@ -208,6 +211,10 @@ int te_get_params(te_ctx* ctx, te_params* p);
  * at most 15 cells, the general kernel above), 1 the tile kernel wherever its window fits, 2 the general kernel always.  The
  * layers are identical either way, bit for bit. */
 #define TE_OPT_MEDIAN_ROUTE 10
+/* te_run_radius_filter: 0 (default) the kernel the plan names (csrc/te_radius_plan.h), 1 the sliding kernel wherever its
+ * result is provably exact (its segments fit in LDS; a workgroup of the Mean whose values fail the plan's predicate still runs
+ * the in-order gather), 2 the in-order gather always.  The layers are identical under every value, bit for bit. */
+#define TE_OPT_RADIUS_ROUTE 11
 int te_set_option(te_ctx* ctx, int option, int value);
 /* The face flags a footprint run would be given now (tests, diagnostics): batch x ceil(cols / 4) x ceil(rows / 64) bytes, the
  * flag of 64 cells along the rows fastest; `bytes` must be exactly that.  TE_ERR_NOT_READY while they are unknown or
@@ -815,6 +822,43 @@ int te_download_fill_mask(te_ctx* ctx, int map, unsigned char* out, size_t bytes
  * follows a fill of the elevation (the input must survive the repeats: in_layer != out_layer is required).  p == NULL: a device
  * copy of in_layer into out_layer, the fill's floor. */
 int te_time_median_fill_samples(te_ctx* ctx, const te_median_fill_params* p, int in_layer, int out_layer, int warmup, int iters, float* ms);
+
+/* ---- gridMapFilters/MeanInRadiusFilter and MinInRadiusFilter on the device: smoothing and the lower surface ----
+ * Like the median fill this contract is RESTATED from memory of grid_map_filters; nothing the reference holds pins it.  The
+ * yardstick of the tests is the same contract in numpy (tests/ref_py/radius_filter_ref.py).
+ *   1. disc            for every cell c of the map (valid or not): center = getPosition(c), the window is
+ *      CircleIterator(map, center, radius) -- the disc of csrc/te_disc_table.h: cells outside the map are no cells, cells on
+ *      the circle are decided per centre with the reference's double arithmetic.  The same disc as StepFilter's first window;
+ *   2. iteration order row index ascending outer, column index ascending inner;
+ *   3. values used     a value takes part iff std::isfinite(value): +-inf is skipped like NaN;
+ *   4. Mean            double sum = 0.0; int n = 0; over the window in that order: sum += (double)value; ++n.  The output is
+ *      (float)(sum / n) for n > 0, else NaN (the freshly added layer).  Defined bit for bit, including where partial sums round
+ *      (a disc of -0.0 cells gives +0.0);
+ *   5. Min             the smallest finite value of the window, NaN if there is none: one of the inputs, bit for bit.  Where a
+ *      window holds -0.0 and +0.0 as its minimum upstream's sign depends on the order; here -0.0 sorts below +0.0;
+ *   6. parameters      radius, input_layer, output_layer.  The radius must be finite and >= 0 (TE_ERR_BAD_PARAM + message);
+ *      radius 0 is the centre cell alone;
+ *   7. the same layer in and out behaves as if the input had been copied first (what upstream does with equal names is not
+ *      restated). */
+#define TE_RADIUS_MEAN 1
+#define TE_RADIUS_MIN 2
+/* out_layer = the Mean / Min in `radius` of in_layer for maps [map0, map0 + nmaps) of the batch; the other maps are untouched.
+ * Any two float layers of the context, any radius: the call owns its disc table and does not depend on
+ * TE_OPT_FILTER_ANY_RADIUS.  Exact: identical run after run and between the kernels (TE_OPT_RADIUS_ROUTE).  The Mean's sliding
+ * kernel adds column prefix sums -- another order than 2. -- and a workgroup takes it only where the order provably cannot
+ * matter (csrc/te_radius_plan.h: order_free over the exponents of the cells it reads); otherwise the workgroup walks its windows
+ * in order.  Asynchronous on the context's stream unless out_layer is the elevation.
+ *   TE_ERR_NOT_READY, TE_ERR_INVALID_ARG (also: an op that is neither), TE_ERR_BAD_PARAM (the radius), the context afterwards and
+ *   the joining of a prefetch: as te_run_median_fill.  TE_ERR_UNSUPPORTED: the window table or the copy of the input layer does
+ *   not fit in device memory. */
+int te_run_radius_filter(te_ctx* ctx, int op, double radius, int in_layer, int out_layer, int map0, int nmaps);
+/* Which kernel the last te_run_radius_filter ran: counts[0] = workgroups the sliding kernel settled, counts[1] = workgroups the
+ * in-order gather settled (the gather kernel's own, and those of the sliding Mean that failed the predicate).  Waits for the
+ * call.  TE_ERR_NOT_READY before any call. */
+int te_radius_filter_stats(te_ctx* ctx, uint64_t counts[2]);
+/* Measurement aid (tools/radius_filter_bench.py), like te_time_median_fill_samples: `iters` launches over the whole batch, one
+ * HIP event pair each, after `warmup` untimed ones; in_layer != out_layer is required.  op = 0: a device copy of the layer. */
+int te_time_radius_filter_samples(te_ctx* ctx, int op, double radius, int in_layer, int out_layer, int warmup, int iters, float* ms);
 
 const char* te_last_error(void);
 const char* te_version(void);

@@ -32,6 +32,8 @@ OPT_FP_BLOCKED_WALK, OPT_FP_BLOCKED_BLOCKS_PER_CU, OPT_POLYGON_PER_CELL, OPT_GRA
 OPT_FP_ANY_REACH = 7  # circular footprint: 0 routes by reach (above 20 cells: the route of any reach), 1 that route always
 OPT_FACE_FLAGS = 9  # mask kernel of the footprint pass: 1 (default) skips the step-check staging on tiles the upload found without a vertical face, 0 never (identical layers)
 OPT_MEDIAN_ROUTE = 10  # te_run_median_fill: 0 by plan, 1 the tile kernel wherever its window fits, 2 the general kernel always (identical layers)
+OPT_RADIUS_ROUTE = 11  # te_run_radius_filter: 0 by plan, 1 the sliding kernel wherever its result is provably exact, 2 the in-order gather always (identical layers)
+RADIUS_MEAN, RADIUS_MIN = 1, 2  # te_run_radius_filter: gridMapFilters/MeanInRadiusFilter, MinInRadiusFilter
 OPT_FILTER_ANY_RADIUS = 8  # filter discs: 0 up to 32 cells (TE_ERR_UNSUPPORTED above), 1 any radius, 2 the route of any radius for every disc
 
 # every symbol include/travgpu.h declares (tests/test_cabi.py checks the library exports them all)
@@ -52,7 +54,8 @@ SYMBOLS = ["te_params_default", "te_params_validate", "te_device_count", "te_cre
            "te_submap_geometry", "te_download_submap", "te_download_submap_msg",
            "te_expr_check", "te_run_expression", "te_time_expression_samples",
            "te_median_fill_params_default", "te_median_fill_params_validate", "te_run_median_fill", "te_download_fill_mask",
-           "te_time_median_fill_samples"]
+           "te_time_median_fill_samples",
+           "te_run_radius_filter", "te_radius_filter_stats", "te_time_radius_filter_samples"]
 MSG_MAX_NAME = 64
 OCCUPANCY_MAX_LAYERS = CLOUD_MAX_LAYERS = SUBMAP_MAX_LAYERS = 16
 POINTFIELD_FLOAT32 = 7
@@ -282,6 +285,9 @@ def load():
         L.te_run_median_fill.argtypes = [vp, mp, C.c_int, C.c_int, C.c_int, C.c_int]
         L.te_download_fill_mask.argtypes = [vp, C.c_int, C.POINTER(C.c_ubyte), C.c_size_t]
         L.te_time_median_fill_samples.argtypes = [vp, mp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.te_run_radius_filter.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.te_radius_filter_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.te_time_radius_filter_samples.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.te_last_error.restype = C.c_char_p
         L.te_version.restype = C.c_char_p
         _lib = L
@@ -708,6 +714,27 @@ class Context:
         ms = (C.c_float * int(iters))()
         _check(load().te_time_median_fill_samples(self._h, None if params is None else C.byref(params), LAYERS[layer], LAYERS[out],
                                                   int(warmup), int(iters), ms))
+        return np.array(ms[:], dtype=np.float64)
+
+    def run_radius_filter(self, op, radius, in_layer="elevation", out_layer=None, map0=0, nmaps=None):
+        """gridMapFilters/MeanInRadiusFilter (op RADIUS_MEAN or "mean") / MinInRadiusFilter (RADIUS_MIN, "min") on the device
+        (te_run_radius_filter): `out_layer` (default: `in_layer`, in place) = the mean / minimum of `in_layer` within `radius`."""
+        op = {"mean": RADIUS_MEAN, "min": RADIUS_MIN}.get(op, op)
+        lid = lambda name: LAYERS[name] if isinstance(name, str) else int(name)
+        nmaps = self.batch - map0 if nmaps is None else nmaps
+        _check(load().te_run_radius_filter(self._h, int(op), float(radius), lid(in_layer), lid(in_layer if out_layer is None else out_layer),
+                                           int(map0), int(nmaps)))
+
+    def radius_filter_stats(self):
+        """(workgroups the sliding kernel settled, workgroups the in-order gather settled) of the last run_radius_filter."""
+        counts = (C.c_uint64 * 2)()
+        _check(load().te_radius_filter_stats(self._h, counts))
+        return int(counts[0]), int(counts[1])
+
+    def time_radius_filter_samples(self, op, radius, in_layer="elevation", out_layer="traversability_roughness", warmup=3, iters=50):
+        """Device time of each of `iters` radius filters (op 0: device copies of the layer), in ms."""
+        ms = (C.c_float * int(iters))()
+        _check(load().te_time_radius_filter_samples(self._h, int(op), float(radius), LAYERS[in_layer], LAYERS[out_layer], int(warmup), int(iters), ms))
         return np.array(ms[:], dtype=np.float64)
 
     def time_expression_samples(self, text, warmup=3, iters=50):

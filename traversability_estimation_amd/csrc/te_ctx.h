@@ -94,6 +94,8 @@ struct te_ctx {
     // its mask passes, behind each other; the copy of the input layer a call with in_layer == out_layer reads; the general
     // route's counts and list
     te::DevBuf median_mask, median_tmp, median_copy, median_any;
+    // te_run_radius_filter (te_radius.hip): the copy of the input layer a call with in_layer == out_layer reads
+    te::DevBuf radius_copy;
     // the circular footprint at any reach (te_footprint_any.hip): its tables and its prefix-sum scratch ([batch][cols][rows + 1]
     // doubles, then as many unsigned), allocated when the footprint tables are rebuilt for that route; c->fp.any_* point into them
     struct FpAny {
@@ -112,6 +114,8 @@ struct te_ctx {
     te::DevBuf clip_table, fp_clip_table;
     te::DevBuf fa_tab;         // the tables of the filter discs of any radius (Disc::tab points into it); grown
     te::DevBuf tile_in[2], tile_out[2];  // the device staging of in_slot / out_slot; grown
+    // te_run_radius_filter: the window table of the last call (device copy of radius_tab_host; grown) and its two block counts
+    te::DevBuf radius_tab, radius_counts;
   } cmem;
   float* poly_rot = nullptr;  // (derived: lmem.poly)
   bool check_inclination = false;  // footprint/check_robot_inclination (:114)
@@ -134,6 +138,13 @@ struct te_ctx {
   // te_run_median_fill (empty: of none; cleared by every te_set_geometry)
   int opt_median_route = 0;
   std::vector<uint8_t> fill_mask_valid;
+  // TE_OPT_RADIUS_ROUTE (te_radius_plan.h); the host copy of the last call's window table (alive until its asynchronous
+  // upload has been consumed) with the (radius, resolution) it was built for; whether a call has left block counts
+  int opt_radius_route = 0;
+  std::vector<int32_t> radius_tab_host;
+  double radius_tab_radius = -1.0, radius_tab_res = 0.0;
+  te::DiscTable radius_disc;
+  bool radius_counts_valid = false;
   // face flags (te_face_flags.h): the bytes live in the slab; what they describe: te::CtxState::face_crit
   uint8_t* face_flags = nullptr;
   int opt_face_flags = 1;  // TE_OPT_FACE_FLAGS
@@ -199,6 +210,11 @@ int count_invalid_elevation(te_ctx* c);
 const uint8_t* usable_face_flags(const te_ctx* c);
 float* layer_ptr(te_ctx* c, int layer);
 int ensure_input_layer(te_ctx* c, int layer);
+// te_median_api.hip, shared by the device filters: the layer a filter may read (TE_ERR_NOT_READY: it does not exist yet);
+// b.reserve with TE_ERR_UNSUPPORTED and a message; the facts of an upload of the same values into out_layer
+int filter_input_layer(const char* who, te_ctx* c, int id, const float** out);
+int reserve_scratch(const char* who, te::DevBuf& b, size_t bytes, hipStream_t stream, const char* what);
+int note_layer_written(te_ctx* c, int out_layer);
 int rebuild_tables(te_ctx* c);
 void rebuild_footprint_tables(te_ctx* c);
 int sync_tiles(te_ctx* c);  // waits for the copy streams of the streaming-tile calls

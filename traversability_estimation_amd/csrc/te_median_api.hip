@@ -6,10 +6,12 @@
 using namespace te;
 using namespace te::shim;
 
-namespace {
+// shared with te_radius_api.hip (declared in te_ctx.h)
+namespace te {
+namespace shim {
 
 // the layers a call may read: as te_run_expression sees them, and an elevation that was uploaded
-int input_layer(const char* who, te_ctx* c, int id, const float** out) {
+int filter_input_layer(const char* who, te_ctx* c, int id, const float** out) {
   constexpr unsigned optional = bit(TE_LAYER_NORMAL_X) | bit(TE_LAYER_NORMAL_Y) | bit(TE_LAYER_NORMAL_Z) | bit(TE_LAYER_SLOPE_FOOTPRINT) |
                                 bit(TE_LAYER_STEP_FOOTPRINT) | bit(TE_LAYER_ROUGHNESS_FOOTPRINT) | bit(TE_LAYER_TRAVERSABILITY_X) |
                                 bit(TE_LAYER_TRAVERSABILITY_ROT);
@@ -23,11 +25,28 @@ int input_layer(const char* who, te_ctx* c, int id, const float** out) {
   return TE_OK;
 }
 
-int reserve(const char* who, DevBuf& b, size_t bytes, hipStream_t stream, const char* what) {
+int reserve_scratch(const char* who, DevBuf& b, size_t bytes, hipStream_t stream, const char* what) {
   const hipError_t e = b.reserve(bytes, stream);
   if (e != hipSuccess) return fail(TE_ERR_UNSUPPORTED, "%s: %s (%zu bytes) does not fit in device memory: %s", who, what, bytes, hipGetErrorString(e));
   return TE_OK;
 }
+
+// the context's facts about a layer a device filter (te_run_median_fill, te_run_radius_filter) has written: those of an upload of the same values (te_upload_elevation /
+// te_upload_layer); caller holds the lock
+int note_layer_written(te_ctx* c, int out_layer) {
+  if (out_layer == TE_LAYER_ELEVATION) {
+    c->st.elevation_replaced();
+    // the pass of an elevation upload over the whole layer: invalid cells, their runs, the face flags (it waits for the fill)
+    return count_invalid_elevation(c);
+  }
+  c->st.layer_written(out_layer, CtxState::kUploaded);
+  return TE_OK;
+}
+
+}  // namespace shim
+}  // namespace te
+
+namespace {
 
 struct Call {
   median::Args a;
@@ -41,7 +60,7 @@ int prepare(const char* who, te_ctx* c, const te_median_fill_params* p, int in_l
   if (out_layer < 0 || out_layer >= TE_LAYER_COUNT) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
   if (map0 < 0 || nmaps <= 0 || map0 > c->geo.batch - nmaps) return fail(TE_ERR_INVALID_ARG, "%s: maps [%d,%d) of batch %d", who, map0, map0 + nmaps, c->geo.batch);
   const float* in = nullptr;
-  if (const int rc = input_layer(who, c, in_layer, &in)) return rc;
+  if (const int rc = filter_input_layer(who, c, in_layer, &in)) return rc;
   if (out_layer != TE_LAYER_ROBOT_SLOPE && !layer_ptr(c, out_layer))
     return fail(TE_ERR_INVALID_ARG, "%s: the output layer %d has no memory yet", who, out_layer);
   if (in_layer != out_layer)
@@ -63,12 +82,12 @@ int prepare(const char* who, te_ctx* c, const te_median_fill_params* p, int in_l
   te_ctx::LayerMem& m = c->lmem;
   const float* in_first = in + cells * map0;  // the first map of the call
   const size_t batch_cells = cells * (size_t)c->geo.batch;
-  if (const int rc = reserve(who, m.median_mask, batch_cells, c->stream, "the fill mask")) return rc;
-  if (const int rc = reserve(who, m.median_tmp, 2 * batch_cells, c->stream, "the scratch masks")) return rc;
+  if (const int rc = reserve_scratch(who, m.median_mask, batch_cells, c->stream, "the fill mask")) return rc;
+  if (const int rc = reserve_scratch(who, m.median_tmp, 2 * batch_cells, c->stream, "the scratch masks")) return rc;
   if (plan.route == median::kRouteAny)
-    if (const int rc = reserve(who, m.median_any, (median::any_blocks(cells) + 1 + cells) * sizeof(unsigned), c->stream, "the list of cells")) return rc;
+    if (const int rc = reserve_scratch(who, m.median_any, (median::any_blocks(cells) + 1 + cells) * sizeof(unsigned), c->stream, "the list of cells")) return rc;
   if (in_layer == out_layer) {
-    if (const int rc = reserve(who, m.median_copy, c->layer_elems * sizeof(float), c->stream, "the copy of the input layer")) return rc;
+    if (const int rc = reserve_scratch(who, m.median_copy, c->layer_elems * sizeof(float), c->stream, "the copy of the input layer")) return rc;
     HIP_TRY(hipMemcpyAsync(m.median_copy.p, in_first, total * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     in_first = m.median_copy.as<float>();
   }
@@ -87,18 +106,6 @@ int prepare(const char* who, te_ctx* c, const te_median_fill_params* p, int in_l
   a.r_exist = r_exist;
   a.iterations = p->num_erode_dilation_iterations;
   call->plan = plan;
-  return TE_OK;
-}
-
-// the context's facts about a layer the fill has written: those of an upload of the same values (te_upload_elevation /
-// te_upload_layer); caller holds the lock
-int note_written(te_ctx* c, int out_layer) {
-  if (out_layer == TE_LAYER_ELEVATION) {
-    c->st.elevation_replaced();
-    // the pass of an elevation upload over the whole layer: invalid cells, their runs, the face flags (it waits for the fill)
-    return count_invalid_elevation(c);
-  }
-  c->st.layer_written(out_layer, CtxState::kUploaded);
   return TE_OK;
 }
 
@@ -142,7 +149,7 @@ int te_run_median_fill(te_ctx* c, const te_median_fill_params* p, int in_layer, 
   HIP_TRY(median::launch(call.a, call.plan, c->stream));
   if (c->fill_mask_valid.size() != (size_t)c->geo.batch) c->fill_mask_valid.assign((size_t)c->geo.batch, 0);
   for (int m = map0; m < map0 + nmaps; ++m) c->fill_mask_valid[(size_t)m] = 1;
-  return note_written(c, out_layer);
+  return note_layer_written(c, out_layer);
 }
 
 int te_download_fill_mask(te_ctx* c, int map, unsigned char* out, size_t bytes) {
@@ -190,7 +197,7 @@ int te_time_median_fill_samples(te_ctx* c, const te_median_fill_params* p, int i
   if (p) {
     c->fill_mask_valid.assign((size_t)c->geo.batch, 1);
   }
-  return note_written(c, out_layer);
+  return note_layer_written(c, out_layer);
 }
 
 }  // extern "C"

@@ -959,6 +959,10 @@ int te_set_option(te_ctx* c, int option, int value) {
       if (value < 0 || value > 2) return fail(TE_ERR_INVALID_ARG, "te_set_option: TE_OPT_MEDIAN_ROUTE takes 0 (by plan), 1 (the tile kernel wherever its window fits), 2 (the general kernel)");
       c->opt_median_route = value;
       return TE_OK;  // (read by te_run_median_fill alone, which is never captured; identical layers either way)
+    case TE_OPT_RADIUS_ROUTE:
+      if (value < 0 || value > 2) return fail(TE_ERR_INVALID_ARG, "te_set_option: TE_OPT_RADIUS_ROUTE takes 0 (by plan), 1 (the sliding kernel wherever it can run), 2 (the in-order gather)");
+      c->opt_radius_route = value;
+      return TE_OK;  // (read by te_run_radius_filter alone, which is never captured; identical layers either way)
     case TE_OPT_NORMALS_RANK_RULE:
       c->opt_rank_rule = value != 0;
       c->st.filter_option_changed();

@@ -258,3 +258,33 @@ def median_fill_from_yaml(path_or_dict, resolution=None):
         out["fill_hole_cells"] = int(out["fill_hole_radius"] / resolution)
         out["existing_value_cells"] = int(out["existing_value_radius"] / resolution)
     return out
+
+
+RADIUS_FILTER_TYPES = {"gridMapFilters/MeanInRadiusFilter": "mean", "gridMapFilters/MinInRadiusFilter": "min"}
+_RADIUS_FILTER_KEYS = {"radius", "input_layer", "output_layer"}
+
+
+def radius_filter_from_yaml(path_or_dict):
+    """The `gridMapFilters/MeanInRadiusFilter` and `gridMapFilters/MinInRadiusFilter` entries of every filter list of the
+    document, in the order of the file: a list of dicts {"op": "mean" | "min", "radius", "input_layer", "output_layer"} -- the
+    arguments of capi.Context.run_radius_filter -- empty when the file has none.  All three keys are required, as the
+    filters' configure() has them (restated from grid_map_filters: include/travgpu.h); a key the filter does not have is
+    refused, and so is a radius that is not finite or negative."""
+    doc = path_or_dict if isinstance(path_or_dict, (dict, list)) else _load(path_or_dict)
+    lists = [doc] if isinstance(doc, list) else [v for v in (doc or {}).values() if isinstance(v, list)]
+    out = []
+    for f in (f for lst in lists for f in lst if isinstance(f, dict) and str(f.get("type")) in RADIUS_FILTER_TYPES):
+        name = str(f["type"]).split("/")[1]
+        prm = f.get("params") or {}
+        unknown = set(prm) - _RADIUS_FILTER_KEYS
+        if unknown:
+            raise ParamsYamlError(f"{name}: unknown parameter(s) {sorted(unknown)}")
+        for k in ("radius", "input_layer", "output_layer"):
+            if k not in prm:
+                raise ParamsYamlError(f"{name} did not find param {k}")
+        radius = float(prm["radius"])
+        if not (np.isfinite(radius) and radius >= 0.0):
+            raise ParamsYamlError(f"{name}: radius must be finite and not negative (got {radius})")
+        out.append({"op": RADIUS_FILTER_TYPES[str(f["type"])], "radius": radius, "input_layer": str(prm["input_layer"]),
+                    "output_layer": str(prm["output_layer"])})
+    return out

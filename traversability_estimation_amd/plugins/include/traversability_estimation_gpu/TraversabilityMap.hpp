@@ -58,6 +58,11 @@ class TraversabilityMap {
    *  then sees a layer without the holes that had observed neighbours.  NULL switches it off again (the default).  false (and
    *  nothing changed) for parameters te_median_fill_params_validate refuses. */
   bool setFillHoles(const te_median_fill_params* params);
+  /*! Smoothing in front of the chain (gridMapFilters/MeanInRadiusFilter on the device, te_run_radius_filter): with a radius
+   *  above 0, computeTraversability() replaces the resident elevation layer by its mean within that radius -- once per
+   *  elevation map, after the hole filling of setFillHoles -- and the chain sees the smoothed layer.  0 switches it off again
+   *  (the default).  false (and nothing changed) for a radius that is negative or not finite. */
+  bool setSmoothElevation(double radius);
   /*! traversabilityFootprint(radius, offset) (:307-318): layer traversability_footprint. */
   bool traversabilityFootprint(const double& radius, const double& offset);
   /*! traversabilityFootprint(footprintYaw) (:239-305): layers traversability_x / traversability_rot. */
@@ -109,6 +114,8 @@ class TraversabilityMap {
   te_params params_;
   te_median_fill_params fillParams_;
   bool fillHoles_, elevationFilled_;  // setFillHoles; the resident elevation has been filled with fillParams_
+  double smoothRadius_;               // setSmoothElevation (0: off)
+  bool elevationSmoothed_;            // the resident elevation has been smoothed with smoothRadius_
   std::vector<geometry_msgs::Point32> footprintPoints_;
   grid_map::GridMap geometry_;  // geometry and start index of the last elevation map (no layers)
   bool elevationMapInitialized_, traversabilityMapInitialized_, footprintLayer_, polygonLayers_;

@@ -50,6 +50,9 @@ class DeviceMap {
   bool runExpression(const std::string& text);
   /*! out_layer = MedianFillFilter(in_layer) on the device (te_run_median_fill); what a plugin uploaded into out_layer is gone. */
   bool runMedianFill(const te_median_fill_params& params, int in_layer, int out_layer);
+  /*! out_layer = the mean (TE_RADIUS_MEAN) / minimum (TE_RADIUS_MIN) of in_layer within radius on the device
+   *  (te_run_radius_filter); what a plugin uploaded into out_layer is gone. */
+  bool runRadiusFilter(int op, double radius, int in_layer, int out_layer);
   bool download(grid_map::GridMap& map, const std::string& layer, int te_layer);
   const std::string& error() const { return error_; }
 

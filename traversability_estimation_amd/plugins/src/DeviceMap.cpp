@@ -237,6 +237,11 @@ bool DeviceMap::runMedianFill(const te_median_fill_params& params, int in_layer,
   return check(te_run_median_fill(ctx_, &params, in_layer, out_layer, 0, 1));
 }
 
+bool DeviceMap::runRadiusFilter(int op, double radius, int in_layer, int out_layer) {
+  if (out_layer >= 0 && out_layer < kLayers) resident_[out_layer].valid = false;  // (written on the device)
+  return check(te_run_radius_filter(ctx_, op, radius, in_layer, out_layer, 0, 1));
+}
+
 bool DeviceMap::download(grid_map::GridMap& map, const std::string& layer, int te_layer) {
   if (start_row_ || start_col_) return check(te_download_layer_circular(ctx_, te_layer, map.get(layer).data(), 0, start_row_, start_col_));
   return check(te_download_layer(ctx_, te_layer, map.get(layer).data(), 0, 1));

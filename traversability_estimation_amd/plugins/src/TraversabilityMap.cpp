@@ -24,6 +24,8 @@ TraversabilityMap::TraversabilityMap(int device)
   te_params_default(&params_);
   te_median_fill_params_default(&fillParams_);
   fillHoles_ = elevationFilled_ = false;
+  smoothRadius_ = 0.0;
+  elevationSmoothed_ = false;
   // (the reference's filters take any radius: TE_OPT_FILTER_ANY_RADIUS = 1)
   if (check(te_create(device, &ctx_))) {
     if (check(te_set_option(ctx_, TE_OPT_FILTER_ANY_RADIUS, 1))) {
@@ -91,7 +93,7 @@ bool TraversabilityMap::setElevationMap(const grid_map::GridMap& elevationMap) {
   geometry_.setGeometry(elevationMap.getLength(), elevationMap.getResolution(), elevationMap.getPosition());
   geometry_.setStartIndex(start);
   elevationMapInitialized_ = true;
-  elevationFilled_ = false;
+  elevationFilled_ = elevationSmoothed_ = false;
   traversabilityMapInitialized_ = false;
   footprintLayer_ = polygonLayers_ = false;
   return true;
@@ -136,7 +138,7 @@ bool TraversabilityMap::setElevationFromImage(const sensor_msgs::Image& image, d
   length(1) = resolution * info.width;
   geometry_.setGeometry(length, resolution, position);
   elevationMapInitialized_ = true;
-  elevationFilled_ = false;
+  elevationFilled_ = elevationSmoothed_ = false;
   traversabilityMapInitialized_ = false;
   footprintLayer_ = polygonLayers_ = false;
   return true;
@@ -155,6 +157,17 @@ bool TraversabilityMap::setFillHoles(const te_median_fill_params* params) {
   return true;
 }
 
+bool TraversabilityMap::setSmoothElevation(double radius) {
+  std::lock_guard<std::mutex> lock(mutex_);
+  if (!(radius >= 0.0) || !std::isfinite(radius)) {
+    ROS_ERROR("Traversability Estimation: the smoothing radius must be finite and not negative.");
+    return false;
+  }
+  smoothRadius_ = radius;
+  // (an elevation smoothed under another radius stays as it is until the next elevation map: the filter reads its own output)
+  return true;
+}
+
 bool TraversabilityMap::computeTraversability() {
   std::lock_guard<std::mutex> lock(mutex_);
   if (!elevationMapInitialized_) {  // :228-231
@@ -168,6 +181,14 @@ bool TraversabilityMap::computeTraversability() {
       return false;
     }
     elevationFilled_ = true;
+  }
+  if (smoothRadius_ > 0.0 && !elevationSmoothed_) {
+    if (!check(te_run_radius_filter(ctx_, TE_RADIUS_MEAN, smoothRadius_, TE_LAYER_ELEVATION, TE_LAYER_ELEVATION, 0, 1))) {
+      ROS_ERROR("Traversability Estimation: Could not smooth the elevation map! No traversability computed!");
+      traversabilityMapInitialized_ = false;
+      return false;
+    }
+    elevationSmoothed_ = true;
   }
   if (!check(te_run_chain(ctx_, 0))) {  // :214-218
     ROS_ERROR("Traversability Estimation: Could not update the filter chain! No traversability computed!");
