@@ -9,9 +9,9 @@ exact model, so a deviation beyond TOL here is the kernel's.
 Routes are steered with what the library offers, nothing test-only: the fixture's shape and radius, TE_RUN_KEEP_NORMALS (the
 kernel that keeps the normals exists with the dense march only; the slim ring, the sparse march and k_chain_window need a
 run without it), a 48-row copy of the map (k_normals_slide), TE_RUN_GENERIC_KERNELS, TE_OPT_FILTER_ANY_RADIUS = 2, a
-batch of two maps and a region run over an odd-origin rectangle.  The kernel in a test id is NOMINAL: the one section 4.7
-names for that input, worked out here from the table's words; the library does not report which kernel it launched, so an
-id documents the intent and proves nothing.  What the plan gives these shapes -- interior block columns, strip heights --
+batch of two maps and a region run over an odd-origin rectangle.  The kernel in a test id is the one plan_chain_route
+(te_chain_route.h) gives that input: tests/test_chain_route.py asks the library's own header for every (fixture, route) here
+and compares.  What the strip plan gives these shapes -- interior block columns, strip heights --
 is asked of the kernels' own header in tests/test_conditioning_ref.py.
 
 Strip length: one map of this size gets strips of 8 rows; test_long_strips runs a batch of LONG_STRIP_MAPS copies of the
@@ -70,10 +70,12 @@ def kernel_of(name, route):
         return "k_fa_normals+k_fa_exact"
     c = _cells(over, res)
     tie = abs(c - round(c)) < 1e-9
+    if c < 3 and (not tie or c <= 2):  # a whole-map launch of these sizes is one kernel, kept or not, 48 rows or 200
+        return "k_chain_window"        # (the region run of batch+region: k_normals_small)
     if route == "rows48" or rows < 64 or c >= 11:
+        if tie:  # the TIES march needs 64 rows and nothing else takes a tie radius of three cells and more
+            return "k_normals"  # (alone: no fix-up pass behind the generic kernel)
         return "k_normals_slide<R>" if c >= 11 else "k_normals_slide"
-    if c < 3 and (not tie or c <= 2):
-        return "k_chain_window" if route == "scores" else "k_normals_small"
     if tie:
         return "k_normals3-TIES"
     h = _holes(elev)

@@ -133,6 +133,40 @@ inline void tie_summary(const Disc& d, int reach, bool* on_circle, int* n_gen) {
   }
 }
 
+// What plan_chain_route (te_chain_route.h) asks about a filter's disc, plain values (O(R) to fill)
+struct DiscSummary {
+  bool any = false;  // Disc::any: the kernels of te_filter_any.hip, nothing else below is meaningful
+  int R = -1, Q = -1, reach = 0, npoints = 0, n_ties = 0;
+  bool ties_on_circle = true;  // every tie offset has the squared norm reach^2 (a whole-cell radius)
+  int n_gen = 0;               // tie offsets with both parts non-zero
+  int q_runs = 0;              // largest di^2 + dj^2 in the runs: the shape a tie disc leaves without its circle
+  int n_offsets = 0;           // cells besides the centre, runs and ties together
+  long long sii_runs = 0, sii_ties = 0;  // sum of di^2 over the runs / over the tie offsets
+};
+inline DiscSummary disc_summary(const Disc& d) {
+  DiscSummary s;
+  s.any = d.any != 0;
+  s.R = d.R;
+  s.Q = d.Q;
+  s.reach = d.reach;
+  s.npoints = d.npoints;
+  s.n_ties = d.n_ties;
+  if (s.any) return s;
+  tie_summary(d, d.reach, &s.ties_on_circle, &s.n_gen);
+  for (int b = 0; b <= d.R; ++b) {
+    const int hw = d.hw[b];
+    if (hw < 0) continue;
+    if (hw * hw + b * b > s.q_runs) s.q_runs = hw * hw + b * b;
+    s.sii_runs += (b == 0 ? 1 : 2) * ((long long)hw * (hw + 1) * (2 * hw + 1) / 3);
+  }
+  s.n_offsets = d.npoints > 0 ? d.npoints - 1 : 0;
+  for (int t = 0; t < d.n_ties; ++t) {
+    s.sii_ties += (int)d.tie_di[t] * d.tie_di[t];
+    s.n_offsets += (d.tie_di[t] != 0 || d.tie_dj[t] != 0) ? 1 : 0;
+  }
+  return s;
+}
+
 // x/y moments of the disc clipped to di in [lo_i, hi_i], dj in [lo_j, hi_j] for every clip code (kx, ky) in [-R, R]^2
 // (see k_normals_slide): n, sum di, sum dj, sum di^2, sum di dj, sum dj^2.  out must hold (2R+1)^2 * 6 ints.
 inline void build_clip_table(const Disc& d, int R, int* out) {

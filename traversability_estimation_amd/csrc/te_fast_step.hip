@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void k_step_score_ties(Geo g, TieArgs t, doubl
 }
 
 // ---- small windows: at most 13 cells, gathered directly ---------------------------------------------------------------
-constexpr int kSmallWin = 12;  // offsets besides the centre (the 13-point disc: reach 2)
+constexpr int kSmallWin = kSmallOffsets;  // offsets besides the centre (the 13-point disc: reach 2)
 struct SmallWin {
   int n;
   signed char di[kSmallWin], dj[kSmallWin];
@@ -181,11 +181,14 @@ __global__ __launch_bounds__(256) void k_step_small(Geo g, SmallWin w, double cr
   }
 }
 
-// the window of a tie-free shape Q, or of a disc with tie cells; false: more than kSmallWin cells besides the centre
-bool small_window(int Q, const Disc* d, SmallWin* w) {
+// the window of k_step_small: the cells of the disc besides the centre, tie cells tested per centre.  (A tie-free window
+// on this route holds the centre alone: a gather through the vector cache costs 5 us per neighbour and pass on a 4096^2
+// layer -- tools/lab/step_small_ubench.hip: 0 / 4 / 8 neighbours 25 / 51 / 72 us -- so from five cells on the marching
+// kernel beside the normals kernel wins.)  false: more than kSmallWin cells, which the plan does not send here
+bool small_window(const Disc& d, SmallWin* w) {
   w->n = 0;
   w->test_mask = 0;
-  w->r2 = d ? d->r2 : 0.0;
+  w->r2 = d.n_ties ? d.r2 : 0.0;
   for (int k = 0; k < kSmallWin; ++k) w->di[k] = w->dj[k] = 0;
   auto push = [&](int di, int dj, bool test) {
     if (w->n >= kSmallWin) return false;
@@ -195,26 +198,18 @@ bool small_window(int Q, const Disc* d, SmallWin* w) {
     ++w->n;
     return true;
   };
-  if (d) {
-    if (d->reach > 2) return false;
-    for (int dj = -d->R; dj <= d->R; ++dj) {
-      const int hw = d->hw[dj < 0 ? -dj : dj];
-      for (int di = -hw; di <= hw; ++di)
-        if ((di || dj) && !push(di, dj, false)) return false;
-    }
-    for (int t = 0; t < d->n_ties; ++t) {
-      // (a radius of exactly 0: the circle IS the centre -- isInside accepts it, 0 <= 0 -- and the kernels count the centre
-      // themselves: listed again it was counted twice, nCells 2 instead of 1; the sweep's seeds 20477 ... 23804, round 6)
-      if (d->tie_di[t] == 0 && d->tie_dj[t] == 0) continue;
-      if (!push(d->tie_di[t], d->tie_dj[t], true)) return false;
-    }
-    return true;
+  for (int dj = -d.R; dj <= d.R; ++dj) {
+    const int hw = d.hw[dj < 0 ? -dj : dj];
+    for (int di = -hw; di <= hw; ++di)
+      if ((di || dj) && !push(di, dj, false)) return false;
   }
-  // tie-free windows: the centre alone.  (A gather through the vector cache costs 5 us per neighbour and pass on a 4096^2
-  // layer -- tools/lab/step_small_ubench.hip: 0 / 4 / 8 neighbours 25 / 51 / 72 us -- so from five cells on the marching
-  // kernel beside the normals kernel wins: default windows at res 0.03, chain 0.219 ms against 0.267 with this kernel
-  // beside the normals kernel and 0.294 with it ahead of it.)
-  return Q == 0;
+  for (int t = 0; t < d.n_ties; ++t) {
+    // (a radius of exactly 0: the circle IS the centre -- isInside accepts it, 0 <= 0 -- and the kernels count the centre
+    // themselves: listed again it was counted twice, nCells 2 instead of 1; the sweep's seeds 20477 ... 23804, round 6)
+    if (d.tie_di[t] == 0 && d.tie_dj[t] == 0) continue;
+    if (!push(d.tie_di[t], d.tie_dj[t], true)) return false;
+  }
+  return true;
 }
 
 dim3 small_grid(const Geo& g, const Region& r) {
@@ -227,28 +222,15 @@ float largest_float_below(double crit) {  // largest float <= crit: "h > crit" i
   return lo;
 }
 
-// the shapes a whole-cell radius of 3 .. 10 cells leaves without its circle (2 cells: k_step_small) (te_march.h has them all): only these exist as RAW kernels
-constexpr bool tie_free_part(int Q) { return Q == 8 || Q == 13 || Q == 20 || Q == 34 || Q == 45 || Q == 61 || Q == 80 || Q == 98; }
-
-// the shape of a tie disc without its circle (largest norm in its runs), its ties as kernel arguments; false: not a
-// whole-cell radius this file serves
-bool tie_disc(const Disc& d, int* q_free, TieArgs* t) {
-  if (d.n_ties == 0 || d.n_ties > kMaxTies || d.R < 1) return false;
-  int q = 0;
-  for (int b = 0; b <= d.R; ++b)
-    if (d.hw[b] >= 0 && d.hw[b] * d.hw[b] + b * b > q) q = d.hw[b] * d.hw[b] + b * b;
-  const int n2 = d.reach * d.reach;
-  for (int k = 0; k < d.n_ties; ++k)
-    if ((int)d.tie_di[k] * d.tie_di[k] + (int)d.tie_dj[k] * d.tie_dj[k] != n2) return false;
-  if (!tie_free_part(q)) return false;
-  *q_free = q;
-  t->n_ties = d.n_ties;
+TieArgs tie_args(const Disc& d) {
+  TieArgs t;
+  t.n_ties = d.n_ties;
   for (int k = 0; k < kMaxTies; ++k) {
-    t->di[k] = k < d.n_ties ? d.tie_di[k] : 0;
-    t->dj[k] = k < d.n_ties ? d.tie_dj[k] : 0;
+    t.di[k] = k < d.n_ties ? d.tie_di[k] : 0;
+    t.dj[k] = k < d.n_ties ? d.tie_dj[k] : 0;
   }
-  t->r2 = d.r2;
-  return true;
+  t.r2 = d.r2;
+  return t;
 }
 
 dim3 cell_grid(const Geo& g, const Region& r) {
@@ -257,62 +239,37 @@ dim3 cell_grid(const Geo& g, const Region& r) {
 
 }  // namespace
 
-bool step_height_fast(int Q, const Geo& g, const float* elev, float* sh, const Region& r, hipStream_t s) {
+// Each function below launches the route plan_chain_route (te_chain_route.h) named; none of them declines.
+
+hipError_t step_height_small(const Disc& d, const Geo& g, const float* elev, float* sh, const Region& r, hipStream_t s) {
   SmallWin w;
-  static const bool no_small = lab_flag("TE_STEP_NO_SMALL");  // measurement aid
-  if (!no_small && small_window(Q, nullptr, &w)) {
-    hipLaunchKernelGGL(k_step_small<false>, small_grid(g, r), dim3(kLanes, 4), 0, s, g, w, 0.0, 0.0f, 1, elev, sh, r);
-    return true;
-  }
-  return step_height5(Q, g, elev, sh, nullptr, r, s);
+  if (!small_window(d, &w)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_step_small<false>, small_grid(g, r), dim3(kLanes, 4), 0, s, g, w, 0.0, 0.0f, 1, elev, sh, r);
+  return hipSuccess;
 }
 
-// a tie radius (see the header); scratch: one float per cell of the layer
-bool step_height_ties(const Disc& d, const Geo& g, const float* elev, float* sh, float* scratch, const Region& r, hipStream_t s) {
-  static const bool off = lab_flag("TE_STEP_NO_TIES");  // measurement aid: tie radii to the generic kernels as before
-  int q = 0;
-  TieArgs t;
+hipError_t step_score_small(const Disc& d, const Geo& g, double crit, int ncrit, const float* sh, float* out, const Region& r, hipStream_t s) {
   SmallWin w;
-  static const bool no_small = lab_flag("TE_STEP_NO_SMALL");
-  if (d.any) return false;  // (te_filter_any.hip)
-  if (!off && !no_small && d.n_ties != 0 && small_window(-1, &d, &w)) {  // a tie radius of one or two cells
-    hipLaunchKernelGGL(k_step_small<false>, small_grid(g, r), dim3(kLanes, 4), 0, s, g, w, 0.0, 0.0f, 1, elev, sh, r);
-    return true;
-  }
-  if (off || !scratch || r.i1 - r.i0 < kLanes || !tie_disc(d, &q, &t)) return false;
-  if (!step_height5(q, g, elev, sh, scratch, r, s)) return false;
-  hipLaunchKernelGGL(k_step_height_ties, cell_grid(g, r), dim3(256), 0, s, g, t, elev, sh, (const float*)scratch, r);
-  return true;
+  if (!small_window(d, &w)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_step_small<true>, small_grid(g, r), dim3(kLanes, 4), 0, s, g, w, crit, largest_float_below(crit), ncrit, sh, out, r);
+  return hipSuccess;
 }
 
-bool step_score_fast(int Q, const Geo& g, double crit, int ncrit, const float* sh, float* out, const Region& r,
-                     hipStream_t s) {
-  SmallWin w;
-  static const bool no_small = lab_flag("TE_STEP_NO_SMALL");
-  if (!no_small && small_window(Q, nullptr, &w)) {
-    hipLaunchKernelGGL(k_step_small<true>, small_grid(g, r), dim3(kLanes, 4), 0, s, g, w, crit, largest_float_below(crit), ncrit, sh, out, r);
-    return true;
-  }
-  return step_score5(Q, g, crit, ncrit, sh, out, nullptr, r, s);
+// a tie radius (see the header): the RAW march on shape q, the disc without its circle; scratch: one float per cell of the layer
+hipError_t step_height_ties(const Disc& d, int q, const Geo& g, const float* elev, float* sh, float* scratch, const Region& r, hipStream_t s) {
+  const hipError_t e = step_height5(q, g, elev, sh, scratch, r, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_step_height_ties, cell_grid(g, r), dim3(256), 0, s, g, tie_args(d), elev, sh, (const float*)scratch, r);
+  return hipSuccess;
 }
 
-bool step_score_ties(const Disc& d, const Geo& g, double crit, int ncrit, const float* sh, float* out, float* scratch, const Region& r,
-                     hipStream_t s) {
-  static const bool off = lab_flag("TE_STEP_NO_TIES");
-  int q = 0;
-  TieArgs t;
-  SmallWin w;
-  static const bool no_small = lab_flag("TE_STEP_NO_SMALL");
-  if (d.any) return false;
-  if (!off && !no_small && d.n_ties != 0 && small_window(-1, &d, &w)) {
-    hipLaunchKernelGGL(k_step_small<true>, small_grid(g, r), dim3(kLanes, 4), 0, s, g, w, crit, largest_float_below(crit), ncrit, sh, out, r);
-    return true;
-  }
-  if (off || !scratch || r.i1 - r.i0 < kLanes || !tie_disc(d, &q, &t)) return false;
-  const float lo = largest_float_below(crit);
-  if (!step_score5(q, g, crit, ncrit, sh, out, scratch, r, s)) return false;
-  hipLaunchKernelGGL(k_step_score_ties, cell_grid(g, r), dim3(256), 0, s, g, t, crit, lo, ncrit, sh, out, (const float*)scratch, r);
-  return true;
+hipError_t step_score_ties(const Disc& d, int q, const Geo& g, double crit, int ncrit, const float* sh, float* out, float* scratch,
+                           const Region& r, hipStream_t s) {
+  const hipError_t e = step_score5(q, g, crit, ncrit, sh, out, scratch, r, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_step_score_ties, cell_grid(g, r), dim3(256), 0, s, g, tie_args(d), crit, largest_float_below(crit), ncrit, sh, out,
+                     (const float*)scratch, r);
+  return hipSuccess;
 }
 
 }  // namespace fast

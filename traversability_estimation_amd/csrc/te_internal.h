@@ -8,6 +8,7 @@
 
 #include <vector>
 
+#include "te_chain_route.h"
 #include "te_disc.h"
 #include "te_face_flags.h"
 #include "te_fp_route.h"
@@ -67,6 +68,9 @@ struct ChainParams {
   double slope_crit, step_crit, rough_crit;
   int step_ncrit;
   float w_scale, w_slope, w_step, w_rough;
+  // what plan_chain_route asks that changes only with the parameters and the geometry (the discs' summaries, the map, the
+  // device's CUs, the lab switches): filled by chain_route_template when the tables are rebuilt; a launch adds its own facts
+  fast::ChainRouteIn route;
 };
 
 // THE CLIP OF A SCORE.  SlopeFilter / RoughnessFilter clip their scores at 0 (SlopeFilter.cpp:77-81, RoughnessFilter.cpp:119-124)
@@ -208,11 +212,10 @@ void build_path_polygons(int n_paths, const int* pose_offset, const double* pose
 constexpr int kFixTiles = 8;
 inline int fix_groups(int ntiles) { return ntiles <= 2048 ? ntiles : (ntiles + kFixTiles - 1) / kFixTiles; }
 
-struct FastGrid {  // fix-up flag grid of the last sliding-disc normals launch: 64x16 tiles of the region
+struct FastGrid {  // fix-up flag grid of a sliding-disc normals launch: 64x16 tiles of the region
   int ntx, nty, nbz;
-  int frame;  // > 0: the fix-up pass also owns every cell within `frame` cells of the map border (k_normals3 computes
-              // only discs that lie inside the map), whatever the flags and the slope layer say;
-              // < 0: the kernel settled every cell itself (k_normals_small): no fix-up pass at all
+  int frame;  // > 0: the fix-up pass also owns every cell within `frame` cells of the map border, whatever the flags and
+              // the slope layer say (no launch asks for it today)
 };
 
 // te_stage.hip: whole-layer transfers through pageable caller buffers -- a ring of page-locked slots per context, chunked,
@@ -237,7 +240,7 @@ struct HostStager {
 // The marching kernels of te_march5.h read kSlabGuardRows rows above and below the layers they are given (unconditional
 // raw buffer loads, no bounds check: DESIGN.md).  Layers of a context's slab have that slack by its plan (te_slab.h); any other
 // pointer -- a caller's own allocation handed in through a future entry point -- is checked here against the allocation
-// that holds it, and the launchers fall back to the bounds-checked generic kernels when the slack is not there.
+// that holds it, and the route plans send a layer without the slack to the bounds-checked generic kernels.
 // (One driver query per distinct (pointer, shape); the verdicts are dropped whenever a context frees its layers.)
 inline std::atomic<unsigned>& guard_cache_generation() {
   static std::atomic<unsigned> g{0};
@@ -288,7 +291,10 @@ inline int device_cus() {
   return cus;
 }
 
-// launch wrappers (te_kernels.hip); all asynchronous on `stream`
+// te_kernels.hip: fills p.route from p's discs and parameters, the geometry and the current device (rebuild_tables)
+void chain_route_template(const Geo& g, ChainParams& p);
+// launch wrappers (te_kernels.hip); all asynchronous on `stream`.  hipErrorInvalidValue: a planned route without its
+// instantiation, which the shim reports as an internal routing error
 hipError_t launch_filter(const Geo& g, const ChainParams& p, const Layers& L, int filter, unsigned flags,
                          hipStream_t stream);
 hipError_t launch_chain(const Geo& g, const ChainParams& p, const Layers& L, const Region& r, unsigned flags,
@@ -361,38 +367,39 @@ hipError_t step_score(const Geo& g, const Disc& d, double crit, int ncrit, const
 hipError_t normals(const Geo& g, const NormalsJob& a, const Layers& L, float* nx, float* ny, float* nz, const Region& r, hipStream_t s);
 }  // namespace any
 
-// shape-specialised kernels (te_fast_*.hip); return false when the shape Q is not instantiated
+// The shape-specialised kernels of the filter chain, each the launcher of ONE route plan_chain_route (te_chain_route.h)
+// names: they build their argument block and launch.  hipErrorInvalidValue: a planned route without its instantiation
+// (an internal routing error, never a slower kernel).
 namespace fast {
-bool step_height_fast(int Q, const Geo& g, const float* elev, float* sh, const Region& r, hipStream_t s);
-bool step_score_fast(int Q, const Geo& g, double crit, int ncrit, const float* sh, float* out, const Region& r,
-                     hipStream_t s);
-// te_step5.hip: the marching kernels behind the two functions above (and, RAW -- second output pointer set -- behind the two below)
-bool step_height5(int Q, const Geo& g, const float* elev, float* sh, float* sh_min, const Region& r, hipStream_t s);
-bool step_score5(int Q, const Geo& g, double crit, int ncrit, const float* sh, float* out, float* out_count, const Region& r, hipStream_t s);
-// ... at a tie radius (whole-cell radii of 2 .. 10 cells): the marching kernels on the shape without its circle, then the
+inline FastGrid fast_grid(const Geo& g, const Region& r) {  // the fix-up flag grid of region r
+  return FastGrid{(r.i1 - r.i0 + 63) / 64, (r.j1 - r.j0 + 15) / 16, r.map >= 0 ? 1 : g.batch, 0};
+}
+// te_fast_step.hip: k_step_small on the disc's window (the centre alone, or a tie radius of one or two cells)
+hipError_t step_height_small(const Disc& d, const Geo& g, const float* elev, float* sh, const Region& r, hipStream_t s);
+hipError_t step_score_small(const Disc& d, const Geo& g, double crit, int ncrit, const float* sh, float* out, const Region& r, hipStream_t s);
+// te_step5.hip: the marching kernels on shape Q (RAW -- second output pointer set -- behind the two *_ties below)
+hipError_t step_height5(int Q, const Geo& g, const float* elev, float* sh, float* sh_min, const Region& r, hipStream_t s);
+hipError_t step_score5(int Q, const Geo& g, double crit, int ncrit, const float* sh, float* out, float* out_count, const Region& r, hipStream_t s);
+// ... at a tie radius (whole-cell radii of 3 .. 10 cells): the RAW march on q, the shape without its circle, then the
 // accepted circle cells folded in per cell; scratch: one float per cell of the layer (Layers::tie_scratch)
-bool step_height_ties(const Disc& d, const Geo& g, const float* elev, float* sh, float* scratch, const Region& r, hipStream_t s);
-bool step_score_ties(const Disc& d, const Geo& g, double crit, int ncrit, const float* sh, float* out, float* scratch, const Region& r,
-                     hipStream_t s);
-// normals + slope + roughness (same disc for normals and roughness, positive axis z); with `combine`
-// the traversability layer is written too (the step layer must be complete).
-// *combined tells whether it did (the k_normals3 path leaves the combine to the caller).
-bool normals_fast(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, bool combine,
-                  const Region& r, int* block_flags, const int* clip_table, FastGrid* fg, hipStream_t s, bool* combined);
-// te_slide_normals.hip: RoughnessFilter alone with the normals of the layers (false: shape / map not taken)
-bool roughness_given_fast(const Geo& g, const ChainParams& p, const Layers& L, const Region& r, int* block_flags, FastGrid* fg, hipStream_t s);
-// te_normals3.hip: the cells whose disc lies inside the map (false: shape / region not taken)
-bool normals_fast3(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, const Region& r, int* block_flags,
-                   FastGrid* fg, hipStream_t s);
-// te_normals_small.hip: discs that reach at most two cells (the one-cell tie radius of the default parameters on a 0.05 m
-// map; small launches of the tie-free 5- to 13-point discs), one cell per thread; false: not taken
+hipError_t step_height_ties(const Disc& d, int q, const Geo& g, const float* elev, float* sh, float* scratch, const Region& r, hipStream_t s);
+hipError_t step_score_ties(const Disc& d, int q, const Geo& g, double crit, int ncrit, const float* sh, float* out, float* scratch,
+                           const Region& r, hipStream_t s);
+// te_slide_normals.hip: k_normals_slide for the tie-free disc d (sii: sum of di^2 over it), shape or radius form; given:
+// RoughnessFilter alone with the normals of the layers; combine: the traversability layer is written too (the step layer
+// must be complete)
+hipError_t normals_slide(const Geo& g, const ChainParams& p, const Layers& L, const Disc& d, int sii, bool shape_form, bool given,
+                         bool keep_normals, bool combine, const Region& r, int* block_flags, hipStream_t s);
+// te_normals3.hip: k_normals3 / k_normals3s, the cells whose disc lies inside the map; march, shape and strips from rt
+hipError_t normals3(const Geo& g, const ChainParams& p, const Layers& L, const ChainRoute& rt, const DiscSummary& ds, const Region& r,
+                    int* block_flags, hipStream_t s);
+// te_normals_small.hip: discs that reach at most two cells, one cell per thread, no fix-up pass behind it
 // write_step: both step windows hold one cell -- the step score is 1 (valid) / NaN and this kernel writes the layer; combine:
 // ... and the weighted sum (the step layer must be complete, or written here)
-bool normals_small(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, const Region& r, int* block_flags, FastGrid* fg,
-                   hipStream_t s, bool write_step = false, bool combine = false);
-// ... and the whole chain of a small whole-map launch (at most 2^18 cells, a disc of at most 13 cells, step windows of at most 3 x 3
-// cells) in one kernel: normals, slope, roughness, both step passes, the weighted sum; false: not taken
-bool chain_window(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, const Region& r, bool combine, hipStream_t s);
+hipError_t normals_small(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, bool cross, const Region& r, hipStream_t s,
+                         bool write_step, bool combine);
+// ... and the whole chain of a small whole-map launch in one kernel (k_chain_window)
+hipError_t chain_window(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, const Region& r, bool combine, hipStream_t s);
 int normals_fast_max_blocks(const Geo& g);
 size_t normals_hole_queue_bytes();  // te_normals3.hip: scratch of the sparse-hole march for one device (any map, any batch)
 // The sum kernels of the circular footprint pass, each on the route plan_fp_route chose for it (false: the shape is not

@@ -481,15 +481,6 @@ __global__ void k_slope_from_nz(Geo g, double crit, const float* __restrict__ nz
   slope[o] = __builtin_isfinite(v) ? slope_score(v, crit) : __builtin_nanf("");
 }
 
-inline Region clamp_region(const Geo& g, const Region& r, int grow) {
-  Region o = r;
-  o.i0 = r.i0 - grow < 0 ? 0 : r.i0 - grow;
-  o.j0 = r.j0 - grow < 0 ? 0 : r.j0 - grow;
-  o.i1 = r.i1 + grow > g.rows ? g.rows : r.i1 + grow;
-  o.j1 = r.j1 + grow > g.cols ? g.cols : r.j1 + grow;
-  return o;
-}
-
 inline dim3 tile_grid(const Geo& g, const Region& r) {
   return dim3((unsigned)((r.i1 - r.i0 + TX - 1) / TX), (unsigned)((r.j1 - r.j0 + TY - 1) / TY),
               (unsigned)(r.map >= 0 ? 1 : g.batch));
@@ -505,183 +496,246 @@ int chain_max_reach(const ChainParams& p) {
   return a > b ? a : b;
 }
 
-// One reference plugin at a time (the drop-in SlopeFilter / StepFilter / RoughnessFilter adapters).
-hipError_t launch_chain(const Geo& g, const ChainParams& p, const Layers& L, const Region& r, unsigned flags, hipStream_t stream);
+namespace {
 
-hipError_t launch_filter(const Geo& g, const ChainParams& p, const Layers& L, int filter, unsigned flags,
-                         hipStream_t stream) {
-  const Region r = {-1, 0, 0, g.rows, g.cols};
+using namespace fast;  // the route plan's types (te_chain_route.h)
+
+static_assert(kFilterSlope == TE_FILTER_SLOPE && kFilterStep == TE_FILTER_STEP && kFilterRoughness == TE_FILTER_ROUGHNESS &&
+                  kFilterCombine == TE_FILTER_COMBINE && kFilterNormals == TE_FILTER_NORMALS,
+              "te_chain_route.h: ChainFilter restates TE_FILTER_*");
+
+// The measurement switches of the lab build, read once per process: a ChainRouteIn that holds nothing else
+ChainRouteIn lab_switches() {
+  ChainRouteIn in;
+  in.no_small = lab_flag("TE_NO_SMALL");
+  in.no_chain_window = lab_flag("TE_NO_CHAIN_WINDOW");
+  in.no_n3 = lab_flag("TE_NO_N3");
+  in.n3_no_ties = lab_flag("TE_N3_NO_TIES");
+  in.n3_no_slim = lab_flag("TE_N3_NO_SLIM");
+  in.step_no_small = lab_flag("TE_STEP_NO_SMALL");
+  in.step_no_ties = lab_flag("TE_STEP_NO_TIES");
+  in.small_max_cells = lab_int("TE_SMALL_MAX_CELLS", 0);
+  in.n3_blocks_per_cu = lab_int("TE_N3_BLOCKS_PER_CU", 0);
+  in.n3_edge_percent = lab_int("TE_N3_EDGE_PERCENT", 50);
+  in.n3_strip_rows = lab_int("TE_N3_STRIP_ROWS", 0);
+  return in;
+}
+
+// What plan_chain_route / plan_filter_route ask about a launch: the template of the parameters plus this launch's facts
+ChainRouteIn route_inputs(const Geo& g, const ChainParams& p, const Layers& L, const Region& r, unsigned flags) {
+  ChainRouteIn in = p.route;
+  in.whole = r.map < 0;
+  in.region = ChainRect{r.i0, r.j0, r.i1, r.j1};
+  in.keep_normals = (flags & TE_RUN_KEEP_NORMALS) != 0;
+  in.normals_only = (flags & TE_RUN_NORMALS_ONLY) != 0;  // measurement aid: the dominant kernel alone
+  in.generic_kernels = (flags & TE_RUN_GENERIC_KERNELS) != 0;
+  in.defer_combine = (flags & kDeferCombine) != 0;
+  in.aux_stream = L.aux_stream != nullptr;
+  in.sparse_holes = L.sparse_holes != 0;
+  in.no_holes = L.no_holes != 0;
+  in.skip_clean = L.skip_clean != 0;
+  in.short_strips = L.short_strips != 0;
+  in.hole_queue = L.hole_queue != nullptr;
+  in.clip_table = L.clip_table != nullptr;
+  in.tie_scratch = L.tie_scratch != nullptr;
+  in.block_flags = L.block_flags != nullptr;
+  in.guard_rows_elev = layer_has_guard_rows(L.elev, g, sizeof(float));  // (the marches load rows beyond the layer: te_internal.h)
+  in.guard_rows_step_height = layer_has_guard_rows(L.step_height, g, sizeof(float));
+  return in;
+}
+
+Region region_of(const Region& r, const ChainRect& c) { return Region{r.map, c.i0, c.j0, c.i1, c.j1}; }
+
+// StepFilter pass 1 on r1 (a region run: the region dilated by the first window), pass 2 on r2 (by first + second)
+hipError_t launch_step_filter(const Geo& g, const ChainParams& p, const Layers& L, const ChainRoute& rt, const Region& r1, const Region& r2,
+                              hipStream_t s) {
   const dim3 blk(TX, BY);
-  const bool use_fast = (flags & TE_RUN_GENERIC_KERNELS) == 0;
-  if (filter == TE_FILTER_SLOPE) {
+  hipError_t e = hipSuccess;
+  switch (rt.step_height.kind) {
+    case kStepAny: e = any::step_height(g, p.step1, L.elev, L.step_height, r1, s); break;
+    case kStepSmall: e = step_height_small(p.step1, g, L.elev, L.step_height, r1, s); break;
+    case kStepMarch: e = step_height5(rt.step_height.Q, g, L.elev, L.step_height, nullptr, r1, s); break;
+    case kStepMarchTies: e = step_height_ties(p.step1, rt.step_height.Q, g, L.elev, L.step_height, L.tie_scratch, r1, s); break;
+    case kStepGeneric:
+      hipLaunchKernelGGL(k_step_height, tile_grid(g, r1), blk, tile_bytes(p.step1.reach), s, g, p.step1, L.elev, L.step_height, r1);
+      break;
+  }
+  if (e != hipSuccess) return e;
+  switch (rt.step_score.kind) {
+    case kStepAny: return any::step_score(g, p.step2, p.step_crit, p.step_ncrit, L.step_height, L.step, r2, s);
+    case kStepSmall: return step_score_small(p.step2, g, p.step_crit, p.step_ncrit, L.step_height, L.step, r2, s);
+    case kStepMarch: return step_score5(rt.step_score.Q, g, p.step_crit, p.step_ncrit, L.step_height, L.step, nullptr, r2, s);
+    case kStepMarchTies:
+      return step_score_ties(p.step2, rt.step_score.Q, g, p.step_crit, p.step_ncrit, L.step_height, L.step, L.tie_scratch, r2, s);
+    case kStepGeneric:
+      hipLaunchKernelGGL(k_step_score, tile_grid(g, r2), blk, tile_bytes(p.step2.reach), s, g, p.step2, p.step_crit, p.step_ncrit,
+                         L.step_height, L.step, r2);
+      break;
+  }
+  return hipSuccess;
+}
+
+// k_normals' arguments for the discs dn / dr; given: RoughnessFilter alone with the normals of the layers (no weights)
+NormalsArgs normals_args(const ChainParams& p, const Disc& dn, const Disc& dr, bool same_disc, bool given, bool combine) {
+  NormalsArgs na;
+  na.dn = dn;
+  na.dr = dr;
+  na.same_disc = same_disc ? 1 : 0;
+  na.axis = p.axis;
+  na.rank_rule = p.rank_rule;
+  na.slope_crit = p.slope_crit;
+  na.rough_crit = p.rough_crit;
+  na.w_scale = given ? 0.0f : p.w_scale;
+  na.w_slope = given ? 0.0f : p.w_slope;
+  na.w_step = given ? 0.0f : p.w_step;
+  na.w_rough = given ? 0.0f : p.w_rough;
+  na.combine = combine ? 1 : 0;
+  na.given_normals = given ? 1 : 0;
+  na.band_slope = clip_band_slope(p.slope_crit);
+  na.band_rough = clip_band_rough(p.rough_crit);
+  return na;
+}
+
+// The normals stage of route rt on region rn (+ the fix-up pass); nx, ny, nz: the normals to keep (given normals: the inputs)
+hipError_t launch_normals(const Geo& g, const ChainParams& p, const Layers& L, const ChainRoute& rt, const ChainRouteIn& in,
+                          const NormalsArgs& na, bool given, float* nx, float* ny, float* nz, const Region& rn, hipStream_t s) {
+  const dim3 blk(TX, BY);
+  const int Kn = na.dn.reach > na.dr.reach ? na.dn.reach : na.dr.reach;
+  const bool shape_form = rt.normals == kNormalsSlideShape;
+  hipError_t e = hipSuccess;
+  switch (rt.normals) {
+    case kNormalsAny: return any::normals(g, na, L, nx, ny, nz, rn, s);
+    case kNormalsGeneric:
+      hipLaunchKernelGGL(k_normals, tile_grid(g, rn), blk, tile_bytes(Kn), s, g, na, L.elev, L.step, L.slope, L.rough, L.trav, nx, ny, nz, rn);
+      return hipSuccess;
+    case kNormalsSmall: return normals_small(g, p, L, rt.keep, rt.cross, rn, s, false, false);  // (settles every cell itself)
+    case kNormals3Slim:
+    case kNormals3Sparse:
+    case kNormals3Dense:
+    case kNormals3Ties: e = normals3(g, p, L, rt, in.normals, rn, L.block_flags, s); break;
+    case kNormalsSlideShape:
+    case kNormalsSlideRadius:
+      e = given ? normals_slide(g, p, L, p.rough, (int)in.rough.sii_runs, shape_form, true, true, false, rn, L.block_flags, s)
+                : normals_slide(g, p, L, p.normals, (int)in.normals.sii_runs, shape_form, false, rt.keep, na.combine != 0, rn, L.block_flags, s);
+      break;
+    case kNormalsNone: return hipErrorInvalidValue;
+  }
+  if (e != hipSuccess || !rt.fixup) return e;
+  const FastGrid fg = fast_grid(g, rn);
+  hipLaunchKernelGGL(k_normals_fixup, dim3((unsigned)fix_groups(fg.ntx * fg.nty * fg.nbz)), blk, tile_bytes(Kn), s, g, na, L.elev, L.step,
+                     L.slope, L.rough, L.trav, nx, ny, nz, L.block_flags, fg, rn);
+  return hipSuccess;
+}
+
+void launch_combine(const Geo& g, const ChainParams& p, const Layers& L, const Region& rc, hipStream_t s) {
+  const dim3 cgrid((unsigned)((rc.i1 - rc.i0 + 255) / 256), (unsigned)(rc.j1 - rc.j0), (unsigned)(rc.map >= 0 ? 1 : g.batch));
+  hipLaunchKernelGGL(k_combine, cgrid, dim3(256), 0, s, g, p.w_scale, p.w_slope, p.w_step, p.w_rough, L.slope, L.step, L.rough, L.trav, rc);
+}
+
+// The stages of route rt on region r, one after the other or on two streams
+hipError_t launch_route(const Geo& g, const ChainParams& p, const Layers& L, const Region& r, const ChainRouteIn& in, const ChainRoute& rt,
+                        hipStream_t stream) {
+  const bool comb_in_chain = rt.combine == kCombineInChain;
+  hipError_t e;
+  // SINGLE-CELL STEP WINDOWS and a normals disc k_normals_small takes (the reference's defaults on a map coarser than
+  // 0.04 m): the step score needs no neighbour -- 1 where the elevation is valid, NaN elsewhere (te_normals_small.hip) --, so
+  // that kernel writes the step layer and the weighted sum as well: the whole chain is ONE kernel
+  // (4096^2, default parameters at res 0.05: 0.34 -> 0.24 ms; 256^2: 17 -> 5 us).  Whole-map runs only: a region run
+  // re-filters dilated regions stage by stage.
+  if (rt.whole == kWholeChainWindow) {  // a small launch: the whole chain in one kernel
+    TraceRange tr("chain: one kernel (k_chain_window)");
+    e = chain_window(g, p, L, rt.keep, r, comb_in_chain, stream);
+    return e != hipSuccess ? e : hipGetLastError();
+  }
+  if (rt.whole == kWholeNormalsSmall) {
+    TraceRange tr("chain: normals + slope + roughness + single-cell step windows + combine (one kernel)");
+    e = normals_small(g, p, L, rt.keep, rt.cross, r, stream, /*write_step*/ true, comb_in_chain);
+    return e != hipSuccess ? e : hipGetLastError();
+  }
+  // The step filter and the normals/slope/roughness kernel are independent until the combine: on whole
+  // maps they run concurrently on two HIP streams (each alone leaves the VALUs half idle), joined by an
+  // event before the combine.
+  hipStream_t ss = rt.two_streams ? L.aux_stream : stream;
+  if (rt.two_streams) {
+    (void)hipEventRecord(L.ev_fork, stream);
+    (void)hipStreamWaitEvent(ss, L.ev_fork, 0);
+  }
+  if (rt.steps) {
+    TraceRange tr("chain: step filter (height, score)");
+    if ((e = launch_step_filter(g, p, L, rt, region_of(r, rt.r_step1), region_of(r, rt.r_step2), ss)) != hipSuccess) return e;
+  }
+  if (rt.two_streams) (void)hipEventRecord(L.ev_join, ss);
+  {
+    TraceRange tr_normals("chain: normals + slope + roughness (+ fix-up)");
+    const NormalsArgs na = normals_args(p, p.normals, p.rough, p.same_rough_disc != 0, false, rt.combine == kCombineInNormals);
+    e = launch_normals(g, p, L, rt, in, na, false, rt.keep ? L.nx : nullptr, rt.keep ? L.ny : nullptr, rt.keep ? L.nz : nullptr,
+                       region_of(r, rt.r_normals), stream);
+    if (e != hipSuccess) return e;
+  }
+  if (rt.two_streams) (void)hipStreamWaitEvent(stream, L.ev_join, 0);
+  // (region runs: the region grown by the chain's reach; deferred: the footprint mask kernel writes the layer)
+  if (rt.combine == kCombineKernel) launch_combine(g, p, L, region_of(r, rt.r_combine), stream);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+void chain_route_template(const Geo& g, ChainParams& p) {
+  static const ChainRouteIn lab = lab_switches();
+  ChainRouteIn& in = p.route;
+  in = lab;
+  in.normals = disc_summary(p.normals);
+  in.rough = disc_summary(p.rough);
+  in.step1 = disc_summary(p.step1);
+  in.step2 = disc_summary(p.step2);
+  in.same_rough_disc = p.same_rough_disc != 0;
+  in.axis = p.axis;
+  in.res = g.res;
+  in.rows = g.rows;
+  in.cols = g.cols;
+  in.batch = g.batch;
+  in.cus = device_cus();
+}
+
+// One reference plugin at a time (the drop-in SlopeFilter / StepFilter / RoughnessFilter adapters), routed by
+// plan_filter_route (te_chain_route.h).
+hipError_t launch_filter(const Geo& g, const ChainParams& p, const Layers& L, int filter, unsigned flags, hipStream_t stream) {
+  const Region r = {-1, 0, 0, g.rows, g.cols};
+  if (filter == TE_FILTER_SLOPE) {  // (these two have no route to plan)
     const size_t n = (size_t)g.rows * g.cols * g.batch;
-    hipLaunchKernelGGL(k_slope_from_nz, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, g, p.slope_crit, L.nz,
-                       L.slope);
-  } else if (filter == TE_FILTER_STEP) {
-    hipError_t e;
-    if (p.step1.any) {
-      if ((e = any::step_height(g, p.step1, L.elev, L.step_height, r, stream)) != hipSuccess) return e;
-    } else if (!(use_fast && (fast::step_height_fast(p.step1.Q, g, L.elev, L.step_height, r, stream) ||
-                              fast::step_height_ties(p.step1, g, L.elev, L.step_height, L.tie_scratch, r, stream))))
-      hipLaunchKernelGGL(k_step_height, tile_grid(g, r), blk, tile_bytes(p.step1.reach), stream, g, p.step1, L.elev,
-                         L.step_height, r);
-    if (p.step2.any) {
-      if ((e = any::step_score(g, p.step2, p.step_crit, p.step_ncrit, L.step_height, L.step, r, stream)) != hipSuccess) return e;
-    } else if (!(use_fast && (fast::step_score_fast(p.step2.Q, g, p.step_crit, p.step_ncrit, L.step_height, L.step, r, stream) ||
-                       fast::step_score_ties(p.step2, g, p.step_crit, p.step_ncrit, L.step_height, L.step, L.tie_scratch, r, stream))))
-      hipLaunchKernelGGL(k_step_score, tile_grid(g, r), blk, tile_bytes(p.step2.reach), stream, g, p.step2, p.step_crit,
-                         p.step_ncrit, L.step_height, L.step, r);
+    hipLaunchKernelGGL(k_slope_from_nz, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, g, p.slope_crit, L.nz, L.slope);
+    return hipGetLastError();
+  }
+  if (filter == TE_FILTER_COMBINE) {
+    launch_combine(g, p, L, r, stream);
+    return hipGetLastError();
+  }
+  if (filter != TE_FILTER_STEP && filter != TE_FILTER_ROUGHNESS && filter != TE_FILTER_NORMALS) return hipErrorInvalidValue;
+  const ChainRouteIn in = route_inputs(g, p, L, r, flags);
+  const ChainRoute rt = plan_filter_route(in, filter);
+  hipError_t e;
+  if (filter == TE_FILTER_STEP) {
+    e = launch_step_filter(g, p, L, rt, r, r, stream);
   } else if (filter == TE_FILTER_ROUGHNESS) {
-    NormalsArgs na;
-    na.dn = p.rough;
-    na.dr = p.rough;
-    na.same_disc = 1;
-    na.axis = p.axis;
-    na.rank_rule = p.rank_rule;
-    na.slope_crit = p.slope_crit;
-    na.rough_crit = p.rough_crit;
-    na.w_scale = na.w_slope = na.w_step = na.w_rough = 0.0f;
-    na.combine = 0;
-    na.given_normals = 1;
-    na.band_slope = clip_band_slope(p.slope_crit);
-    na.band_rough = clip_band_rough(p.rough_crit);
     // tie-free discs: the sliding kernel with the layers' normals (interior, hole-free discs in closed form from the
     // moments), the fix-up pass for the frame and the holes; otherwise the generic kernel on every cell
-    FastGrid fg;
-    if (p.rough.any) return any::normals(g, na, L, L.nx, L.ny, L.nz, r, stream);  // (a disc marked Disc::any: te_filter_any.hip, whatever the flags)
-    if (use_fast && fast::roughness_given_fast(g, p, L, r, L.block_flags, &fg, stream))
-      hipLaunchKernelGGL(k_normals_fixup, dim3((unsigned)fix_groups(fg.ntx * fg.nty * fg.nbz)), blk, tile_bytes(p.rough.reach), stream, g, na,
-                         L.elev, L.step, L.slope, L.rough, L.trav, L.nx, L.ny, L.nz, L.block_flags, fg, r);
-    else
-      hipLaunchKernelGGL(k_normals, tile_grid(g, r), blk, tile_bytes(p.rough.reach), stream, g, na, L.elev, L.step, L.slope,
-                         L.rough, L.trav, L.nx, L.ny, L.nz, r);
-  } else if (filter == TE_FILTER_NORMALS) {
+    e = launch_normals(g, p, L, rt, in, normals_args(p, p.rough, p.rough, true, true, false), true, L.nx, L.ny, L.nz, r, stream);
+  } else {
     // the normals pass alone, normals kept: the sliding kernel computes slope and roughness on the way (same disc), the
     // plugins that want those layers compute them from their own inputs later
     ChainParams q = p;
     q.rough = q.normals;
     q.same_rough_disc = 1;
-    return launch_chain(g, q, L, r, (flags & TE_RUN_GENERIC_KERNELS) | TE_RUN_KEEP_NORMALS | TE_RUN_NORMALS_ONLY, stream);
-  } else if (filter == TE_FILTER_COMBINE) {
-    const dim3 cgrid((unsigned)((g.rows + 255) / 256), (unsigned)g.cols, (unsigned)g.batch);
-    hipLaunchKernelGGL(k_combine, cgrid, dim3(256), 0, stream, g, p.w_scale, p.w_slope, p.w_step, p.w_rough, L.slope,
-                       L.step, L.rough, L.trav, r);
-  } else {
-    return hipErrorInvalidValue;
+    return launch_route(g, q, L, r, in, rt, stream);
   }
-  return hipGetLastError();
+  return e != hipSuccess ? e : hipGetLastError();
 }
 
-hipError_t launch_chain(const Geo& g, const ChainParams& p, const Layers& L, const Region& r, unsigned flags,
-                        hipStream_t stream) {
+// The chain on region r, routed by plan_chain_route (te_chain_route.h): DESIGN.md 4.7.
+hipError_t launch_chain(const Geo& g, const ChainParams& p, const Layers& L, const Region& r, unsigned flags, hipStream_t stream) {
   if (r.i1 <= r.i0 || r.j1 <= r.j0) return hipSuccess;
-  const bool whole = (r.map < 0);
-  const dim3 blk(TX, BY);
-  // StepFilter pass 1 on the region dilated by the first window, pass 2 on first+second.
-  const Region r1 = whole ? r : clamp_region(g, r, p.step1.reach);
-  const Region r2 = whole ? r : clamp_region(g, r, p.step1.reach + p.step2.reach);
-  const Region rn = whole ? r : clamp_region(g, r, p.normals.reach > p.rough.reach ? p.normals.reach : p.rough.reach);
-  const Region rc = whole ? r : clamp_region(g, r, chain_max_reach(p));
-  const bool use_fast = (flags & TE_RUN_GENERIC_KERNELS) == 0;
-  // The step filter and the normals/slope/roughness kernel are independent until the combine: on whole
-  // maps they run concurrently on two HIP streams (each alone leaves the VALUs half idle), joined by an
-  // event before the combine.
-  const bool normals_only = (flags & TE_RUN_NORMALS_ONLY) != 0;  // measurement aid: the dominant kernel alone
-  // SINGLE-CELL STEP WINDOWS and a normals disc k_normals_small takes (the reference's defaults on a map coarser than
-  // 0.04 m): the step score needs no neighbour -- 1 where the elevation is valid, NaN elsewhere (te_normals_small.hip) --, so
-  // that kernel writes the step layer and the weighted sum as well: the whole chain is ONE kernel
-  // (4096^2, default parameters at res 0.05: 0.34 -> 0.24 ms; 256^2: 17 -> 5 us).  Whole-map runs only: a region run
-  // re-filters dilated regions stage by stage as before.
-  // (a disc marked Disc::any takes te_filter_any.hip for its own stage: none of the one-kernel chains)
-  const bool any_normals = p.normals.any || p.rough.any;
-  const bool any_disc = any_normals || p.step1.any || p.step2.any;
-  if (whole && use_fast && !any_disc && !normals_only && p.same_rough_disc && p.axis == 2) {  // a small launch: the whole chain in one kernel
-    TraceRange tr("chain: one kernel (k_chain_window)");
-    if (fast::chain_window(g, p, L, (flags & TE_RUN_KEEP_NORMALS) != 0, r, !(flags & kDeferCombine), stream)) return hipGetLastError();
-  }
-  if (whole && use_fast && !any_disc && !normals_only && p.same_rough_disc && p.axis == 2 && p.step1.n_ties == 0 && p.step1.Q == 0 &&
-      p.step2.n_ties == 0 && p.step2.Q == 0) {
-    const bool comb = !(flags & kDeferCombine);
-    FastGrid fg;
-    TraceRange tr("chain: normals + slope + roughness + single-cell step windows + combine (one kernel)");
-    if (fast::normals_small(g, p, L, (flags & TE_RUN_KEEP_NORMALS) != 0, r, L.block_flags, &fg, stream, /*write_step*/ true, comb)) {
-      return hipGetLastError();
-    }
-  }
-  const bool overlap = whole && L.aux_stream != nullptr && !normals_only;
-  hipStream_t ss = overlap ? L.aux_stream : stream;
-  if (overlap) {
-    (void)hipEventRecord(L.ev_fork, stream);
-    (void)hipStreamWaitEvent(ss, L.ev_fork, 0);
-  }
-  if (!normals_only) {
-    TraceRange tr("chain: step filter (height, score)");
-    hipError_t e;
-    if (p.step1.any) {
-      if ((e = any::step_height(g, p.step1, L.elev, L.step_height, r1, ss)) != hipSuccess) return e;
-    } else if (!(use_fast && (fast::step_height_fast(p.step1.Q, g, L.elev, L.step_height, r1, ss) ||
-                              fast::step_height_ties(p.step1, g, L.elev, L.step_height, L.tie_scratch, r1, ss))))
-      hipLaunchKernelGGL(k_step_height, tile_grid(g, r1), blk, tile_bytes(p.step1.reach), ss, g, p.step1, L.elev,
-                         L.step_height, r1);
-    if (p.step2.any) {
-      if ((e = any::step_score(g, p.step2, p.step_crit, p.step_ncrit, L.step_height, L.step, r2, ss)) != hipSuccess) return e;
-    } else if (!(use_fast && (fast::step_score_fast(p.step2.Q, g, p.step_crit, p.step_ncrit, L.step_height, L.step, r2, ss) ||
-                       fast::step_score_ties(p.step2, g, p.step_crit, p.step_ncrit, L.step_height, L.step, L.tie_scratch, r2, ss))))
-      hipLaunchKernelGGL(k_step_score, tile_grid(g, r2), blk, tile_bytes(p.step2.reach), ss, g, p.step2, p.step_crit,
-                         p.step_ncrit, L.step_height, L.step, r2);
-  }
-  if (overlap) (void)hipEventRecord(L.ev_join, ss);
-  const bool keep = (flags & TE_RUN_KEEP_NORMALS) != 0;
-  const int Kn = p.normals.reach > p.rough.reach ? p.normals.reach : p.rough.reach;
-  NormalsArgs na;
-  na.dn = p.normals;
-  na.dr = p.rough;
-  na.same_disc = p.same_rough_disc;
-  na.axis = p.axis;
-  na.rank_rule = p.rank_rule;
-  na.slope_crit = p.slope_crit;
-  na.rough_crit = p.rough_crit;
-  na.w_scale = p.w_scale;
-  na.w_slope = p.w_slope;
-  na.w_step = p.w_step;
-  na.w_rough = p.w_rough;
-  na.given_normals = 0;
-  na.band_slope = clip_band_slope(p.slope_crit);
-  na.band_rough = clip_band_rough(p.rough_crit);
-  // the combine is fused into the normals kernel only when the step layer is complete before it starts;
-  // region runs: the step reach may exceed the normals reach, combine separately
-  na.combine = (whole && !overlap && !normals_only && !(flags & kDeferCombine)) ? 1 : 0;
-  float* const knx = keep ? L.nx : nullptr;
-  float* const kny = keep ? L.ny : nullptr;
-  float* const knz = keep ? L.nz : nullptr;
-  const bool fused_combine = whole && !overlap && !normals_only && !(flags & kDeferCombine);
-  FastGrid fg;
-  bool combined = false;
-  TraceRange tr_normals("chain: normals + slope + roughness (+ fix-up)");
-  if (any_normals) {
-    combined = na.combine != 0;
-    const hipError_t e = any::normals(g, na, L, knx, kny, knz, rn, stream);
-    if (e != hipSuccess) return e;
-  } else if (use_fast && p.same_rough_disc && p.axis == 2 &&
-      fast::normals_fast(g, p, L, keep, fused_combine, rn, L.block_flags, L.clip_table, &fg, stream, &combined)) {
-    na.combine = combined ? 1 : 0;
-    if (fg.frame >= 0)  // (k_normals_small settles every cell itself)
-      hipLaunchKernelGGL(k_normals_fixup, dim3((unsigned)fix_groups(fg.ntx * fg.nty * fg.nbz)), blk, tile_bytes(Kn), stream, g, na, L.elev, L.step, L.slope,
-                       L.rough, L.trav, knx, kny, knz, L.block_flags, fg, rn);
-  } else {
-    combined = na.combine != 0;
-    hipLaunchKernelGGL(k_normals, tile_grid(g, rn), blk, tile_bytes(Kn), stream, g, na, L.elev, L.step, L.slope,
-                       L.rough, L.trav, knx, kny, knz, rn);
-  }
-  if (overlap) (void)hipStreamWaitEvent(stream, L.ev_join, 0);
-  // with the footprint pass right behind, its mask kernel (which reads the three scores anyway) combines
-  if (!combined && !normals_only && !(flags & kDeferCombine)) {
-    const dim3 cgrid((unsigned)((rc.i1 - rc.i0 + 255) / 256), (unsigned)(rc.j1 - rc.j0),
-                     (unsigned)(rc.map >= 0 ? 1 : g.batch));
-    hipLaunchKernelGGL(k_combine, cgrid, dim3(256), 0, stream, g, p.w_scale, p.w_slope, p.w_step, p.w_rough, L.slope,
-                       L.step, L.rough, L.trav, rc);
-  }
-  return hipGetLastError();
+  const ChainRouteIn in = route_inputs(g, p, L, r, flags);
+  return launch_route(g, p, L, r, in, plan_chain_route(in), stream);
 }
 
 }  // namespace te

@@ -16,38 +16,12 @@
 #include <utility>
 
 #include "te_internal.h"
+#include "te_shapes.h"  // Shape<Q> and the shape lists
 
 namespace te {
 namespace fast {
 
-constexpr int isqrt_c(int v) {
-  int r = 0;
-  while ((r + 1) * (r + 1) <= v) ++r;
-  return r;
-}
-
-template <int Q>
-struct Shape {
-  static constexpr int R = isqrt_c(Q);
-  static constexpr int P = 2 * R + 1;  // accumulators in flight == rows per unrolled period
-  // half-width of the run at column offset d (0 <= d <= R)
-  static constexpr int hw(int d) { return isqrt_c(Q - d * d); }
-  static constexpr int npoints() {
-    int n = 0;
-    for (int d = -R; d <= R; ++d) n += 2 * hw(d < 0 ? -d : d) + 1;
-    return n;
-  }
-};
-
 constexpr int kLanes = 64;
-
-// The disc shapes (Q = largest di^2+dj^2 in the disc) with radius up to 10 cells: every sum of two squares <= 100.
-#ifndef TE_DISC_SHAPES  // (tools: -D'TE_DISC_SHAPES(X)=X(81)' compiles one shape)
-#define TE_DISC_SHAPES(X) \
-  X(0) X(1) X(2) X(4) X(5) X(8) X(9) X(10) X(13) X(16) X(17) X(18) X(20) X(25) X(26) X(29) X(32) X(34) X(36) X(37) \
-  X(40) X(41) X(45) X(49) X(50) X(52) X(53) X(58) X(61) X(64) X(65) X(68) X(72) X(73) X(74) X(80) X(81) X(82) X(85) \
-  X(89) X(90) X(97) X(98) X(100)
-#endif
 
 __device__ __forceinline__ float qnan() { return __builtin_nanf(""); }
 

@@ -1157,17 +1157,14 @@ __global__ __launch_bounds__(kLanes) __attribute__((amdgpu_waves_per_eu(TIES ? k
 // host counted them at upload (N3Args::no_holes) -- and shapes whose centre column alone reaches rows j +- R.  Should an
 // invalid cell turn up all the same (the layer was written behind the library's back), the rest of the strip goes to
 // the fix-up pass, which is correct for any input.
-constexpr int n3_blocks_per_cu(int lds_bytes) {  // single-wave blocks the LDS admits (2 KiB granules, tools/census.hip), at most 3 waves per SIMD
-  const int n = (160 * 1024) / (((lds_bytes + 2047) / 2048) * 2048);
-  return n > kN3Waves * 4 ? kN3Waves * 4 : n;
-}
+static_assert(kN3Waves == kN3RouteWaves && kN3TieWaves == kN3RouteTieWaves, "te_chain_route.h plans the resident blocks for these waves per SIMD");
 // ... and only where the two rows saved buy a resident block: R = 9 (11 -> 12 per CU) and R = 10 (10 -> 11).  At smaller
 // radii both rings admit the 12 blocks the registers allow, and the slim march -- chunks of 2 or 3 rows instead of 4, more
 // chunk rotations -- measured 2 % slower there (8192^2 at R = 5: 1.156 -> 1.18 ms per launch).
+// (te_chain_route.h: n3_slim_shape, the LDS arithmetic of the plan)
 template <int Q>
 constexpr bool slim_shape() {
-  constexpr int R = Shape<Q>::R, W = kLanes + 2 * R;
-  return R >= 2 && Shape<Q>::hw(1) < R && n3_blocks_per_cu(2 * R * W * 8) > n3_blocks_per_cu((2 * R + 2) * W * 8 + (2 * R + 2) * 16);
+  return n3_slim_shape(Q);
 }
 template <int Q>
 __global__ __launch_bounds__(kLanes) __attribute__((amdgpu_waves_per_eu(kN3Waves, kN3Waves))) void k_normals3s(N3Args a) {
@@ -1204,81 +1201,42 @@ __global__ __launch_bounds__(kLanes) __attribute__((amdgpu_waves_per_eu(kN3Waves
   }
 }
 
+// One launch of the march the plan named (te_chain_route.h: plan_n3): as many blocks as fill the resident wave slots in ONE
+// round, the strip plan in `a`.  The LDS the plan counted on is the LDS the kernels declare:
 template <int Q>
-int resident_blocks_slim() {
+hipError_t launch3(const N3Args& a, const ChainRoute& rt, int maps, hipStream_t s) {
   constexpr int R = Shape<Q>::R;
-  constexpr int lds = (2 * R) * (kLanes + 2 * R) * 8;
-  int per_cu = (160 * 1024) / (((lds + 2047) / 2048) * 2048);
-  if (per_cu > kN3Waves * 4) per_cu = kN3Waves * 4;
-  static const int ov = lab_int("TE_N3_BLOCKS_PER_CU", 0);  // measurement aid
-  if (ov > 0) per_cu = ov < kN3Waves * 4 ? ov : kN3Waves * 4;
-  return per_cu * device_cus();
-}
-
-// Resident single-wave blocks per CU and CUs of the current device.  The LDS allocation granularity decides: at R = 9
-// (13 120 B) 11 blocks fit, not 12 (tools/census.hip), and a grid of 12 per CU runs in two rounds -- twice the time.
-template <int Q, bool KEEP>
-int resident_blocks(bool ties = false) {
-  // (hipOccupancyMaxActiveBlocksPerMultiprocessor answers 12 for 13 120 B; the hardware admits 11: the census fits an
-  // allocation granule of 1280..2048 bytes, the conservative end is used here)
-  constexpr int R = Shape<Q>::R;
-  constexpr int lds = (2 * R + 2) * (kLanes + 2 * R) * 8 + (2 * R + 2) * 16;  // ring + hole masks
-  int per_cu = (160 * 1024) / (((lds + 2047) / 2048) * 2048);
-  if (per_cu > kN3Waves * 4) per_cu = kN3Waves * 4;
-  if (ties && per_cu > kN3TieWaves * 4) per_cu = kN3TieWaves * 4;
-  static const int ov = lab_int("TE_N3_BLOCKS_PER_CU", 0);  // measurement aid
-  if (ov > 0) per_cu = ov < kN3Waves * 4 ? ov : kN3Waves * 4;  // (the hole queues are allocated for kN3Waves * 4 per CU)
-  return per_cu * device_cus();
-}
-
-template <int Q>
-bool launch3(const Geo& g, const N3Args& a0, bool keep, int maps, hipStream_t s) {
-  N3Args a = a0;
-  // As many blocks as fill the resident wave slots in ONE round.  Edge block columns run the general tail on every row
-  // (about 1.5x the time of an interior row): their strips are 1.5x shorter so that all blocks finish together.
-  static const bool no_slim = lab_flag("TE_N3_NO_SLIM");  // measurement aid
-  const bool slim = slim_shape<Q>() && a.no_holes && !keep && a.n_ties == 0 && !no_slim;
-  const int resident = slim ? resident_blocks_slim<Q>() : keep ? resident_blocks<Q, true>(a.n_ties != 0) : resident_blocks<Q, false>(a.n_ties != 0);
-  constexpr int R = Shape<Q>::R;
-  static const int pct_env = lab_int("TE_N3_EDGE_PERCENT", 50);  // measurement aid: strip height of the edge columns in percent
-  static const int rows_env = lab_int("TE_N3_STRIP_ROWS", 0);    // measurement aid
-  // strips of 32 rows only when the upload counted invalid cells and the dense march serves them (Layers::short_strips): a
-  // clean map would pay the extra strip starts for nothing (profiles/r05_experiments.json, exp13)
-  bool fits = false;
-  const int nblocks = n3_plan_strips(a, g.cols, R, resident, maps, a.short_strips && !slim && a.n_ties == 0, pct_env, rows_env, &fits);
-  (void)fits;
-  if (nblocks <= 0) return true;
-  const dim3 grid((unsigned)nblocks, 1, (unsigned)maps);
+  static_assert(n3_lds_bytes(R, false) == (int)(sizeof(double) * (2 * R + 2) * (kLanes + 2 * R) + sizeof(unsigned long long) * (2 * R + 2) * 2),
+                "k_normals3: ring + hole masks");
+  static_assert(n3_lds_bytes(R, true) == (int)(sizeof(double) * (2 * R) * (kLanes + 2 * R)), "k_normals3s: the slim ring");
+  const dim3 grid((unsigned)rt.n3_blocks, 1, (unsigned)maps);
   constexpr unsigned kDyn = TE_N3_DYN_LDS ? (unsigned)((2 * R + 2) * (kLanes + 2 * R) * 8) : 0u;  // the ring, when the kernel declares it extern
-  if (a.n_ties != 0) {  // tie radius: the whole-cell shapes only
-    if constexpr (R * R == Q && R >= 3) {  // (tie radii of one and two cells: k_normals_small, te_normals_small.hip)
-      // the kernel knows the circle's cells from R (te_tie_triple.h): the disc's own table must say the same
-      if (a.n_gen != tie_triple_cells(R) || a.n_ties != 4 + a.n_gen) return false;
-      if (keep)
-        hipLaunchKernelGGL((k_normals3<Q, true, 2, true>), grid, dim3(kLanes), kDyn, s, a);
+  switch (rt.normals) {
+    case kNormals3Ties:  // tie radius: the whole-cell shapes only (one and two cells: k_normals_small)
+      if constexpr (R * R == Q && R >= 3) {
+        if (rt.keep)
+          hipLaunchKernelGGL((k_normals3<Q, true, 2, true>), grid, dim3(kLanes), kDyn, s, a);
+        else
+          hipLaunchKernelGGL((k_normals3<Q, false, 2, true>), grid, dim3(kLanes), kDyn, s, a);
+        return hipSuccess;
+      }
+      return hipErrorInvalidValue;
+    case kNormals3Slim:
+      if (!slim_shape<Q>()) return hipErrorInvalidValue;
+      hipLaunchKernelGGL((k_normals3s<Q>), grid, dim3(kLanes), 0, s, a);
+      return hipSuccess;
+    case kNormals3Sparse:
+    case kNormals3Dense:  // (the kernel that keeps the normals -- the plugin path -- exists with the dense march only)
+      if (rt.keep)
+        hipLaunchKernelGGL((k_normals3<Q, true, 2>), grid, dim3(kLanes), kDyn, s, a);
+      else if (rt.normals == kNormals3Sparse)
+        hipLaunchKernelGGL((k_normals3<Q, false, 1>), grid, dim3(kLanes), kDyn, s, a);
       else
-        hipLaunchKernelGGL((k_normals3<Q, false, 2, true>), grid, dim3(kLanes), kDyn, s, a);
-      return true;
-    }
-    return false;
+        hipLaunchKernelGGL((k_normals3<Q, false, 2>), grid, dim3(kLanes), kDyn, s, a);
+      return hipSuccess;
+    default:
+      return hipErrorInvalidValue;
   }
-  if (slim) {
-    hipLaunchKernelGGL((k_normals3s<Q>), grid, dim3(kLanes), 0, s, a);
-    return true;
-  }
-  // (the kernel that keeps the normals -- the plugin path -- exists with the dense march only)
-  // The sparse march indexes its queue scratch by block (blockIdx.x + gridDim.x * blockIdx.z) and the scratch holds one
-  // queue per RESIDENT block of the device (normals_hole_queue_bytes): a grid that did not fit one round -- no strip
-  // height up to 512 rows fits `capacity` on a large batch, a very large map or a small / partitioned device -- has more
-  // blocks than queues and takes the dense march, which needs no scratch.
-  const bool queues_fit = (long long)nblocks * (long long)(maps > 0 ? maps : 1) <= (long long)(kN3Waves * 4) * (long long)device_cus();
-  if (keep)
-    hipLaunchKernelGGL((k_normals3<Q, true, 2>), grid, dim3(kLanes), kDyn, s, a);
-  else if (a.sparse_holes && queues_fit)
-    hipLaunchKernelGGL((k_normals3<Q, false, 1>), grid, dim3(kLanes), kDyn, s, a);
-  else
-    hipLaunchKernelGGL((k_normals3<Q, false, 2>), grid, dim3(kLanes), kDyn, s, a);
-  return true;
 }
 
 }  // namespace
@@ -1286,13 +1244,7 @@ bool launch3(const Geo& g, const N3Args& a0, bool keep, int maps, hipStream_t s)
 // Shapes this file is instantiated for: every disc shape up to radius 10 (te_march.h) except the single cell.  The file
 // is compiled in TE_PARTS parts (build.py: -DTE_PARTS=6 -DTE_PART=k, one object each, side by side) -- the 43 shapes x
 // 2 x 4 marches take 13 minutes in one translation unit.  Part k instantiates the shapes of its list and exports one
-// function that launches them; part 0 also holds normals_fast3.  -DTE_N3_SHAPES=... (tools) compiles one part with that list.
-#define TE_N3_P0(X) X(9) X(20) X(32) X(52) X(61) X(72) X(100)
-#define TE_N3_P1(X) X(8) X(18) X(29) X(50) X(58) X(82) X(98)
-#define TE_N3_P2(X) X(5) X(17) X(26) X(49) X(53) X(81) X(97)
-#define TE_N3_P3(X) X(4) X(16) X(37) X(45) X(68) X(80) X(90)
-#define TE_N3_P4(X) X(10) X(13) X(36) X(41) X(65) X(74) X(89)
-#define TE_N3_P5(X) X(1) X(2) X(25) X(34) X(40) X(64) X(73) X(85)
+// function that launches them; part 0 also holds normals3.  -DTE_N3_SHAPES=... (tools) compiles one part with that list.
 #if !defined(TE_PARTS) || defined(TE_N3_SHAPES)
 #undef TE_PARTS
 #undef TE_PART
@@ -1314,13 +1266,13 @@ bool launch3(const Geo& g, const N3Args& a0, bool keep, int maps, hipStream_t s)
 #define TE_N3_NAME2(k) n3_launch_part##k
 #define TE_N3_NAME(k) TE_N3_NAME2(k)
 
-// launches shape Q if it belongs to this part (args: the N3Args block of part 0 -- the same struct in every part)
-bool TE_N3_NAME(TE_PART)(int Q, const Geo& g, const void* args, bool keep_normals, int maps, hipStream_t s, bool* ok) {
+// launches shape rt.n3_shape if it belongs to this part (args: the N3Args block of part 0 -- the same struct in every part)
+bool TE_N3_NAME(TE_PART)(const void* args, const ChainRoute& rt, int maps, hipStream_t s, hipError_t* e) {
   const N3Args& a = *static_cast<const N3Args*>(args);
-  switch (Q) {
-#define X(q)                                      \
-  case q:                                         \
-    *ok = launch3<q>(g, a, keep_normals, maps, s); \
+  switch (rt.n3_shape) {
+#define X(q)                            \
+  case q:                               \
+    *e = launch3<q>(a, rt, maps, s);    \
     return true;
     TE_N3_SHAPES(X)
 #undef X
@@ -1331,62 +1283,32 @@ bool TE_N3_NAME(TE_PART)(int Q, const Geo& g, const void* args, bool keep_normal
 
 #if TE_PART == 0
 #if TE_PARTS > 1
-bool n3_launch_part1(int Q, const Geo& g, const void* args, bool keep_normals, int maps, hipStream_t s, bool* ok);
-bool n3_launch_part2(int Q, const Geo& g, const void* args, bool keep_normals, int maps, hipStream_t s, bool* ok);
-bool n3_launch_part3(int Q, const Geo& g, const void* args, bool keep_normals, int maps, hipStream_t s, bool* ok);
-bool n3_launch_part4(int Q, const Geo& g, const void* args, bool keep_normals, int maps, hipStream_t s, bool* ok);
-bool n3_launch_part5(int Q, const Geo& g, const void* args, bool keep_normals, int maps, hipStream_t s, bool* ok);
+bool n3_launch_part1(const void* args, const ChainRoute& rt, int maps, hipStream_t s, hipError_t* e);
+bool n3_launch_part2(const void* args, const ChainRoute& rt, int maps, hipStream_t s, hipError_t* e);
+bool n3_launch_part3(const void* args, const ChainRoute& rt, int maps, hipStream_t s, hipError_t* e);
+bool n3_launch_part4(const void* args, const ChainRoute& rt, int maps, hipStream_t s, hipError_t* e);
+bool n3_launch_part5(const void* args, const ChainRoute& rt, int maps, hipStream_t s, hipError_t* e);
 #endif
 
 // Scratch of the sparse-hole march: one queue per resident block (the grids are sized to one round of resident blocks,
 // whatever the map and the batch).
 size_t normals_hole_queue_bytes() { return (size_t)(kN3Waves * 4) * (size_t)device_cus() * (size_t)kHoleQueueBytes; }
 
-// The normals / slope / roughness pass over region r (discs clipped by the map border included); returns false
-// if this kernel does not take the case (the caller then uses the sliding kernel of te_slide_normals.hip for everything).
-// On success the caller still owes the fix-up pass for the tiles this kernel flagged.
-bool normals_fast3(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, const Region& r, int* flags,
-                   FastGrid* fgp, hipStream_t s) {
-  FastGrid& fg = *fgp;
+// The normals / slope / roughness pass over region r (discs clipped by the map border included) with the march, the
+// shape and the strip plan of route rt (te_chain_route.h); ds: the summary of the normals disc the plan read.  The caller owes the
+// fix-up pass for the frame and the tiles this kernel flags.
+hipError_t normals3(const Geo& g, const ChainParams& p, const Layers& L, const ChainRoute& rt, const DiscSummary& ds, const Region& r, int* flags,
+                    hipStream_t s) {
+  const FastGrid fg = fast_grid(g, r);
   const Disc& d = p.normals;
-  if (d.any || p.rough.any) return false;  // (te_filter_any.hip)
-  // The shape the kernel slides: the disc, or for a tie radius the disc with its circle (whole-cell radii: every cell
-  // on the circle has the norm reach^2, the runs plus the circle are the shape reach^2)
-  int shape = d.Q, R = d.R;
-  if (d.n_ties != 0) {
-    static const bool no_ties = lab_flag("TE_N3_NO_TIES");  // measurement aid: tie radii to the generic kernel as before
-    R = d.reach;
-    shape = R * R;
-    if (no_ties) return false;
-    for (int t = 0; t < d.n_ties; ++t)
-      if ((int)d.tie_di[t] * d.tie_di[t] + (int)d.tie_dj[t] * d.tie_dj[t] != shape) return false;
-  }
-  // cells and sum(di^2) of the shape the kernel slides (a tie disc WITH its circle: at a radius of exactly one cell the runs
-  // hold the centre alone and the four edge neighbours are all ties -- robot_filter_parameter.yaml's 0.05 m on a 0.05 m map)
-  int shape_points = d.npoints;
-  long long sii = 0;  // of the runs (the constants of the closed-form tail below)
-  for (int dj = -d.R; dj <= d.R; ++dj) {
-    const int hw = d.hw[dj < 0 ? -dj : dj];
-    for (int di = -hw; di <= hw; ++di) sii += di * di;
-  }
-  long long shape_sii = sii;
-  for (int t = 0; t < d.n_ties; ++t) {
-    ++shape_points;
-    shape_sii += (int)d.tie_di[t] * d.tie_di[t];
-  }
-  if (R < 1 || shape < 1 || shape_points < 3) return false;
-  N3Args a;
-  a.i_lo = r.i0;
-  a.i_hi = r.i1;
-  a.j_lo = r.j0;
-  a.j_hi = r.j1;
-  if (a.i_hi - a.i_lo < kLanes || a.j_hi <= a.j_lo || !L.clip_table) return false;
-  if (g.rows < 2 * R + 1 || g.cols < 2 * R + 1) return false;  // both borders inside one disc: the clip codes do not cover that
-  if ((double)g.rows * (double)g.cols * 4.0 >= 4294967296.0) return false;  // 32-bit byte offsets inside a map
-  if (!(g.res * g.res * ((double)shape_sii / (double)shape_points) > 1e-8)) return false;  // NormalVectorsFilter's eigenvalue test would fail everywhere
+  if (rt.n3_blocks <= 0) return hipSuccess;
   // (N, sii of the runs: the constants of the closed-form tail of the tie-free marches; the TIES march takes every disc's
   // x/y moments from its clip table and the general tail)
   const double N = (double)(d.npoints > 1 ? d.npoints : 2);
+  N3Args a;
+#define X(f) a.f = rt.n3.f;
+  TE_N3_STRIP_FIELDS(X)  // (the strip plan; a.rows is the map's, as the plan's)
+#undef X
   a.elev = L.elev;
   a.slope = L.slope;
   a.rough = L.rough;
@@ -1398,11 +1320,9 @@ bool normals_fast3(const Geo& g, const ChainParams& p, const Layers& L, bool kee
   a.cols = g.cols;
   a.map_cells = (long long)g.rows * g.cols;
   a.map = r.map;
-  n3_plan_edges(a, g.rows, R);
   a.gtab = d.n_ties ? L.clip_table + kClipInts : L.clip_table;  // (ties: the table of the shape with its circle)
   a.n_ties = d.n_ties;
-  a.n_gen = 0;
-  for (int t = 0; t < d.n_ties; ++t) a.n_gen += (d.tie_di[t] != 0 && d.tie_dj[t] != 0) ? 1 : 0;
+  a.n_gen = ds.n_gen;
   a.gen_tab = L.clip_table + 2 * kClipInts;
   a.r2 = d.r2;
   a.ax = g.ax;
@@ -1415,8 +1335,8 @@ bool normals_fast3(const Geo& g, const ChainParams& p, const Layers& L, bool kee
   a.skip_clean = L.skip_clean;
   a.short_strips = L.short_strips;
   a.hole_queue = L.hole_queue;
-  a.SIIi = (int)sii;
-  a.K1h = 0.5 * N * g.res * g.res * (double)sii;
+  a.SIIi = (int)ds.sii_runs;
+  a.K1h = 0.5 * N * g.res * g.res * (double)ds.sii_runs;
   a.Kr2 = (N * g.res) * (N * g.res);
   a.kinv = 1.0 / (N * (N - 1.0));
   a.inv_slope_crit = (float)(1.0 / p.slope_crit);
@@ -1430,15 +1350,14 @@ bool normals_fast3(const Geo& g, const ChainParams& p, const Layers& L, bool kee
   a.nty = fg.nty;
   a.fix_groups = fix_groups(fg.ntx * fg.nty * fg.nbz);
   const int maps = r.map >= 0 ? 1 : g.batch;
-  bool ok = false;
-  if (n3_launch_part0(shape, g, &a, keep_normals, maps, s, &ok)) return ok;
+  hipError_t e = hipErrorInvalidValue;  // a planned shape without its instantiation
+  if (n3_launch_part0(&a, rt, maps, s, &e)) return e;
 #if TE_PARTS > 1
-  if (n3_launch_part1(shape, g, &a, keep_normals, maps, s, &ok) || n3_launch_part2(shape, g, &a, keep_normals, maps, s, &ok) ||
-      n3_launch_part3(shape, g, &a, keep_normals, maps, s, &ok) || n3_launch_part4(shape, g, &a, keep_normals, maps, s, &ok) ||
-      n3_launch_part5(shape, g, &a, keep_normals, maps, s, &ok))
-    return ok;
+  if (n3_launch_part1(&a, rt, maps, s, &e) || n3_launch_part2(&a, rt, maps, s, &e) || n3_launch_part3(&a, rt, maps, s, &e) ||
+      n3_launch_part4(&a, rt, maps, s, &e) || n3_launch_part5(&a, rt, maps, s, &e))
+    return e;
 #endif
-  return false;
+  return e;
 }
 #endif  // TE_PART == 0
 

@@ -32,7 +32,7 @@ namespace fast {
 
 namespace {
 
-constexpr int kSmallMaxOffsets = 12;  // the 13-point disc (reach 2) without its centre
+constexpr int kSmallMaxOffsets = kSmallOffsets;  // the 13-point disc (reach 2) without its centre
 constexpr int kSmallBY = 4;           // rows of a workgroup (64 x 4 threads, one cell each)
 
 struct SmallArgs {
@@ -419,18 +419,10 @@ void fill_common(SmallArgs& a, const Geo& g, const ChainParams& p, const Layers&
 
 // Discs that reach at most two cells, tie radii included: the one-cell tie radius of the default parameters on a 0.05 m
 // map first of all.  Tie-free discs of that size only on small launches (the sliding kernels are faster from about 2^18
-// cells on: 4096^2 at 1.67 cells 0.09 ms).  False: not taken.
-bool normals_small(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, const Region& r, int* flags, FastGrid* fg,
-                   hipStream_t s, bool write_step, bool combine) {
+// cells on: 4096^2 at 1.67 cells 0.09 ms).  The route is plan_chain_route's (te_chain_route.h); cross: the CROSS instantiation.
+hipError_t normals_small(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, bool cross, const Region& r, hipStream_t s,
+                         bool write_step, bool combine) {
   const Disc& d = p.normals;
-  static const bool off = lab_flag("TE_NO_SMALL");  // measurement aid
-  static const int max_cells_env = lab_int("TE_SMALL_MAX_CELLS", 0);
-  (void)flags;  // (no cell is left to the fix-up pass)
-  if (off || d.any || p.rough.any || d.reach < 1 || d.reach > 2) return false;
-  if ((double)g.rows * (double)g.cols * 4.0 >= 4294967296.0) return false;
-  const long long cells = (long long)(r.i1 - r.i0) * (r.j1 - r.j0) * (r.map >= 0 ? 1 : g.batch);
-  const long long small_launch = max_cells_env > 0 ? max_cells_env : (1ll << 18);
-  if (d.n_ties == 0 && cells > small_launch) return false;
   SmallArgs a;
   a.n_off = 0;
   a.tie_mask = 0;
@@ -439,77 +431,54 @@ bool normals_small(const Geo& g, const ChainParams& p, const Layers& L, bool kee
     const int hw = d.hw[dj < 0 ? -dj : dj];
     for (int di = -hw; di <= hw; ++di) {
       if (di == 0 && dj == 0) continue;
-      if (a.n_off >= kSmallMaxOffsets) return false;
+      if (a.n_off >= kSmallMaxOffsets) return hipErrorInvalidValue;
       a.di[a.n_off] = (signed char)di;
       a.dj[a.n_off] = (signed char)dj;
       ++a.n_off;
     }
   }
   for (int t = 0; t < d.n_ties; ++t) {
-    if (a.n_off >= kSmallMaxOffsets) return false;
+    if (a.n_off >= kSmallMaxOffsets) return hipErrorInvalidValue;
     a.di[a.n_off] = d.tie_di[t];
     a.dj[a.n_off] = d.tie_dj[t];
     a.tie_mask |= 1u << a.n_off;
     ++a.n_off;
   }
-  if (a.n_off < 2) return false;  // fewer than three points in every disc: UnitZ everywhere, the generic kernel's business
   for (int k = a.n_off; k < kSmallMaxOffsets; ++k) a.di[k] = a.dj[k] = 0;
   fill_common(a, g, p, L, r);
   a.write_step = write_step ? 1 : 0;
   a.combine = combine ? 1 : 0;
-  fg->ntx = (r.i1 - r.i0 + kLanes - 1) / kLanes;
-  fg->nty = (r.j1 - r.j0 + 15) / 16;
-  fg->nbz = r.map >= 0 ? 1 : g.batch;
-  fg->frame = -1;  // nothing is left to the fix-up pass: the caller does not launch it
-  const dim3 grid((unsigned)fg->ntx, (unsigned)((r.j1 - r.j0 + kSmallBY - 1) / kSmallBY), (unsigned)fg->nbz);
-  // the one-cell tie radius: the four edge neighbours, every one of them on the circle (any order in the table)
-  bool cross = a.n_off == 4 && a.tie_mask == 0xfu;
-  for (int k = 0; k < 4 && cross; ++k) cross = (a.di[k] == 0) != (a.dj[k] == 0) && a.di[k] * a.di[k] + a.dj[k] * a.dj[k] == 1;
-  for (int k = 0; k < 4 && cross; ++k)
-    for (int q = 0; q < k; ++q) cross = cross && !(a.di[k] == a.di[q] && a.dj[k] == a.dj[q]);
+  const dim3 grid((unsigned)((r.i1 - r.i0 + kLanes - 1) / kLanes), (unsigned)((r.j1 - r.j0 + kSmallBY - 1) / kSmallBY),
+                  (unsigned)(r.map >= 0 ? 1 : g.batch));
+  // (CROSS: the four edge neighbours, every one of them on the circle, in any order in the table)
   if (cross) {
     if (keep_normals)
       hipLaunchKernelGGL((k_normals_small<true, true>), grid, dim3(kLanes, kSmallBY), 0, s, a);
     else
       hipLaunchKernelGGL((k_normals_small<false, true>), grid, dim3(kLanes, kSmallBY), 0, s, a);
-    return true;
-  }
-  if (keep_normals)
+  } else if (keep_normals) {
     hipLaunchKernelGGL((k_normals_small<true, false>), grid, dim3(kLanes, kSmallBY), 0, s, a);
-  else
+  } else {
     hipLaunchKernelGGL((k_normals_small<false, false>), grid, dim3(kLanes, kSmallBY), 0, s, a);
-  return true;
+  }
+  return hipSuccess;
 }
 
-// The whole chain of a small whole-map launch in one kernel (k_chain_window); false: not taken.  Conditions: at most 2^18
-// cells, a normals disc that reaches at most two cells (tie cells included), both step windows tie-free and at most 3 x 3.
-bool chain_window(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, const Region& r, bool combine, hipStream_t s) {
-  static const bool off = lab_flag("TE_NO_CHAIN_WINDOW");  // measurement aid
+// The whole chain of a small whole-map launch in one kernel (k_chain_window): at most 2^18 cells, a normals disc that
+// reaches at most two cells (tie cells included), both step windows tie-free and at most 3 x 3 -- the plan's conditions.
+hipError_t chain_window(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, const Region& r, bool combine, hipStream_t s) {
   const Disc& d = p.normals;
-  if (off || d.any || p.rough.any || p.step1.any || p.step2.any) return false;  // (te_filter_any.hip)
-  if (off || d.reach < 1 || d.reach > 2 || p.step1.n_ties != 0 || p.step2.n_ties != 0 || p.step1.Q < 0 || p.step1.Q > 2 || p.step2.Q < 0 || p.step2.Q > 2) return false;
-  const long long cells = (long long)(r.i1 - r.i0) * (r.j1 - r.j0) * (r.map >= 0 ? 1 : g.batch);
-  if (cells > (1ll << 18) || (double)g.rows * (double)g.cols * 4.0 >= 4294967296.0) return false;
   SmallArgs a;
   a.n_off = 0;
   a.tie_mask = 0;
   for (int k = 0; k < kSmallMaxOffsets; ++k) a.di[k] = a.dj[k] = 0;
   fill_common(a, g, p, L, r);
-  int points = 1;
   for (int dj = -d.R; dj <= d.R; ++dj) {
     const int hw = d.hw[dj < 0 ? -dj : dj];
     for (int di = -hw; di <= hw; ++di)
-      if (di || dj) {
-        a.disc25 |= 1u << ((dj + 2) * 5 + (di + 2));
-        ++points;
-      }
+      if (di || dj) a.disc25 |= 1u << ((dj + 2) * 5 + (di + 2));
   }
-  for (int t = 0; t < d.n_ties; ++t) {
-    if (d.tie_di[t] == 0 && d.tie_dj[t] == 0) return false;
-    a.tie25 |= 1u << ((d.tie_dj[t] + 2) * 5 + (d.tie_di[t] + 2));
-    ++points;
-  }
-  if (points < 3) return false;  // UnitZ everywhere: the generic kernel's business
+  for (int t = 0; t < d.n_ties; ++t) a.tie25 |= 1u << ((d.tie_dj[t] + 2) * 5 + (d.tie_di[t] + 2));
   auto window = [](int Q) {
     unsigned m = 0;
     for (int dj = -1; dj <= 1; ++dj)
@@ -529,7 +498,7 @@ bool chain_window(const Geo& g, const ChainParams& p, const Layers& L, bool keep
     hipLaunchKernelGGL(k_chain_window<true>, grid, dim3(kLanes, kSmallBY), 0, s, a);
   else
     hipLaunchKernelGGL(k_chain_window<false>, grid, dim3(kLanes, kSmallBY), 0, s, a);
-  return true;
+  return hipSuccess;
 }
 
 }  // namespace fast

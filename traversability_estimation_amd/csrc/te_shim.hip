@@ -545,6 +545,8 @@ int rebuild_tables(te_ctx* c) {
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
   c->L.clip_table = c->cmem.clip_table.as<int>();
+  HIP_TRY(hipSetDevice(c->device));
+  chain_route_template(c->geo, c->cp);  // (what plan_chain_route asks of the discs and the map: once, not per launch)
 
   c->tables_ready = true;
   rebuild_footprint_tables(c);
@@ -602,6 +604,16 @@ int ensure_input_layer(te_ctx* c, int layer) {
   return TE_OK;
 }
 
+// The launch wrappers of the filters return hipErrorInvalidValue for a planned route without its instantiation
+// (te_chain_route.h): an internal routing error, not a failure of the runtime
+#define ROUTE_TRY(expr, what)                                                                              \
+  do {                                                                                                     \
+    if ((expr) == hipErrorInvalidValue) {                                                                  \
+      (void)hipGetLastError();                                                                             \
+      return fail(TE_ERR_UNSUPPORTED, "%s: the planned kernel route has no instantiation: internal routing error", what); \
+    }                                                                                                      \
+  } while (0)
+
 int run_chain_locked(te_ctx* c, unsigned flags, const Region& r) {
   if (!c->have_params || !c->have_geo) return fail(TE_ERR_NOT_READY, "te_run_chain: set params and geometry first");
   if (!c->tables_ready) {
@@ -631,7 +643,9 @@ int run_chain_locked(te_ctx* c, unsigned flags, const Region& r) {
   c->L.fb_blocks_per_cu = c->opt_fb_blocks_per_cu;
   set_launch_hints(c);  // (run_whole_locked allocates their buffers before it captures)
   if (c->opt_rank_rule) flags |= TE_RUN_GENERIC_KERNELS;  // (the rule lives in the generic normals kernel only)
-  HIP_TRY(launch_chain(c->geo, c->cp, c->L, r, flags, c->stream));
+  const hipError_t e = launch_chain(c->geo, c->cp, c->L, r, flags, c->stream);
+  ROUTE_TRY(e, "te_run_chain");
+  HIP_TRY(e);
   c->st.chain_launched(whole, flags);
   return TE_OK;
 }
@@ -1079,7 +1093,9 @@ int te_run_filter(te_ctx* c, int filter, unsigned flags) {
   HIP_TRY(hipSetDevice(c->device));
   set_launch_hints(c);  // (as in the chain: never stale ones)
   if (c->opt_rank_rule) flags |= TE_RUN_GENERIC_KERNELS;
-  HIP_TRY(launch_filter(c->geo, c->cp, c->L, filter, flags, c->stream));
+  const hipError_t e = launch_filter(c->geo, c->cp, c->L, filter, flags, c->stream);
+  ROUTE_TRY(e, "te_run_filter");
+  HIP_TRY(e);
   c->st.filter_ran(filter);
   return TE_OK;
 }

@@ -524,157 +524,63 @@ void launch_r(const Geo& g, SlideArgs a, const Layers& L, bool keep, const Regio
 
 }  // namespace
 
-// Normals + slope + roughness for a tie-free disc (same disc for normals and roughness, positive axis
-// z, at least 3 cells).  Returns false if the shape is not supported by this kernel.
-bool normals_fast(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, bool combine,
-                  const Region& r, int* flags, const int* gtab, FastGrid* fg, hipStream_t s, bool* combined) {
-  const Disc& d = p.normals;
-  if (d.any || p.rough.any) return false;  // (te_filter_any.hip)
-  if (normals_small(g, p, L, keep_normals, r, flags, fg, s)) {  // discs of at most 13 cells: one cell per thread
-    *combined = false;
-    return true;
-  }
-  if (d.n_ties != 0) {  // a tie radius: k_normals3's TIES march or nothing
-    static const bool no_n3_ties = lab_flag("TE_NO_N3");
-    if (no_n3_ties || !gtab || g.rows < 2 * d.reach + 1 || g.cols < 2 * d.reach + 1) return false;
-    fg->ntx = (r.i1 - r.i0 + kLanes - 1) / kLanes;
-    fg->nty = (r.j1 - r.j0 + 15) / 16;
-    fg->nbz = r.map >= 0 ? 1 : g.batch;
-    fg->frame = 0;
-    if (!normals_fast3(g, p, L, keep_normals, r, flags, fg, s)) return false;
-    *combined = false;
-    return true;
-  }
-  if (d.R < 1 || d.R > 16 || d.npoints < 3) return false;
+// k_normals_slide on region r for the tie-free disc d, the route plan_chain_route (te_chain_route.h) named: the shape form
+// (shape_form: Shape<d.Q>, a compile-time run table) or the radius form <d.R, -1>.  given: RoughnessFilter alone with the
+// normals of the layers (SlideArgs::given; the normals are read, not kept).  The fix-up pass behind it is the caller's.
+hipError_t normals_slide(const Geo& g, const ChainParams& p, const Layers& L, const Disc& d, int sii, bool shape_form, bool given,
+                         bool keep_normals, bool combine, const Region& r, int* flags, hipStream_t s) {
+  const FastGrid fg = fast_grid(g, r);
   SlideArgs a;
-  int sii = 0;
   for (int k = 0; k <= kMaxRadiusCells; ++k) {
     a.h[k] = k <= d.R ? d.hw[k] : -1;
     a.hd[k] = (double)a.h[k];
   }
-  for (int dj = -d.R; dj <= d.R; ++dj) {
-    const int hw = d.hw[dj < 0 ? -dj : dj];
-    for (int di = -hw; di <= hw; ++di) sii += di * di;
-  }
   a.np = d.npoints;
   a.sii = sii;
-  fg->ntx = (r.i1 - r.i0 + kLanes - 1) / kLanes;
-  fg->nty = (r.j1 - r.j0 + 15) / 16;
-  fg->nbz = r.map >= 0 ? 1 : g.batch;
   a.fi0 = r.i0;
   a.fj0 = r.j0;
-  a.ntx = fg->ntx;
-  a.nty = fg->nty;
-  a.fix_groups = fix_groups(fg->ntx * fg->nty * fg->nbz);
+  a.ntx = fg.ntx;
+  a.nty = fg.nty;
+  a.fix_groups = fix_groups(fg.ntx * fg.nty * fg.nbz);
   a.slope_crit = p.slope_crit;
   a.inv_slope_crit = 1.0 / p.slope_crit;
   a.rough_crit = p.rough_crit;
   a.inv_rough_crit = 1.0 / p.rough_crit;
   a.band_slope = clip_band_slope(p.slope_crit);
   a.band_rough = clip_band_rough(p.rough_crit);
-  a.w_scale = p.w_scale;
-  a.w_slope = p.w_slope;
-  a.w_step = p.w_step;
-  a.w_rough = p.w_rough;
+  a.w_scale = given ? 0.0f : p.w_scale;
+  a.w_slope = given ? 0.0f : p.w_slope;
+  a.w_step = given ? 0.0f : p.w_step;
+  a.w_rough = given ? 0.0f : p.w_rough;
   a.combine = combine ? 1 : 0;
-  a.given = 0;
-  a.gtab = gtab;
-  if (g.rows < 2 * d.R + 1 || g.cols < 2 * d.R + 1 || !gtab) return false;  // both borders inside one disc
-  // cells whose disc lies inside the map: k_normals3 (3 waves per SIMD); this file keeps the frame
-  static const bool no_n3 = lab_flag("TE_NO_N3");
-  fg->frame = 0;
-  if (!no_n3 && normals_fast3(g, p, L, keep_normals, r, flags, fg, s)) {
-    *combined = false;  // k_normals3 does not combine: the caller runs k_combine (or the footprint mask kernel does)
-    return true;        // the frame and whatever that kernel flagged belong to the fix-up pass
-  }
-  *combined = combine;
-  if (d.Q >= 1) {  // instantiated shape: compile-time run table
+  a.given = given ? 1 : 0;
+  a.gtab = given ? nullptr : L.clip_table;
+  const bool keep = given || keep_normals;  // (given: the kernel's normal pointers are its inputs)
+  if (shape_form) {
     switch (d.Q) {
-#define X(q)                                                              \
-  case q:                                                                 \
-    if constexpr (q >= 1) {                                               \
-      launch_r<Shape<q>::R, q>(g, a, L, keep_normals, r, flags, s);       \
-      return true;                                                        \
-    }                                                                     \
+#define X(q)                                                  \
+  case q:                                                     \
+    if constexpr (q >= 1) {                                   \
+      launch_r<Shape<q>::R, q>(g, a, L, keep, r, flags, s);   \
+      return hipSuccess;                                      \
+    }                                                         \
     break;
       TE_DISC_SHAPES(X)
 #undef X
       default:
         break;
     }
+    return hipErrorInvalidValue;  // a planned shape without its instantiation
   }
   switch (d.R) {
 #define X(q) \
   case q:    \
-    launch_r<q, -1>(g, a, L, keep_normals, r, flags, s); \
-    return true;
+    launch_r<q, -1>(g, a, L, keep, r, flags, s); \
+    return hipSuccess;
     X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
 #undef X
     default:
-      return false;
-  }
-}
-
-// RoughnessFilter alone on the roughness disc with the normals of the layers (SlideArgs::given).  False: not taken.
-bool roughness_given_fast(const Geo& g, const ChainParams& p, const Layers& L, const Region& r, int* flags, FastGrid* fg, hipStream_t s) {
-  const Disc& d = p.rough;
-  if (d.any || d.n_ties != 0 || d.R < 1 || d.R > 16 || d.npoints < 3 || !flags) return false;
-  if (g.rows < 2 * d.R + 1 || g.cols < 2 * d.R + 1) return false;
-  SlideArgs a;
-  int sii = 0;
-  for (int k = 0; k <= kMaxRadiusCells; ++k) {
-    a.h[k] = k <= d.R ? d.hw[k] : -1;
-    a.hd[k] = (double)a.h[k];
-  }
-  for (int dj = -d.R; dj <= d.R; ++dj) {
-    const int hw = d.hw[dj < 0 ? -dj : dj];
-    for (int di = -hw; di <= hw; ++di) sii += di * di;
-  }
-  a.np = d.npoints;
-  a.sii = sii;
-  fg->ntx = (r.i1 - r.i0 + kLanes - 1) / kLanes;
-  fg->nty = (r.j1 - r.j0 + 15) / 16;
-  fg->nbz = r.map >= 0 ? 1 : g.batch;
-  fg->frame = 0;
-  a.fi0 = r.i0;
-  a.fj0 = r.j0;
-  a.ntx = fg->ntx;
-  a.nty = fg->nty;
-  a.fix_groups = fix_groups(fg->ntx * fg->nty * fg->nbz);
-  a.slope_crit = p.slope_crit;
-  a.inv_slope_crit = 1.0 / p.slope_crit;
-  a.rough_crit = p.rough_crit;
-  a.inv_rough_crit = 1.0 / p.rough_crit;
-  a.band_slope = clip_band_slope(p.slope_crit);
-  a.band_rough = clip_band_rough(p.rough_crit);
-  a.w_scale = a.w_slope = a.w_step = a.w_rough = 0.0f;
-  a.combine = 0;
-  a.given = 1;
-  a.gtab = nullptr;
-  if (d.Q >= 1) {  // instantiated shape: compile-time run table
-    switch (d.Q) {
-#define X(q)                                                      \
-  case q:                                                         \
-    if constexpr (q >= 1) {                                       \
-      launch_r<Shape<q>::R, q>(g, a, L, true, r, flags, s);       \
-      return true;                                                \
-    }                                                             \
-    break;
-      TE_DISC_SHAPES(X)
-#undef X
-      default:
-        break;
-    }
-  }
-  switch (d.R) {
-#define X(q) \
-  case q:    \
-    launch_r<q, -1>(g, a, L, true, r, flags, s); \
-    return true;
-    X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
-#undef X
-    default:
-      return false;
+      return hipErrorInvalidValue;
   }
 }
 

@@ -331,11 +331,8 @@ long wave_slots5(int waves) {
   return 4L * device_cus() * (ov > 0 ? ov : waves);
 }
 
-// the shapes a whole-cell radius of 3 .. 10 cells leaves without its circle (2 cells: k_step_small) (te_march.h has them all): only these exist as RAW kernels
-constexpr bool tie_free_part5(int Q) { return Q == 8 || Q == 13 || Q == 20 || Q == 34 || Q == 45 || Q == 61 || Q == 80 || Q == 98; }
-
 template <int Q>
-bool launch_step5(bool score, const Geo& g, Step5Args a, const Region& r, hipStream_t s) {
+hipError_t launch_step5(bool score, const Geo& g, Step5Args a, const Region& r, hipStream_t s) {
   const unsigned nx = (unsigned)((r.i1 - r.i0 + kLanes - 1) / kLanes), nz = (unsigned)(r.map >= 0 ? 1 : g.batch);
   a.rows = g.rows;
   a.cols = g.cols;
@@ -344,25 +341,24 @@ bool launch_step5(bool score, const Geo& g, Step5Args a, const Region& r, hipStr
   a.strip_rows = plan_strip_rows(r.j1 - r.j0, (long)nx * nz, wave_slots5(score ? kScore5Waves : kHeight5Waves));
   const dim3 grid(nx, (unsigned)((r.j1 - r.j0 + a.strip_rows - 1) / a.strip_rows), nz);
   constexpr int C = kStep5Queue;
-  if (a.out2) {
-    if constexpr (tie_free_part5(Q)) {
+  if (a.out2) {  // RAW: only the shapes of TE_STEP_RAW_SHAPES exist
+    if constexpr (step_raw_shape(Q)) {
       if (score)
         hipLaunchKernelGGL((k_step_score5<Q, true, C>), grid, dim3(kLanes), 0, s, a);
       else
         hipLaunchKernelGGL((k_step_height5<Q, true, C>), grid, dim3(kLanes), 0, s, a);
-      return true;
+      return hipSuccess;
     }
-    return false;
+    return hipErrorInvalidValue;
   }
   if (score)
     hipLaunchKernelGGL((k_step_score5<Q, false, C>), grid, dim3(kLanes), 0, s, a);
   else
     hipLaunchKernelGGL((k_step_height5<Q, false, C>), grid, dim3(kLanes), 0, s, a);
-  return true;
+  return hipSuccess;
 }
 
-bool dispatch_step5(int Q, bool score, const Geo& g, const Step5Args& a, const Region& r, hipStream_t s) {
-  if (r.i1 - r.i0 < kLanes || r.j1 <= r.j0) return false;  // the blocks are 64 cells wide and never mask a lane (the last one is shifted)
+hipError_t dispatch_step5(int Q, bool score, const Geo& g, const Step5Args& a, const Region& r, hipStream_t s) {
   switch (Q) {
 #define X(q) \
   case q:    \
@@ -370,15 +366,14 @@ bool dispatch_step5(int Q, bool score, const Geo& g, const Step5Args& a, const R
     TE_DISC_SHAPES(X)
 #undef X
     default:
-      return false;
+      return hipErrorInvalidValue;  // a planned march without its instantiation
   }
 }
 
 }  // namespace
 
-// sh_min != nullptr: RAW (the running maximum goes to sh, the minimum to sh_min); false: shape / region not taken
-bool step_height5(int Q, const Geo& g, const float* elev, float* sh, float* sh_min, const Region& r, hipStream_t s) {
-  if (!layer_has_guard_rows(elev, g, sizeof(float))) return false;  // (the march loads rows beyond the layer: te_internal.h)
+// sh_min != nullptr: RAW (the running maximum goes to sh, the minimum to sh_min)
+hipError_t step_height5(int Q, const Geo& g, const float* elev, float* sh, float* sh_min, const Region& r, hipStream_t s) {
   Step5Args a = {};
   a.in = elev;
   a.out = sh;
@@ -387,9 +382,8 @@ bool step_height5(int Q, const Geo& g, const float* elev, float* sh, float* sh_m
 }
 
 // out_count != nullptr: RAW (maximum to out, count to out_count)
-bool step_score5(int Q, const Geo& g, double crit, int ncrit, const float* sh, float* out, float* out_count, const Region& r,
-                 hipStream_t s) {
-  if (!layer_has_guard_rows(sh, g, sizeof(float))) return false;
+hipError_t step_score5(int Q, const Geo& g, double crit, int ncrit, const float* sh, float* out, float* out_count, const Region& r,
+                       hipStream_t s) {
   Step5Args a = {};
   a.in = sh;
   a.out = out;
