@@ -60,6 +60,9 @@
  *   te_run_radius_filter / te_radius_filter_stats
  *                        <- gridMapFilters/MeanInRadiusFilter and MinInRadiusFilter (grid_map_filters; restated, see below):
  *                           the radial blur between the fill and the normals, and the conservative lower surface
+ *   te_run_window_expression / te_window_expr_check / te_window_expression_stats
+ *                        <- gridMapFilters/SlidingWindowMathExpressionFilter (grid_map_filters; restated, see below): an
+ *                           EigenLab expression over a square window around every cell (local deviation, box mean, relief)
  *
  * Data contract (identical to grid_map::Matrix = Eigen::MatrixXf): float32, COLUMN-major,
  * element (row i, col j) of map m at ptr[m*rows*cols + j*rows + i]; invalid cell = non-finite.
@@ -215,6 +218,10 @@ int te_get_params(te_ctx* ctx, te_params* p);
  * result is provably exact (its segments fit in LDS; a workgroup of the Mean whose values fail the plan's predicate still runs
  * the in-order gather), 2 the in-order gather always.  The layers are identical under every value, bit for bit. */
 #define TE_OPT_RADIUS_ROUTE 11
+/* te_run_window_expression: 0 (default) the route the plan names (csrc/te_window_plan.h), 1 the separable route wherever it is
+ * allowed (no nested reduction, its column partials fit in LDS; a workgroup that `mean` padding gives a clipped window still
+ * walks directly), 2 the direct walk always.  The layers are identical under every value, bit for bit. */
+#define TE_OPT_WINDOW_EXPR_ROUTE 12
 int te_set_option(te_ctx* ctx, int option, int value);
 /* The face flags a footprint run would be given now (tests, diagnostics): batch x ceil(cols / 4) x ceil(rows / 64) bytes, the
  * flag of 64 cells along the rows fastest; `bytes` must be exactly that.  TE_ERR_NOT_READY while they are unknown or
@@ -859,6 +866,72 @@ int te_radius_filter_stats(te_ctx* ctx, uint64_t counts[2]);
 /* Measurement aid (tools/radius_filter_bench.py), like te_time_median_fill_samples: `iters` launches over the whole batch, one
  * HIP event pair each, after `warmup` untimed ones; in_layer != out_layer is required.  op = 0: a device copy of the layer. */
 int te_time_radius_filter_samples(te_ctx* ctx, int op, double radius, int in_layer, int out_layer, int warmup, int iters, float* ms);
+
+/* ---- gridMapFilters/SlidingWindowMathExpressionFilter on the device: an expression over a window around every cell ----
+ * Like the median fill and the radius filters this contract is RESTATED from memory of grid_map_filters and EigenLab; nothing
+ * the reference holds pins it.  The yardstick of the tests is the same contract in numpy (tests/ref_py/window_expression_ref.py).
+ *   1. parameters      input_layer, output_layer, expression; exactly one of window_size (int) and window_length (double,
+ *      metres); compute_empty_cells (default true); edge_handling in inside | crop | empty | mean (default inside).
+ *   2. window size     window_size is taken as given.  With window_length: w = (int)std::round(window_length / resolution) (a
+ *      double division, halves away from zero), then ++w if w is even.  w must be odd and at least 1 (upstream throws; here
+ *      TE_ERR_BAD_PARAM + message, also for a length that is negative or not finite).  Margin m = (w - 1) / 2.
+ *   3. the window of cell (i, j): rows [i - m, i + m], columns [j - m, j + m]; B is that rectangle clipped to the map.
+ *        inside   a cell whose rectangle is not wholly inside the map is not visited;
+ *        crop     the window W is B, smaller near the border;
+ *        empty    W is w x w, NaN outside the map;
+ *        mean     W is w x w; outside the map it holds the float32 meanOfFinites(B) by rule 5 (NaN if B has no finite value);
+ *        compute_empty_cells == false: a cell whose own input value is not finite is not visited.
+ *      A cell that is not visited gets NaN.  The whole output layer of the covered maps is written (upstream add()s it first).
+ *   4. the expression  the language of te_run_expression with three differences: (a) the only variable is the input layer,
+ *      written by its name, and it denotes W (any other layer name: TE_ERR_BAD_PARAM); (b) the result must be a scalar -- a
+ *      main expression that leaves a map, like abs(elevation), is refused when it is compiled (TE_ERR_BAD_PARAM; upstream logs
+ *      an error per cell and leaves NaN); (c) reductions nest ONE level: a reduction's argument may hold reductions whose own
+ *      arguments hold none (deeper: TE_ERR_BAD_PARAM).  At most 4 reductions and 64 instructions in all.  Scalar .* ./ ^ as
+ *      in te_run_expression; * between two maps stays TE_ERR_UNSUPPORTED.  A scalar argument of a reduction counts once per
+ *      cell of W, as it counts once per cell of the map there.
+ *   5. reductions over W, defined bit for bit: every column of W in ascending column order yields a partial -- a double sum
+ *      starting at 0.0 over the rows in ascending order (and minimum, maximum and count of the finite values); the column
+ *      partials are folded in ascending column order into an empty partial (sum += sum); the result is taken from that with
+ *      cells = rows(W) * cols(W).  sum and mean take every value (a NaN poisons them), the ...OfFinites kinds skip the
+ *      non-finite ones.  Eigen's own redux order depends on its vectorisation and is not restated.
+ *   6. the same layer in and out behaves as if the input had been copied first. */
+#define TE_EDGE_INSIDE 0
+#define TE_EDGE_CROP 1
+#define TE_EDGE_EMPTY 2
+#define TE_EDGE_MEAN 3
+typedef struct te_window_expr_params {
+  uint32_t size; /* sizeof(te_window_expr_params) */
+  uint32_t abi_version;
+  int32_t window_size;       /* odd, >= 1; 0 with use_window_length */
+  int32_t use_window_length; /* 0: window_size, 1: window_length */
+  double window_length;      /* metres; 0 without use_window_length */
+  int32_t compute_empty_cells;
+  int32_t edge_handling; /* TE_EDGE_* */
+} te_window_expr_params;
+/* Defaults: window_size 3 (upstream has none: one of the two must be given), compute_empty_cells 1, TE_EDGE_INSIDE. */
+int te_window_expr_params_default(te_window_expr_params* p);
+/* TE_ERR_INVALID_ARG: NULL, size / abi mismatch.  TE_ERR_BAD_PARAM + message: an even window_size or one below 1, both or
+ * neither of window_size and window_length, a length that is negative or not finite, an edge_handling that is none of the four. */
+int te_window_expr_params_validate(const te_window_expr_params* p);
+/* Host only, no context: compiles `text` as a window expression over in_layer and describes it (`info` may be NULL).  Errors as
+ * te_expr_check, the message with the column. */
+int te_window_expr_check(const char* text, int in_layer, te_expr_info* info);
+/* out_layer = the expression over the window of every cell of in_layer, for maps [map0, map0 + nmaps) of the batch; the other
+ * maps are untouched.  Any two float layers of the context, any window.  Exact: identical run after run and between the
+ * routes (TE_OPT_WINDOW_EXPR_ROUTE): the direct walk is rule 5 literally, O(w^2) per cell; the separable route keeps the column
+ * partials of a tile in LDS and folds them per cell in rule 5's order, O(w) per cell.  The transcendental functions are the
+ * device's, as in te_run_expression.  Asynchronous on the context's stream unless out_layer is the elevation.
+ *   TE_ERR_NOT_READY, TE_ERR_INVALID_ARG, the context afterwards (the recount when the elevation is written included) and the
+ *   joining of a prefetch: as te_run_radius_filter.  TE_ERR_BAD_PARAM: the parameters, the window, the expression.
+ *   TE_ERR_UNSUPPORTED: valid EigenLab that is not built; the copy of the input layer does not fit in device memory. */
+int te_run_window_expression(te_ctx* ctx, const te_window_expr_params* p, const char* text, int in_layer, int out_layer, int map0, int nmaps);
+/* Which route the last te_run_window_expression took: counts[0] = workgroups the separable route settled, counts[1] =
+ * workgroups that walked their windows directly.  Waits for the call.  TE_ERR_NOT_READY before any call. */
+int te_window_expression_stats(te_ctx* ctx, uint64_t counts[2]);
+/* Measurement aid (tools/window_expression_bench.py), like te_time_radius_filter_samples: `iters` launches over the whole
+ * batch, one HIP event pair each, after `warmup` untimed ones; in_layer != out_layer is required.  p == NULL or text == NULL: a
+ * device copy of the layer. */
+int te_time_window_expression_samples(te_ctx* ctx, const te_window_expr_params* p, const char* text, int in_layer, int out_layer, int warmup, int iters, float* ms);
 
 const char* te_last_error(void);
 const char* te_version(void);

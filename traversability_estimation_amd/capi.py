@@ -33,6 +33,9 @@ OPT_FP_ANY_REACH = 7  # circular footprint: 0 routes by reach (above 20 cells: t
 OPT_FACE_FLAGS = 9  # mask kernel of the footprint pass: 1 (default) skips the step-check staging on tiles the upload found without a vertical face, 0 never (identical layers)
 OPT_MEDIAN_ROUTE = 10  # te_run_median_fill: 0 by plan, 1 the tile kernel wherever its window fits, 2 the general kernel always (identical layers)
 OPT_RADIUS_ROUTE = 11  # te_run_radius_filter: 0 by plan, 1 the sliding kernel wherever its result is provably exact, 2 the in-order gather always (identical layers)
+OPT_WINDOW_EXPR_ROUTE = 12  # te_run_window_expression: 0 by plan, 1 the separable route wherever allowed, 2 the direct walk always (identical layers)
+EDGE_INSIDE, EDGE_CROP, EDGE_EMPTY, EDGE_MEAN = 0, 1, 2, 3  # te_window_expr_params.edge_handling
+EDGE_HANDLING = {"inside": EDGE_INSIDE, "crop": EDGE_CROP, "empty": EDGE_EMPTY, "mean": EDGE_MEAN}
 RADIUS_MEAN, RADIUS_MIN = 1, 2  # te_run_radius_filter: gridMapFilters/MeanInRadiusFilter, MinInRadiusFilter
 OPT_FILTER_ANY_RADIUS = 8  # filter discs: 0 up to 32 cells (TE_ERR_UNSUPPORTED above), 1 any radius, 2 the route of any radius for every disc
 
@@ -55,7 +58,9 @@ SYMBOLS = ["te_params_default", "te_params_validate", "te_device_count", "te_cre
            "te_expr_check", "te_run_expression", "te_time_expression_samples",
            "te_median_fill_params_default", "te_median_fill_params_validate", "te_run_median_fill", "te_download_fill_mask",
            "te_time_median_fill_samples",
-           "te_run_radius_filter", "te_radius_filter_stats", "te_time_radius_filter_samples"]
+           "te_run_radius_filter", "te_radius_filter_stats", "te_time_radius_filter_samples",
+           "te_window_expr_params_default", "te_window_expr_params_validate", "te_window_expr_check", "te_run_window_expression",
+           "te_window_expression_stats", "te_time_window_expression_samples"]
 MSG_MAX_NAME = 64
 OCCUPANCY_MAX_LAYERS = CLOUD_MAX_LAYERS = SUBMAP_MAX_LAYERS = 16
 POINTFIELD_FLOAT32 = 7
@@ -153,6 +158,12 @@ class TeMedianFillParams(C.Structure):
     _fields_ = [("size", C.c_uint32), ("abi_version", C.c_uint32), ("fill_hole_radius", C.c_double),
                 ("filter_existing_values", C.c_int32), ("_pad0", C.c_int32), ("existing_value_radius", C.c_double),
                 ("num_erode_dilation_iterations", C.c_int32), ("_pad1", C.c_int32)]
+
+
+class TeWindowExprParams(C.Structure):
+    """te_window_expr_params: the settings of a gridMapFilters/SlidingWindowMathExpressionFilter entry."""
+    _fields_ = [("size", C.c_uint32), ("abi_version", C.c_uint32), ("window_size", C.c_int32), ("use_window_length", C.c_int32),
+                ("window_length", C.c_double), ("compute_empty_cells", C.c_int32), ("edge_handling", C.c_int32)]
 
 
 class TePathCheckStats(C.Structure):
@@ -288,6 +299,13 @@ def load():
         L.te_run_radius_filter.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int]
         L.te_radius_filter_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.te_time_radius_filter_samples.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        wp = C.POINTER(TeWindowExprParams)
+        L.te_window_expr_params_default.argtypes = [wp]
+        L.te_window_expr_params_validate.argtypes = [wp]
+        L.te_window_expr_check.argtypes = [C.c_char_p, C.c_int, C.POINTER(TeExprInfo)]
+        L.te_run_window_expression.argtypes = [vp, wp, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.te_window_expression_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.te_time_window_expression_samples.argtypes = [vp, wp, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.te_last_error.restype = C.c_char_p
         L.te_version.restype = C.c_char_p
         _lib = L
@@ -317,6 +335,22 @@ def default_median_fill_params(**over):
         if not hasattr(p, k):
             raise KeyError(k)
         setattr(p, k, v)
+    return p
+
+
+def window_expr_params(window_size=None, window_length=None, compute_empty_cells=True, edge_handling="inside"):
+    """te_window_expr_params from the keys of a SlidingWindowMathExpressionFilter entry: exactly one of window_size (cells) and
+    window_length (metres); edge_handling by name or as EDGE_*.  Validated by the library."""
+    p = TeWindowExprParams()
+    _check(load().te_window_expr_params_default(C.byref(p)))
+    p.window_size = 0 if window_size is None else int(window_size)
+    p.use_window_length = 0 if window_length is None else 1
+    p.window_length = 0.0 if window_length is None else float(window_length)
+    if window_size is not None and window_length is not None:
+        p.window_length = float(window_length)  # (both given: the library refuses the pair)
+    p.compute_empty_cells = 1 if compute_empty_cells else 0
+    p.edge_handling = EDGE_HANDLING[edge_handling] if isinstance(edge_handling, str) else int(edge_handling)
+    _check(load().te_window_expr_params_validate(C.byref(p)))
     return p
 
 
@@ -542,6 +576,16 @@ def expr_check(text):
             "n_reductions": int(info.n_reductions), "stack_depth": int(info.stack_depth)}
 
 
+def window_expr_check(text, in_layer="elevation"):
+    """te_window_expr_check: compiles a SlidingWindowMathExpressionFilter expression over `in_layer` on the host (no device, no
+    context).  Returns what expr_check returns; raises TeError with the library's message (it names the column) and class."""
+    info = TeExprInfo()
+    lid = LAYERS[in_layer] if isinstance(in_layer, str) else int(in_layer)
+    _check(load().te_window_expr_check(str(text).encode(), lid, C.byref(info)))
+    return {"n_instructions": int(info.n_instructions), "layers": [k for k, v in LAYERS.items() if info.layer_mask >> v & 1],
+            "n_reductions": int(info.n_reductions), "stack_depth": int(info.stack_depth)}
+
+
 def device_count():
     n = C.c_int(0)
     rc = load().te_device_count(C.byref(n))
@@ -735,6 +779,29 @@ class Context:
         """Device time of each of `iters` radius filters (op 0: device copies of the layer), in ms."""
         ms = (C.c_float * int(iters))()
         _check(load().te_time_radius_filter_samples(self._h, int(op), float(radius), LAYERS[in_layer], LAYERS[out_layer], int(warmup), int(iters), ms))
+        return np.array(ms[:], dtype=np.float64)
+
+    def run_window_expression(self, text, params, in_layer="elevation", out_layer=None, map0=0, nmaps=None):
+        """gridMapFilters/SlidingWindowMathExpressionFilter on the device (te_run_window_expression): `out_layer` (default:
+        `in_layer`, in place) = `text` over the window of every cell of `in_layer`.  params: window_expr_params(...), or a dict of
+        its arguments."""
+        p = window_expr_params(**params) if isinstance(params, dict) else params
+        lid = lambda name: LAYERS[name] if isinstance(name, str) else int(name)
+        nmaps = self.batch - map0 if nmaps is None else nmaps
+        _check(load().te_run_window_expression(self._h, C.byref(p), str(text).encode(), lid(in_layer),
+                                               lid(in_layer if out_layer is None else out_layer), int(map0), int(nmaps)))
+
+    def window_expression_stats(self):
+        """(workgroups the separable route settled, workgroups that walked directly) of the last run_window_expression."""
+        counts = (C.c_uint64 * 2)()
+        _check(load().te_window_expression_stats(self._h, counts))
+        return int(counts[0]), int(counts[1])
+
+    def time_window_expression_samples(self, text, params, in_layer="elevation", out_layer="traversability_roughness", warmup=3, iters=50):
+        """Device time of each of `iters` window expressions (text=None: device copies of the layer), in ms."""
+        ms = (C.c_float * int(iters))()
+        _check(load().te_time_window_expression_samples(self._h, None if text is None else C.byref(params), None if text is None else str(text).encode(),
+                                                        LAYERS[in_layer], LAYERS[out_layer], int(warmup), int(iters), ms))
         return np.array(ms[:], dtype=np.float64)
 
     def time_expression_samples(self, text, warmup=3, iters=50):

@@ -96,6 +96,8 @@ struct te_ctx {
     te::DevBuf median_mask, median_tmp, median_copy, median_any;
     // te_run_radius_filter (te_radius.hip): the copy of the input layer a call with in_layer == out_layer reads
     te::DevBuf radius_copy;
+    // te_run_window_expression (te_window_expr.hip): the copy of the input layer a call with in_layer == out_layer reads
+    te::DevBuf window_copy;
     // the circular footprint at any reach (te_footprint_any.hip): its tables and its prefix-sum scratch ([batch][cols][rows + 1]
     // doubles, then as many unsigned), allocated when the footprint tables are rebuilt for that route; c->fp.any_* point into them
     struct FpAny {
@@ -116,6 +118,7 @@ struct te_ctx {
     te::DevBuf tile_in[2], tile_out[2];  // the device staging of in_slot / out_slot; grown
     // te_run_radius_filter: the window table of the last call (device copy of radius_tab_host; grown) and its two block counts
     te::DevBuf radius_tab, radius_counts;
+    te::DevBuf window_counts;  // te_run_window_expression: its two block counts
   } cmem;
   float* poly_rot = nullptr;  // (derived: lmem.poly)
   bool check_inclination = false;  // footprint/check_robot_inclination (:114)
@@ -145,6 +148,9 @@ struct te_ctx {
   double radius_tab_radius = -1.0, radius_tab_res = 0.0;
   te::DiscTable radius_disc;
   bool radius_counts_valid = false;
+  // TE_OPT_WINDOW_EXPR_ROUTE (te_window_plan.h); whether a te_run_window_expression has left block counts
+  int opt_window_expr_route = 0;
+  bool window_counts_valid = false;
   // face flags (te_face_flags.h): the bytes live in the slab; what they describe: te::CtxState::face_crit
   uint8_t* face_flags = nullptr;
   int opt_face_flags = 1;  // TE_OPT_FACE_FLAGS

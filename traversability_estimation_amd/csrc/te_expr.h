@@ -12,6 +12,13 @@
 // cwiseMin(a, b) = (b < a) ? b : a and cwiseMax(a, b) = (a < b) ? b : a: std::min / std::max operand order.  NOT symmetric in
 // NaN -- a NaN in `a` is returned, a NaN in `b` is dropped.
 //
+//
+// Window mode (compile_window; te_run_window_expression, gridMapFilters/SlidingWindowMathExpressionFilter): the one variable is
+// the input layer and denotes the window W around a cell, the result must be a scalar, and reductions nest one level.  A
+// reduction whose argument holds reductions is an OUTER one (red_level 1): its argument reads the results of the INNER ones
+// (red_level 0) with kPushRed, so the inner ones are folded first.  The folds over W (window_column, window_reduce) are
+// defined here once, for both routes of te_window_expr.hip and for the CPU check (tests/cpu/window_expr_check.cpp).
+//
 // Plain C++17, no HIP types: the parser is host code, the evaluator is marked TE_EXPR_HD.
 #pragma once
 #include <math.h>
@@ -59,6 +66,8 @@ struct Program {
   int32_t layer_id[kMaxLayers];  // te_layer ids
   uint8_t red_kind[kMaxRed];
   uint8_t red_begin[kMaxRed], red_end[kMaxRed];
+  uint8_t red_level[kMaxRed];  // window mode: 0 inner (no reduction in its argument), 1 outer; compile() leaves 0
+  int32_t n_outer;             // reductions of level 1
 };
 
 // ---- the evaluator ---------------------------------------------------------------------------------------------------
@@ -200,6 +209,53 @@ TE_EXPR_HD float partial_result(const Partial& q, int kind, uint64_t cells) {
   }
 }
 
+// ---- the folds over a window (rule 5 of the window contract, include/travgpu.h) -------------------------------------------
+// `at(row, col)` is the value of W at map coordinates (the padding where W reaches beyond the map); `res.get(k)` is the
+// result of reduction k for this cell (an outer argument and the main code read them); `st` as in run().
+
+template <class Res>
+struct WindowSource {
+  float x;
+  const Res* res;
+  TE_EXPR_HD Vec<1> layer(int) const { return Vec<1>{{x}}; }
+  TE_EXPR_HD Vec<1> red(int k) const { return Vec<1>{{res->get(k)}}; }
+};
+
+// the Partial of reduction r over one column of W: rows row_lo .. row_hi in ascending order, the sum starting at 0.0
+template <class Stack, class Res, class At>
+TE_EXPR_HD Partial window_column(const Program& p, int r, Stack& st, const Res& res, const At& at, int col, int row_lo, int row_hi) {
+  Partial q = partial_empty();
+  const int kind = p.red_kind[r], begin = p.red_begin[r], end = p.red_end[r];
+  for (int row = row_lo; row <= row_hi; ++row) {
+    const WindowSource<Res> src{at(row, col), &res};
+    partial_add(q, kind, run<1>(p, begin, end, st, src).v[0]);
+  }
+  return q;
+}
+
+// reduction r over W = rows [row_lo, row_hi] x columns [col_lo, col_hi]: the column partials folded in ascending column order
+template <class Stack, class Res, class At>
+TE_EXPR_HD float window_reduce(const Program& p, int r, Stack& st, const Res& res, const At& at, int row_lo, int row_hi, int col_lo, int col_hi) {
+  Partial acc = partial_empty();
+  for (int col = col_lo; col <= col_hi; ++col) {
+    const Partial q = window_column(p, r, st, res, at, col, row_lo, row_hi);
+    partial_merge(acc, q);
+  }
+  return partial_result(acc, p.red_kind[r], (uint64_t)(row_hi - row_lo + 1) * (uint64_t)(col_hi - col_lo + 1));
+}
+
+// float32 meanOfFinites of the raw values of a rectangle by the same rule (the padding of edge handling `mean`)
+template <class At>
+TE_EXPR_HD float window_mean_of_finites(const At& at, int row_lo, int row_hi, int col_lo, int col_hi) {
+  Partial acc = partial_empty();
+  for (int col = col_lo; col <= col_hi; ++col) {
+    Partial q = partial_empty();
+    for (int row = row_lo; row <= row_hi; ++row) partial_add(q, kMeanFinite, at(row, col));
+    partial_merge(acc, q);
+  }
+  return partial_result(acc, kMeanFinite, 0);
+}
+
 // ---- the compiler (host code) ----------------------------------------------------------------------------------------
 struct LayerName {
   const char* name;
@@ -217,8 +273,11 @@ inline const LayerName* layer_names(int* n) {
 class Compiler {
  public:
   // kOk, kBadParam or kUnsupported; on failure `err` (may be NULL) holds the message with the column
-  static int compile(const char* text, Program* out, char* err, size_t err_len) {
+  // window_layer >= 0: window mode with that te_layer as the one variable
+  static int compile(const char* text, Program* out, char* err, size_t err_len, int window_layer = -1) {
     Compiler c(text, err, err_len);
+    c.window_ = window_layer >= 0;
+    c.win_layer_ = window_layer;
     memset(out, 0, sizeof(*out));
     if (!text) return c.fail(kBadParam, 0, "no expression");
     c.skip();
@@ -236,11 +295,14 @@ class Compiler {
       if (ch == ',') return c.fail(kBadParam, c.pos_, "unexpected ','");
       return c.fail(kBadParam, c.pos_, "unexpected character");
     }
-    // main code first, the reduction arguments behind it
+    if (c.window_ && n.map)
+      return c.fail(kBadParam, 0, "the result of a window expression must be a scalar: reduce the window, as in meanOfFinites(...)");
+    // main code first, the reduction arguments behind it (window mode: the arguments of nested reductions last)
     Program& p = *out;
-    if (c.n_main_ + c.n_arg_ > kMaxCode) return c.fail(kBadParam, c.pos_, "more than 64 instructions");
-    for (int k = 0; k < c.n_main_ + c.n_arg_; ++k) {
-      const Ins& i = k < c.n_main_ ? c.main_[k] : c.argc_[k - c.n_main_];
+    const int n_all = c.n_main_ + c.n_arg_ + c.n_arg2_;
+    if (n_all > kMaxCode) return c.fail(kBadParam, c.pos_, "more than 64 instructions");
+    for (int k = 0; k < n_all; ++k) {
+      const Ins& i = k < c.n_main_ ? c.main_[k] : k < c.n_main_ + c.n_arg_ ? c.argc_[k - c.n_main_] : c.arg2_[k - c.n_main_ - c.n_arg_];
       p.op[k] = i.op;
       p.arg[k] = i.arg;
       if (i.op == kPushConst) {
@@ -251,15 +313,18 @@ class Compiler {
       }
     }
     p.n_main = c.n_main_;
-    p.n_code = c.n_main_ + c.n_arg_;
+    p.n_code = n_all;
     p.n_layers = c.n_layers_;
     p.n_red = c.n_red_;
     p.stack_depth = c.max_depth_;
     for (int k = 0; k < kMaxLayers; ++k) p.layer_id[k] = k < c.n_layers_ ? c.layer_id_[k] : -1;
     for (int k = 0; k < c.n_red_; ++k) {
       p.red_kind[k] = c.red_kind_[k];
-      p.red_begin[k] = (uint8_t)(c.n_main_ + c.red_begin_[k]);
-      p.red_end[k] = (uint8_t)(c.n_main_ + c.red_end_[k]);
+      const int base = c.n_main_ + (c.red_stream_[k] == 2 ? c.n_arg_ : 0);
+      p.red_begin[k] = (uint8_t)(base + c.red_begin_[k]);
+      p.red_end[k] = (uint8_t)(base + c.red_end_[k]);
+      p.red_level[k] = c.red_level_[k];
+      p.n_outer += c.red_level_[k];
     }
     return kOk;
   }
@@ -285,15 +350,19 @@ class Compiler {
   char* err_;
   size_t err_len_;
   int rc_ = kOk;
-  Ins main_[kMaxCode + 1], argc_[kMaxCode + 1];
-  int n_main_ = 0, n_arg_ = 0;
-  bool in_red_ = false;  // emitting a reduction's argument
-  int depth_ = 0, max_depth_ = 0, saved_depth_ = 0;
+  Ins main_[kMaxCode + 1], argc_[kMaxCode + 1], arg2_[kMaxCode + 1];
+  int n_main_ = 0, n_arg_ = 0, n_arg2_ = 0;
+  bool window_ = false;  // window mode
+  int win_layer_ = -1;
+  int red_depth_ = 0;  // reductions around the code being emitted: 0 the main code, 1 a reduction's argument, 2 a nested one's
+  int depth_ = 0, max_depth_ = 0;
   int layer_id_[kMaxLayers] = {};
   int n_layers_ = 0;
   int n_red_ = 0;
   uint8_t red_kind_[kMaxRed] = {};
   int red_begin_[kMaxRed] = {}, red_end_[kMaxRed] = {};
+  int red_stream_[kMaxRed] = {};       // 1: argc_, 2: arg2_
+  uint8_t red_level_[kMaxRed] = {};
 
   bool at_end() const { return pos_ >= len_; }
   void skip() {
@@ -309,12 +378,12 @@ class Compiler {
     return false;
   }
 
-  Ins* stream() { return in_red_ ? argc_ : main_; }
-  int& count() { return in_red_ ? n_arg_ : n_main_; }
+  Ins* stream() { return red_depth_ == 0 ? main_ : red_depth_ == 1 ? argc_ : arg2_; }
+  int& count() { return red_depth_ == 0 ? n_main_ : red_depth_ == 1 ? n_arg_ : n_arg2_; }
 
   // pushes grow the stack by one, binary operators shrink it by one
   bool emit(uint8_t op, uint8_t arg, size_t col) {
-    if (n_main_ + n_arg_ >= kMaxCode) return failb(kBadParam, col, "more than 64 instructions");
+    if (n_main_ + n_arg_ + n_arg2_ >= kMaxCode) return failb(kBadParam, col, "more than 64 instructions");
     if (op <= kPushRed) {
       if (++depth_ > kMaxStack) return failb(kBadParam, col, "the operand stack would be deeper than 8: regroup the expression");
       if (depth_ > max_depth_) max_depth_ = depth_;
@@ -549,6 +618,8 @@ class Compiler {
     for (int k = 0; k < n_names; ++k)
       if (strlen(names[k].name) == n && memcmp(names[k].name, s_ + start, n) == 0) {
         if (call) return failb(kUnsupported, pos_, "indexing into a layer is not built");
+        if (window_ && names[k].id != win_layer_)
+          return failb(kBadParam, start, "a window expression has one variable: the input layer, written by its name");
         int slot = 0;
         while (slot < n_layers_ && layer_id_[slot] != names[k].id) ++slot;
         if (slot == n_layers_) {
@@ -566,20 +637,23 @@ class Compiler {
     const size_t open = pos_;
     ++pos_;
     if (f->kind == 2) {
-      if (in_red_) return failb(kBadParam, start, "reductions do not nest");
+      if (!window_ && red_depth_ > 0) return failb(kBadParam, start, "reductions do not nest");
+      if (red_depth_ > 1) return failb(kBadParam, start, "reductions nest one level at most");
       if (n_red_ >= kMaxRed) return failb(kBadParam, start, "more than 4 reductions");
       const int r = n_red_++;
       red_kind_[r] = f->code;
-      red_begin_[r] = n_arg_;
-      in_red_ = true;
-      saved_depth_ = depth_;
+      ++red_depth_;
+      red_stream_[r] = red_depth_;
+      red_begin_[r] = count();
+      const int saved_depth = depth_;
       depth_ = 0;
       Node a;
       const bool ok = parse_expr(nest + 1, &a) && close_call(open, 1);
-      in_red_ = false;
-      depth_ = saved_depth_;
+      if (ok) red_end_[r] = count();
+      --red_depth_;
+      depth_ = saved_depth;
       if (!ok) return false;
-      red_end_[r] = n_arg_;
+      red_level_[r] = n_red_ > r + 1 ? 1 : 0;  // (the reductions numbered behind r so far are those of its argument)
       out->map = false;
       out->konst = false;
       return emit(kPushRed, (uint8_t)r, start);
@@ -610,6 +684,19 @@ class Compiler {
 };
 
 inline int compile(const char* text, Program* out, char* err, size_t err_len) { return Compiler::compile(text, out, err, err_len); }
+
+// window mode: `in_layer` (a te_layer id) is the one variable and denotes the window; the result must be a scalar;
+// reductions nest one level
+inline int compile_window(const char* text, int in_layer, Program* out, char* err, size_t err_len) {
+  int n = 0;
+  layer_names(&n);
+  if (in_layer < 0 || in_layer >= n) {
+    memset(out, 0, sizeof(*out));
+    if (err && err_len) snprintf(err, err_len, "expression: bad input layer %d", in_layer);
+    return kBadParam;
+  }
+  return Compiler::compile(text, out, err, err_len, in_layer);
+}
 
 inline uint32_t layer_mask(const Program& p) {
   uint32_t m = 0;

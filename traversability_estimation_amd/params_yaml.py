@@ -260,6 +260,59 @@ def median_fill_from_yaml(path_or_dict, resolution=None):
     return out
 
 
+WINDOW_EXPRESSION_TYPE = "gridMapFilters/SlidingWindowMathExpressionFilter"
+_WINDOW_EXPRESSION_KEYS = {"input_layer", "output_layer", "expression", "window_size", "window_length", "compute_empty_cells", "edge_handling"}
+_EDGE_HANDLING = ("inside", "crop", "empty", "mean")
+
+
+def window_expression_from_yaml(path_or_dict):
+    """The `gridMapFilters/SlidingWindowMathExpressionFilter` entries of every filter list of the document, in the order of the
+    file: a list of dicts {"expression", "input_layer", "output_layer", "params": {"window_size" | "window_length",
+    "compute_empty_cells", "edge_handling"}} -- "params" holds the arguments of capi.window_expr_params, the rest those of
+    capi.Context.run_window_expression -- empty when the file has none.  An entry that cannot be honoured is refused whole: a key
+    the filter does not have, a missing layer or expression, both or neither of window_size and window_length, an even or
+    non-positive window_size, a length that is negative or not finite, an edge_handling that is none of the four (the
+    contract: include/travgpu.h).  The expression itself is checked by capi.window_expr_check, which needs the library."""
+    doc = path_or_dict if isinstance(path_or_dict, (dict, list)) else _load(path_or_dict)
+    lists = [doc] if isinstance(doc, list) else [v for v in (doc or {}).values() if isinstance(v, list)]
+    out = []
+    name = "SlidingWindowMathExpressionFilter"
+    for f in (f for lst in lists for f in lst if isinstance(f, dict) and str(f.get("type")) == WINDOW_EXPRESSION_TYPE):
+        prm = f.get("params") or {}
+        unknown = set(prm) - _WINDOW_EXPRESSION_KEYS
+        if unknown:
+            raise ParamsYamlError(f"{name}: unknown parameter(s) {sorted(unknown)}")
+        for k in ("input_layer", "output_layer", "expression"):
+            if k not in prm:
+                raise ParamsYamlError(f"{name} did not find param {k}")
+        if ("window_size" in prm) == ("window_length" in prm):
+            raise ParamsYamlError(f"{name}: exactly one of window_size and window_length")
+        params = {}
+        if "window_size" in prm:
+            w = prm["window_size"]
+            if isinstance(w, bool) or not isinstance(w, int) or w < 1 or w % 2 == 0:
+                raise ParamsYamlError(f"{name}: window_size must be an odd integer, at least 1 (got {w!r})")
+            params["window_size"] = w
+        else:
+            length = float(prm["window_length"])
+            if not (np.isfinite(length) and length >= 0.0):
+                raise ParamsYamlError(f"{name}: window_length must be finite and not negative (got {length})")
+            params["window_length"] = length
+        empty = prm.get("compute_empty_cells", True)
+        if not isinstance(empty, bool):
+            raise ParamsYamlError(f"{name}: compute_empty_cells must be true or false (got {empty!r})")
+        params["compute_empty_cells"] = empty
+        edge = str(prm.get("edge_handling", "inside"))
+        if edge not in _EDGE_HANDLING:
+            raise ParamsYamlError(f"{name}: edge_handling must be one of {', '.join(_EDGE_HANDLING)} (got {edge!r})")
+        params["edge_handling"] = edge
+        if not str(prm["expression"]).strip():
+            raise ParamsYamlError(f"{name}: the expression is empty")
+        out.append({"expression": str(prm["expression"]), "input_layer": str(prm["input_layer"]), "output_layer": str(prm["output_layer"]),
+                    "params": params})
+    return out
+
+
 RADIUS_FILTER_TYPES = {"gridMapFilters/MeanInRadiusFilter": "mean", "gridMapFilters/MinInRadiusFilter": "min"}
 _RADIUS_FILTER_KEYS = {"radius", "input_layer", "output_layer"}
 

@@ -16,8 +16,9 @@ EXPRESSION_TEST = os.path.join(HERE, "plugin_expression_test")
 SUBMAP_TEST = os.path.join(HERE, "plugin_submap_test")
 MEDIAN_TEST = os.path.join(HERE, "plugin_median_test")
 RADIUS_FILTER_TEST = os.path.join(HERE, "plugin_radius_filter_test")
+WINDOW_EXPRESSION_TEST = os.path.join(HERE, "plugin_window_expression_test")
 SRCS = ["src/DeviceMap.cpp", "src/SlopeFilter.cpp", "src/StepFilter.cpp", "src/RoughnessFilter.cpp",
-        "src/FusedChainFilter.cpp", "src/SurfaceNormalsFilter.cpp", "src/MedianFillFilter.cpp", "src/MeanInRadiusFilter.cpp", "src/MinInRadiusFilter.cpp", "src/TraversabilityMap.cpp", "stubs/pluginlib/registry.cpp"]
+        "src/FusedChainFilter.cpp", "src/SurfaceNormalsFilter.cpp", "src/MedianFillFilter.cpp", "src/MeanInRadiusFilter.cpp", "src/MinInRadiusFilter.cpp", "src/SlidingWindowMathExpressionFilter.cpp", "src/TraversabilityMap.cpp", "stubs/pluginlib/registry.cpp"]
 
 
 def build(verbose=False):
@@ -81,6 +82,12 @@ def build(verbose=False):
     # traversabilityFilters/MeanInRadiusFilter, MinInRadiusFilter and TraversabilityMap::setSmoothElevation (tests/test_plugins_radius_filter.py)
     cmd = cmd[:cmd.index("-o")] + ["-o", RADIUS_FILTER_TEST]
     cmd[cmd.index(os.path.join(HERE, "test", "plugin_median_test.cpp"))] = os.path.join(HERE, "test", "plugin_radius_filter_test.cpp")
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    # traversabilityFilters/SlidingWindowMathExpressionFilter (tests/test_plugins_window_expression.py)
+    cmd = cmd[:cmd.index("-o")] + ["-o", WINDOW_EXPRESSION_TEST]
+    cmd[cmd.index(os.path.join(HERE, "test", "plugin_radius_filter_test.cpp"))] = os.path.join(HERE, "test", "plugin_window_expression_test.cpp")
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

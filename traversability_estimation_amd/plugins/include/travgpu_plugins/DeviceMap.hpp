@@ -53,6 +53,9 @@ class DeviceMap {
   /*! out_layer = the mean (TE_RADIUS_MEAN) / minimum (TE_RADIUS_MIN) of in_layer within radius on the device
    *  (te_run_radius_filter); what a plugin uploaded into out_layer is gone. */
   bool runRadiusFilter(int op, double radius, int in_layer, int out_layer);
+  /*! out_layer = text over the window of every cell of in_layer on the device (te_run_window_expression); what a plugin
+   *  uploaded into out_layer is gone. */
+  bool runWindowExpression(const te_window_expr_params& params, const std::string& text, int in_layer, int out_layer);
   bool download(grid_map::GridMap& map, const std::string& layer, int te_layer);
   const std::string& error() const { return error_; }
 

@@ -242,6 +242,11 @@ bool DeviceMap::runRadiusFilter(int op, double radius, int in_layer, int out_lay
   return check(te_run_radius_filter(ctx_, op, radius, in_layer, out_layer, 0, 1));
 }
 
+bool DeviceMap::runWindowExpression(const te_window_expr_params& params, const std::string& text, int in_layer, int out_layer) {
+  if (out_layer >= 0 && out_layer < kLayers) resident_[out_layer].valid = false;  // (written on the device)
+  return check(te_run_window_expression(ctx_, &params, text.c_str(), in_layer, out_layer, 0, 1));
+}
+
 bool DeviceMap::download(grid_map::GridMap& map, const std::string& layer, int te_layer) {
   if (start_row_ || start_col_) return check(te_download_layer_circular(ctx_, te_layer, map.get(layer).data(), 0, start_row_, start_col_));
   return check(te_download_layer(ctx_, te_layer, map.get(layer).data(), 0, 1));
