@@ -10,7 +10,9 @@ The calls of a round: te_upload_image (two transparent pixels: the sparse-hole m
 tie radius of the step filter (the tie scratch), TE_OPT_FP_ANY_REACH = 1 and TE_OPT_FILTER_ANY_RADIUS = 2 passes, occupancy,
 cloud and an expression with a reduction, robot_slope + te_check_inclination, the polygon footprint (twice: its table stream
 is reused) and the polygon checks, the circular path checks on the footprint layer and te_check_footprint_paths_radius
-with 20 distinct radii (more than the 16 cached tables: the tables of the call alone), two tiles through the staging slots.
+with 20 distinct radii (more than the 16 cached tables: the tables of the call alone), two tiles through the staging slots,
+and the radius filter, a window expression and the median fill in place on traversability_slope (the copy of the input
+such a call reads: allocated, released with the layers, back larger).
 
 That the inputs reach the tie scratch and the hole queue is checked, not trusted: the step radius is on the circle by
 build_disc's own rule (tie_offsets below restates it) and the upload's counts satisfy te_hole_routing.h's rule for the sparse
@@ -145,6 +147,11 @@ def run_round(capi, ctx, shape, te_p):
         ctx.download_tile_async("traversability", 0, 3, 5, t)
         ctx.sync()
         out[f"tile{k}"] = t
+    # the three layer filters in place on a layer nothing above reads again: the copy of the input each of them reads
+    ctx.run_radius_filter("mean", 1.5 * RES, "traversability_slope")
+    ctx.run_window_expression("mean(traversability_slope)", dict(window_size=3), "traversability_slope")
+    ctx.run_median_fill(None, "traversability_slope")
+    layers("filters_in_place", ("traversability_slope",))
     return out
 
 

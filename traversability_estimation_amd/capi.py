@@ -755,10 +755,18 @@ class Context:
 
     def time_median_fill_samples(self, params, layer="elevation", out="traversability_roughness", warmup=3, iters=50):
         """Device time of each of `iters` fills (params=None: device copies of the layer, the fill's floor), in ms."""
+        return self._time_samples(load().te_time_median_fill_samples, (None if params is None else C.byref(params),), layer, out, warmup, iters)
+
+    def _time_samples(self, entry, args, in_layer, out_layer, warmup, iters):
+        """te_time_*_samples of a layer filter: `args` are what it takes between the context and the two layers."""
         ms = (C.c_float * int(iters))()
-        _check(load().te_time_median_fill_samples(self._h, None if params is None else C.byref(params), LAYERS[layer], LAYERS[out],
-                                                  int(warmup), int(iters), ms))
+        _check(entry(self._h, *args, LAYERS[in_layer], LAYERS[out_layer], int(warmup), int(iters), ms))
         return np.array(ms[:], dtype=np.float64)
+
+    def _block_counts(self, entry):
+        counts = (C.c_uint64 * 2)()
+        _check(entry(self._h, counts))
+        return int(counts[0]), int(counts[1])
 
     def run_radius_filter(self, op, radius, in_layer="elevation", out_layer=None, map0=0, nmaps=None):
         """gridMapFilters/MeanInRadiusFilter (op RADIUS_MEAN or "mean") / MinInRadiusFilter (RADIUS_MIN, "min") on the device
@@ -771,15 +779,11 @@ class Context:
 
     def radius_filter_stats(self):
         """(workgroups the sliding kernel settled, workgroups the in-order gather settled) of the last run_radius_filter."""
-        counts = (C.c_uint64 * 2)()
-        _check(load().te_radius_filter_stats(self._h, counts))
-        return int(counts[0]), int(counts[1])
+        return self._block_counts(load().te_radius_filter_stats)
 
     def time_radius_filter_samples(self, op, radius, in_layer="elevation", out_layer="traversability_roughness", warmup=3, iters=50):
         """Device time of each of `iters` radius filters (op 0: device copies of the layer), in ms."""
-        ms = (C.c_float * int(iters))()
-        _check(load().te_time_radius_filter_samples(self._h, int(op), float(radius), LAYERS[in_layer], LAYERS[out_layer], int(warmup), int(iters), ms))
-        return np.array(ms[:], dtype=np.float64)
+        return self._time_samples(load().te_time_radius_filter_samples, (int(op), float(radius)), in_layer, out_layer, warmup, iters)
 
     def run_window_expression(self, text, params, in_layer="elevation", out_layer=None, map0=0, nmaps=None):
         """gridMapFilters/SlidingWindowMathExpressionFilter on the device (te_run_window_expression): `out_layer` (default:
@@ -793,16 +797,12 @@ class Context:
 
     def window_expression_stats(self):
         """(workgroups the separable route settled, workgroups that walked directly) of the last run_window_expression."""
-        counts = (C.c_uint64 * 2)()
-        _check(load().te_window_expression_stats(self._h, counts))
-        return int(counts[0]), int(counts[1])
+        return self._block_counts(load().te_window_expression_stats)
 
     def time_window_expression_samples(self, text, params, in_layer="elevation", out_layer="traversability_roughness", warmup=3, iters=50):
         """Device time of each of `iters` window expressions (text=None: device copies of the layer), in ms."""
-        ms = (C.c_float * int(iters))()
-        _check(load().te_time_window_expression_samples(self._h, None if text is None else C.byref(params), None if text is None else str(text).encode(),
-                                                        LAYERS[in_layer], LAYERS[out_layer], int(warmup), int(iters), ms))
-        return np.array(ms[:], dtype=np.float64)
+        args = (None, None) if text is None else (C.byref(params), str(text).encode())
+        return self._time_samples(load().te_time_window_expression_samples, args, in_layer, out_layer, warmup, iters)
 
     def time_expression_samples(self, text, warmup=3, iters=50):
         """Device ms of `iters` run_expression(text) launches, one event pair each; text=None times run_filter("combine")."""

@@ -8,6 +8,7 @@
 #define TRAVGPU_PLUGINS_DEVICEMAP_HPP
 
 #include <cstdint>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -57,6 +58,9 @@ class DeviceMap {
    *  uploaded into out_layer is gone. */
   bool runWindowExpression(const te_window_expr_params& params, const std::string& text, int in_layer, int out_layer);
   bool download(grid_map::GridMap& map, const std::string& layer, int te_layer);
+  /*! A filter that works in place in the device's elevation layer (what the Step, Roughness and SurfaceNormals plugins read):
+   *  uploads `in` there, calls `run`, adds `out` to the map, downloads it and notes it resident -- the plugins behind find it. */
+  bool filterElevation(grid_map::GridMap& map, const std::string& in, const std::string& out, const std::function<bool()>& run);
   const std::string& error() const { return error_; }
 
  private:

@@ -252,4 +252,11 @@ bool DeviceMap::download(grid_map::GridMap& map, const std::string& layer, int t
   return check(te_download_layer(ctx_, te_layer, map.get(layer).data(), 0, 1));
 }
 
+bool DeviceMap::filterElevation(grid_map::GridMap& map, const std::string& in, const std::string& out, const std::function<bool()>& run) {
+  if (!(prepare(map) && upload(map, in, TE_LAYER_ELEVATION) && run())) return false;
+  if (!map.exists(out)) map.add(out);
+  // what comes back is what the device layer holds
+  return download(map, out, TE_LAYER_ELEVATION) && noteResident(map, out, TE_LAYER_ELEVATION);
+}
+
 }  // namespace travgpu_plugins

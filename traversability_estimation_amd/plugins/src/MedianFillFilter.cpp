@@ -60,13 +60,7 @@ bool MedianFillFilter<T>::update(const T& mapIn, T& mapOut) {
   }
   DeviceMap& dev = DeviceMap::instance();
   std::lock_guard<std::mutex> lock(dev.mutex());
-  // the layer is filled in place in the device's elevation layer: what the Step, Roughness and SurfaceNormals plugins read
-  bool ok = dev.prepare(mapOut) && dev.upload(mapOut, inputLayer_, TE_LAYER_ELEVATION) && dev.runMedianFill(params_, TE_LAYER_ELEVATION, TE_LAYER_ELEVATION);
-  if (ok) {
-    if (!mapOut.exists(outputLayer_)) mapOut.add(outputLayer_);
-    // what comes back is what the device layer holds: the plugins behind this one find it resident
-    ok = dev.download(mapOut, outputLayer_, TE_LAYER_ELEVATION) && dev.noteResident(mapOut, outputLayer_, TE_LAYER_ELEVATION);
-  }
+  const bool ok = dev.filterElevation(mapOut, inputLayer_, outputLayer_, [&] { return dev.runMedianFill(params_, TE_LAYER_ELEVATION, TE_LAYER_ELEVATION); });
   if (!ok) ROS_ERROR("MedianFillFilter (MI355X): %s", dev.error().c_str());
   return ok;
 }
