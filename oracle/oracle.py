@@ -151,6 +151,50 @@ def step(g, elev, crit, r1, r2, ncrit, want_step_height=False):
     return (out, sh) if want_step_height else out
 
 
+def normals(g, elev, radius, axis=2):
+    """NormalVectorsFilter alone (teo_normals): (surface_normal_x, _y, _z), NaN where the centre elevation is invalid."""
+    n = g.rows * g.cols
+    e = _flat(elev, n)
+    nrm = [np.empty(n, np.float32) for _ in range(3)]
+    rc = lib().teo_normals(C.byref(g), _f(e), float(radius), int(axis), _f(nrm[0]), _f(nrm[1]), _f(nrm[2]))
+    if rc:
+        raise RuntimeError(f"teo_normals failed: {rc}")
+    return tuple(nrm)
+
+
+def slope(g, nz, crit):
+    """SlopeFilter alone (teo_slope) on any surface_normal_z layer."""
+    n = g.rows * g.cols
+    z = _flat(nz, n)
+    out = np.empty(n, np.float32)
+    rc = lib().teo_slope(C.byref(g), _f(z), float(crit), _f(out))
+    if rc:
+        raise RuntimeError(f"teo_slope failed: {rc}")
+    return out
+
+
+def roughness(g, elev, nx, ny, nz, crit, radius):
+    """RoughnessFilter alone (teo_roughness) with the normals it is given, its own or foreign ones."""
+    n = g.rows * g.cols
+    e, x, y, z = (_flat(a, n) for a in (elev, nx, ny, nz))
+    out = np.empty(n, np.float32)
+    rc = lib().teo_roughness(C.byref(g), _f(e), _f(x), _f(y), _f(z), float(crit), float(radius), _f(out))
+    if rc:
+        raise RuntimeError(f"teo_roughness failed: {rc}")
+    return out
+
+
+def combine(slope_layer, step_layer, rough_layer, w_scale, w_slope, w_step, w_rough):
+    """MathExpressionFilter's fixed weighted sum (teo_combine) of three score layers of any common size."""
+    s = np.ascontiguousarray(slope_layer, dtype=np.float32).reshape(-1)
+    t, r = _flat(step_layer, s.size), _flat(rough_layer, s.size)
+    out = np.empty(s.size, np.float32)
+    rc = lib().teo_combine(s.size, _f(s), _f(t), _f(r), w_scale, w_slope, w_step, w_rough, _f(out))
+    if rc:
+        raise RuntimeError(f"teo_combine failed: {rc}")
+    return out
+
+
 def footprint(g, p, elev, layers, want_memo=False):
     n = g.rows * g.cols
     e = _flat(elev, n)

@@ -5,6 +5,9 @@
 //   chain_route_check conditioning  reads "rows cols res radius-cells kept hole-fraction clustered generic any step1-cells
 //                                   step2-cells batch" per line, prints the planned normals kernel in the words of
 //                                   tests/test_gpu_conditioning.py's ids
+//   chain_route_check filter        reads "rows cols batch res filter radius-cells second-radius-cells generic any hole-fraction
+//                                   clustered" per line (filter: TE_FILTER_STEP, _ROUGHNESS or _NORMALS; the second radius is the step
+//                                   filter's second window), prints plan_filter_route's route: the two step passes, or the normals kernel
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -410,6 +413,31 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  fprintf(stderr, "usage: %s cases | sweep N SEED | conditioning < lines\n", argv[0]);
+  if (argc >= 2 && !strcmp(argv[1], "filter")) {
+    Case c;
+    double r1, r2;
+    int generic, any, clustered;
+    while (scanf("%d %d %d %lf %d %lf %lf %d %d %lf %d", &c.rows, &c.cols, &c.batch, &c.res, &c.filter, &r1, &r2, &generic, &any, &c.hole_fraction,
+                 &clustered) == 11) {
+      if (c.filter != kFilterStep && c.filter != kFilterRoughness && c.filter != kFilterNormals) return 1;
+      // (the discs of the other filters: the parameters' defaults, which no single plugin's plan reads)
+      c.rn = c.rr = c.s1 = c.s2 = 0.05 / c.res;
+      if (c.filter == kFilterStep) c.s1 = r1, c.s2 = r2;
+      if (c.filter == kFilterRoughness) c.rr = r1;
+      if (c.filter == kFilterNormals) c.rn = r1;
+      c.generic = generic != 0;
+      c.clustered = clustered != 0;
+      for (bool& a : c.any) a = any != 0;
+      const ChainRouteIn in = inputs(c);
+      const ChainRoute r = plan(in, c);
+      if (check(in, r, c, "filter")) return 1;
+      if (c.filter == kFilterStep)
+        printf("%s %s\n", step_name(r.step_height, true).c_str(), step_name(r.step_score, true).c_str());
+      else
+        printf("%s\n", normals_name(r).c_str());
+    }
+    return 0;
+  }
+  fprintf(stderr, "usage: %s cases | sweep N SEED | conditioning < lines | filter < lines\n", argv[0]);
   return 2;
 }

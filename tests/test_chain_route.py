@@ -139,11 +139,39 @@ def test_conditioning_ids_name_the_planned_kernel(exe):
     assert not wrong, wrong
 
 
+def _plugin_routes(exe):
+    """(case, planned route, claimed route) of every case of tests/plugin_filter_cases.py, asked of plan_filter_route."""
+    from tests import plugin_filter_cases as K
+    r = subprocess.run([exe, "filter"], input="\n".join(K.route_line(c) for c in K.ALL) + "\n", capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    planned = [ln for ln in r.stdout.split("\n") if ln]
+    assert len(planned) == len(K.ALL)
+    return [(K.case_id(c), c.filter, p, K.route_words(c)) for c, p in zip(K.ALL, planned)]
+
+
+# the routes the single plugins' GPU tests have to reach, as the `filter` mode prints them
+PLUGIN_ROUTES = {2: {"k_step_small", "march<5>", "march<29>", "RAW<8>+ties", "RAW<20>+ties", "generic", "any"},
+                 3: {"k_normals_slide", "k_normals_slide<R>", "k_normals", "any"},
+                 5: {"k_normals_small-CROSS", "k_normals3-KEEP-dense", "k_normals3-KEEP-TIES", "k_normals_slide<R>", "k_normals"}}
+
+
+def test_plugin_filter_cases_take_the_routes_they_claim(exe):
+    """tests/test_gpu_plugin_filters.py names a route for every case it runs through te_run_filter: it is the one
+    plan_filter_route gives that shape, radius, flag and hole count; and between them the cases reach every route of each plugin."""
+    rows = _plugin_routes(exe)
+    wrong = [r for r in rows if r[2] != r[3]]
+    assert not wrong, wrong
+    for f, names in PLUGIN_ROUTES.items():
+        assert {w for r in rows if r[1] == f for w in r[2].split()} == names, f
+
+
 def test_under_sanitizers(tmp_path_factory):
-    """The same program with -fsanitize=address,undefined, stand-alone: the named cases and one sweep."""
+    """The same program with -fsanitize=address,undefined, stand-alone: the named cases, one sweep and the plugin cases."""
     exe = _build(tmp_path_factory, "chain_route_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
     r = subprocess.run([exe, "cases"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert _cases(r.stdout)[0] == CASES
     r = subprocess.run([exe, "sweep", "1000", "3"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "1000 cases, 0 failed checks" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    wrong = [r for r in _plugin_routes(exe) if r[2] != r[3]]
+    assert not wrong, wrong

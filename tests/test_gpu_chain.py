@@ -375,40 +375,6 @@ def test_pinned_host_buffers(capi):
         capi.unpin_host(dst)  # not registered any more
 
 
-def _roughness_given_numpy(elev, nx, ny, nz, rows, cols, res, radius, crit, cells):
-    """RoughnessFilter::update (RoughnessFilter.cpp:84-126) for the listed cells, normals taken from the layers.
-    Layout: o = j * rows + i; grid_map positions x = -res * i, y = -res * j (any common shift cancels)."""
-    R = int(np.floor(radius / res))
-    out = {}
-    for (i, j) in cells:
-        o = j * rows + i
-        if not np.isfinite(nx[o]):
-            out[(i, j)] = np.nan
-            continue
-        pts = []
-        for dj in range(-R, R + 1):
-            for di in range(-R, R + 1):
-                a, b = i + di, j + dj
-                if a < 0 or a >= rows or b < 0 or b >= cols:
-                    continue
-                if (di * di + dj * dj) * res * res > radius * radius:
-                    continue
-                z = elev[b * rows + a]
-                if np.isfinite(z):
-                    pts.append((-res * a, -res * b, float(z)))
-        P = np.array(pts, dtype=np.float64).reshape(-1, 3)
-        n = np.array([nx[o], ny[o], nz[o]], dtype=np.float64)
-        if len(P) == 0:
-            out[(i, j)] = 1.0 if crit > 0 else 0.0
-            continue
-        mean = P.sum(axis=0) / len(P)
-        d = P @ n - mean @ n
-        with np.errstate(divide="ignore", invalid="ignore"):
-            rough = np.sqrt(np.float64((d * d).sum()) / np.float64(len(P) - 1)) if len(P) > 1 else np.inf
-        out[(i, j)] = 1.0 - rough / crit if rough < crit else 0.0
-    return out
-
-
 @pytest.mark.parametrize("radius_cells", [3.6, 5.4, 9.2])
 def test_roughness_plugin_with_given_normals(capi, radius_cells):
     """te_run_filter(roughness) with normals that are NOT the chain's own (the unchanged-YAML case: they come from the
@@ -453,7 +419,8 @@ def test_roughness_plugin_with_given_normals(capi, radius_cells):
     cells += [(int(o % rows), int(o // rows)) for o in invalid[:40]]
     cells += [(int(o % rows), int(o // rows)) for o in rng.integers(0, n, size=150)]
     crit = float(p.rough_critical)
-    want = _roughness_given_numpy(elev, nx, ny, nz, rows, cols, res, radius, crit, cells)
-    for (i, j), w in want.items():
-        g = fast[j * rows + i]
+    from tests.ref_py.plugin_filters_ref import roughness_given
+    want = roughness_given(elev, nx, ny, nz, rows, cols, res, radius, crit)
+    for (i, j) in cells:
+        g, w = fast[j * rows + i], float(want[j * rows + i])
         assert (np.isnan(w) and np.isnan(g)) or abs(float(g) - w) <= 1e-5, ((i, j), float(g), w)

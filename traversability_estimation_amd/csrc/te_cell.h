@@ -206,7 +206,7 @@ __device__ __forceinline__ float roughness_score(const Mom& m, const double c[6]
   const double q1 = fma(c[1], a, fma(c[3], b, c[4] * cc));
   const double q2 = fma(c[2], a, fma(c[4], b, c[5] * cc));
   double q = fma(a, q0, fma(b, q1, cc * q2));
-  q = q > 0.0 ? q : 0.0;
+  q = q < 0.0 ? 0.0 : q;  // (a NaN stays: a NaN component of a given normal makes the comparison below false, score 0 -- RoughnessFilter.cpp:119)
   const double rough = sqrt(q * (double)m.n / (double)(m.n - 1));
   return rough < crit ? (float)(1.0 - rough / crit) : 0.0f;
 }

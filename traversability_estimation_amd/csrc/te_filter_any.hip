@@ -607,7 +607,7 @@ __device__ __forceinline__ double fa_rough(const MomL& m, const double c[6], con
   const double q2 = fma(c[2], a, fma(c[4], b, c[5] * cc));
   double q = fma(a, q0, fma(b, q1, cc * q2));
   *unsafe = !(q > 1e-7 * (c[0] + c[3] + c[5]));
-  q = q > 0.0 ? q : 0.0;
+  q = q < 0.0 ? 0.0 : q;  // (a NaN stays, and is `unsafe` above: the exact pass scores it 0 as the reference does)
   return sqrt(q * (double)m.n / (double)(m.n - 1));
 }
 

@@ -351,7 +351,7 @@ __device__ __forceinline__ void march(double* __restrict__ ring, const Geo& g, c
       const double cd = fma(Szz, inv_np, -mz * mz);
       // sum of squared distances to the plane / N = n^T C n with C = [[cxx,0,ca],[0,cxx,cb],[ca,cb,cd]] (RoughnessFilter.cpp:105-117)
       double q = fma(cxx, fma(gx, gx, gy * gy), fma(2.0 * gz, fma(gx, ca, gy * cb), gz * gz * cd));
-      q = q > 0.0 ? q : 0.0;
+      q = q < 0.0 ? 0.0 : q;  // (a NaN stays: NaN in surface_normal_y / _z under a finite _x is score 0, the reference's false comparison)
       const float rgh = __builtin_amdgcn_sqrtf((float)(q * nm1));
       const float rr = 1.0f - rgh * inv_rough_critf;
       const float rs = rgh < rough_critf ? rr : 0.0f;
