@@ -222,6 +222,39 @@ int te_get_params(te_ctx* ctx, te_params* p);
  * allowed (no nested reduction, its column partials fit in LDS; a workgroup that `mean` padding gives a clipped window still
  * walks directly), 2 the direct walk always.  The layers are identical under every value, bit for bit. */
 #define TE_OPT_WINDOW_EXPR_ROUTE 12
+/* gridMapFilters/NormalVectorsFilter `algorithm`: 0 (default) the area method (the PCA plane fit over the disc of normals_radius),
+ * 1 the raster method: the normal from the finite differences of a cell's four neighbours (k_normals_raster,
+ * csrc/te_normals_raster.hip).  Any other value: TE_ERR_INVALID_ARG.  Unlike the options above this one CHANGES the layers: setting
+ * it drops the chain's results and the kept normals (te_ctx_state.h: normals_algorithm_set) and the captured launches.
+ *
+ * The raster contract (restated, not pinned: grid_map_filters is not in the reference tree; written from memory of the filter
+ * shipped with ROS Noetic grid_map 1.6.x).  z: the input layer (float32), element (i, j) of a rows x cols
+ * map; res: the resolution (double); x grows towards smaller i, y towards smaller j; finite means isfinite.
+ *   1. The outermost line of cells is never visited: all three outputs are NaN where i == 0, i == rows-1, j == 0 or j == cols-1.
+ *      A map with fewer than 3 rows or columns is therefore all NaN.
+ *   2. An interior cell takes c = z[i,j], t = z[i-1,j], b = z[i+1,j], l = z[i,j-1], r = z[i,j+1], each widened to double.
+ *      x direction: gx = (b - t) / (2.0 * res) when t and b are finite; otherwise, when c is finite, gx = (c - t) / res if only t is
+ *      finite and gx = (b - c) / res if only b is finite; otherwise none.  y direction: gy likewise with l in place of t and r in
+ *      place of b.  If either direction has none, the three outputs are NaN.  An invalid centre between two finite pairs does get
+ *      a normal.
+ *   3. n = (gx, gy, 1.0); norm = sqrt((gx*gx + gy*gy) + 1.0); every component is divided by norm (a division, not a reciprocal
+ *      multiply); every operation is a separately rounded double; n = -n if the component on normal_vector_positive_axis is
+ *      < 0.0; the result is stored as float32.  This is (-dz/dx, -dz/dy, 1) normalised.
+ * The device's normals are held bit for bit against tests/ref_py/raster_normals_ref.py (tests/test_gpu_raster_normals.py).
+ *
+ * Under raster:
+ *   te_run_filter(TE_FILTER_NORMALS) writes the three normal layers and nothing else; the state afterwards is as after the area
+ *     method.
+ *   te_run_chain (any batch, every TE_RUN_* flag): the raster kernel writes the normals and traversability_slope (SlopeFilter's
+ *     rule on the float32 surface_normal_z), RoughnessFilter runs on those normals by the route TE_FILTER_ROUGHNESS takes (an
+ *     invalid centre with a normal gets a roughness, RoughnessFilter.cpp:84), the step filter and the combine as under area.  The
+ *     normal layers are written by every run, and count as present afterwards only with TE_RUN_KEEP_NORMALS, as under area.
+ *     TE_RUN_NORMALS_ONLY writes the normals and nothing else.
+ *   normals_radius is still validated by te_set_params (and its disc is still built: above 32 cells it needs
+ *     TE_OPT_FILTER_ANY_RADIUS as under area) but takes no part in results or routing; TE_OPT_NORMALS_RANK_RULE has no effect.
+ *   te_run_chain_region returns TE_ERR_UNSUPPORTED: the roughness route on given normals is whole-map only, and a region form of
+ *     it is not built. */
+#define TE_OPT_NORMALS_ALGORITHM 13
 int te_set_option(te_ctx* ctx, int option, int value);
 /* The face flags a footprint run would be given now (tests, diagnostics): batch x ceil(cols / 4) x ceil(rows / 64) bytes, the
  * flag of 64 cells along the rows fastest; `bytes` must be exactly that.  TE_ERR_NOT_READY while they are unknown or

@@ -37,6 +37,7 @@ OPT_WINDOW_EXPR_ROUTE = 12  # te_run_window_expression: 0 by plan, 1 the separab
 EDGE_INSIDE, EDGE_CROP, EDGE_EMPTY, EDGE_MEAN = 0, 1, 2, 3  # te_window_expr_params.edge_handling
 EDGE_HANDLING = {"inside": EDGE_INSIDE, "crop": EDGE_CROP, "empty": EDGE_EMPTY, "mean": EDGE_MEAN}
 RADIUS_MEAN, RADIUS_MIN = 1, 2  # te_run_radius_filter: gridMapFilters/MeanInRadiusFilter, MinInRadiusFilter
+OPT_NORMALS_ALGORITHM = 13  # NormalVectorsFilter: 0 the area method (default), 1 the raster method (finite differences of the four neighbours; changes the layers)
 OPT_FILTER_ANY_RADIUS = 8  # filter discs: 0 up to 32 cells (TE_ERR_UNSUPPORTED above), 1 any radius, 2 the route of any radius for every disc
 
 # every symbol include/travgpu.h declares (tests/test_cabi.py checks the library exports them all)

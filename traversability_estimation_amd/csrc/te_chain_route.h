@@ -59,6 +59,7 @@ struct ChainRouteIn {
   ChainRect region = {0, 0, 0, 0};
   bool keep_normals = false, normals_only = false, generic_kernels = false, defer_combine = false;  // TE_RUN_*, kDeferCombine
   bool aux_stream = false;    // the shim hands a second stream (from 2^21 cells on, not under TE_RUN_SEQUENTIAL)
+  bool raster = false;        // TE_OPT_NORMALS_ALGORITHM = 1: NormalVectorsFilter's raster method (whole maps only)
   bool sparse_holes = false, no_holes = false, skip_clean = false, short_strips = false, hole_queue = false;  // Layers' hints
   bool clip_table = true, tie_scratch = true, block_flags = true;
   bool guard_rows_elev = true, guard_rows_step_height = true;  // layer_has_guard_rows
@@ -75,7 +76,7 @@ enum WholeKind { kWholeNone, kWholeChainWindow, kWholeNormalsSmall };  // k_chai
 enum StepKind { kStepSmall, kStepMarch, kStepMarchTies, kStepGeneric, kStepAny };
 enum NormalsKind {
   kNormalsSmall, kNormals3Slim, kNormals3Sparse, kNormals3Dense, kNormals3Ties, kNormalsSlideShape, kNormalsSlideRadius, kNormalsGeneric,
-  kNormalsAny, kNormalsNone
+  kNormalsAny, kNormalsNone, kNormalsRaster
 };
 enum CombineKind { kCombineNone, kCombineInNormals, kCombineKernel, kCombineDeferred, kCombineInChain };
 
@@ -99,6 +100,11 @@ struct ChainRoute {
   bool cross = false;     // k_normals_small: the CROSS instantiation (the one-cell tie radius)
   bool keep = false;      // the normals kernel writes the normal layers
   bool fixup = false;     // k_normals_fixup follows
+  // raster (normals == kNormalsRaster): k_normals_raster writes the normals, and the slope with `raster_slope`; the roughness
+  // stage behind it reads those normals on the route TE_FILTER_ROUGHNESS takes (kNormalsNone: no roughness stage)
+  bool raster_slope = false;
+  NormalsKind rough = kNormalsNone;
+  bool rough_fixup = false;
   CombineKind combine = kCombineNone;
   bool two_streams = false;
   bool steps = false;     // the step filter runs (not inside a one-kernel chain, not under normals only)
@@ -213,6 +219,36 @@ inline void plan_normals(const ChainRouteIn& in, const ChainRect& r, bool fused,
   o.combine = in.normals_only ? kCombineNone : in.defer_combine ? kCombineDeferred : combined ? kCombineInNormals : kCombineKernel;
 }
 
+// RoughnessFilter on given normals (TE_FILTER_ROUGHNESS, and the roughness stage of a raster chain), whole maps: the sliding
+// kernel + fix-up for a tie-free disc, the generic kernel, or the route of any radius
+inline void plan_given_roughness(const ChainRouteIn& in, NormalsKind& kind, bool& fixup) {
+  const DiscSummary& d = in.rough;
+  fixup = false;
+  if (d.any)
+    kind = kNormalsAny;
+  else if (!in.generic_kernels && d.n_ties == 0 && slide_radius(d.R) && d.npoints >= 3 && in.block_flags && holds_disc(in, d.R)) {
+    kind = d.Q >= 1 && disc_shape(d.Q) ? kNormalsSlideShape : kNormalsSlideRadius;
+    fixup = true;
+  } else
+    kind = kNormalsGeneric;
+}
+
+// The chain under the raster method, whole maps (a region run is refused by the shim: normals stays kNormalsNone, which no
+// launcher takes).  Never a one-kernel route; the normal layers are always written, roughness reads them.
+inline void plan_raster(const ChainRouteIn& in, ChainRoute& o) {
+  o.two_streams = in.aux_stream && !in.normals_only;
+  o.steps = !in.normals_only;
+  if (o.steps) {
+    o.step_height = plan_step(in, in.step1, o.r_step1, in.guard_rows_elev);
+    o.step_score = plan_step(in, in.step2, o.r_step2, in.guard_rows_step_height);
+  }
+  o.normals = kNormalsRaster;
+  o.keep = true;
+  o.raster_slope = !in.normals_only;
+  if (!in.normals_only) plan_given_roughness(in, o.rough, o.rough_fixup);
+  o.combine = in.normals_only ? kCombineNone : in.defer_combine ? kCombineDeferred : kCombineKernel;
+}
+
 inline void plan_rects(const ChainRouteIn& in, ChainRoute& o) {
   const int kn = in.normals.reach > in.rough.reach ? in.normals.reach : in.rough.reach, ks = in.step1.reach + in.step2.reach;
   o.r_step1 = grown(in, in.step1.reach);
@@ -227,6 +263,10 @@ inline ChainRoute plan_chain_route(const ChainRouteIn& in) {
   using namespace route_detail;
   ChainRoute o;
   plan_rects(in, o);
+  if (in.raster) {
+    if (in.whole) plan_raster(in, o);
+    return o;
+  }
   const DiscSummary& d = in.normals;
   // A whole-map launch in ONE kernel (a disc marked `any` takes te_filter_any.hip for its own stage: none of these)
   if (in.whole && !in.generic_kernels && !any_disc(in) && !in.normals_only && in.same_rough_disc && in.axis == 2) {
@@ -260,7 +300,8 @@ inline ChainRoute plan_chain_route(const ChainRouteIn& in) {
 
 // One reference plugin at a time (launch_filter): always the whole maps.  TE_FILTER_STEP fills the two step routes,
 // TE_FILTER_ROUGHNESS `normals` (given normals: the sliding kernel + fix-up, the generic kernel, or any radius),
-// TE_FILTER_NORMALS is the chain plan with the roughness disc set to the normals disc, normals kept, normals only.
+// TE_FILTER_NORMALS is the chain plan with the roughness disc set to the normals disc, normals kept, normals only (under
+// raster: k_normals_raster alone).
 inline ChainRoute plan_filter_route(const ChainRouteIn& in0, int filter) {
   using namespace route_detail;
   ChainRouteIn in = in0;
@@ -279,15 +320,8 @@ inline ChainRoute plan_filter_route(const ChainRouteIn& in0, int filter) {
     o.step_height = plan_step(in, in.step1, o.r_step1, in.guard_rows_elev);
     o.step_score = plan_step(in, in.step2, o.r_step2, in.guard_rows_step_height);
   } else if (filter == kFilterRoughness) {
-    const DiscSummary& d = in.rough;
     o.keep = true;
-    if (d.any)
-      o.normals = kNormalsAny;
-    else if (!in.generic_kernels && d.n_ties == 0 && slide_radius(d.R) && d.npoints >= 3 && in.block_flags && holds_disc(in, d.R)) {
-      o.normals = d.Q >= 1 && disc_shape(d.Q) ? kNormalsSlideShape : kNormalsSlideRadius;
-      o.fixup = true;
-    } else
-      o.normals = kNormalsGeneric;
+    plan_given_roughness(in, o.normals, o.fixup);
   } else if (filter == kFilterCombine) {
     o.combine = kCombineKernel;
   }

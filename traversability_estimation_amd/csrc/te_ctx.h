@@ -132,6 +132,7 @@ struct te_ctx {
   // te_set_option: choices between kernels that give identical results (tests reach both; never read from the environment)
   int opt_fb_walk = 0, opt_fb_blocks_per_cu = 0, opt_polygon_per_cell = 0, opt_graph = 0, opt_bcast_rccl = 0, opt_rank_rule = 0,
       opt_fp_any = 0;
+  int opt_normals_raster = 0;  // TE_OPT_NORMALS_ALGORITHM: 1 the raster method (changes the layers: te_ctx_state.h, normals_algorithm_set)
   // TE_OPT_FILTER_ANY_RADIUS (0: discs above 32 cells refused, 1: those take te_filter_any.hip, 2: every disc does), the host
   // tables of the filter discs that route takes (normals, roughness, step windows 1 and 2) and their device copy (cmem.fa_tab),
   // uploaded by rebuild_tables (never inside a launch: whole-map launches are captured)

@@ -135,6 +135,12 @@ struct CtxState {
   void footprint_option_changed() { footprint_done_ = false; }
   // TE_OPT_FILTER_ANY_RADIUS changed, TE_OPT_NORMALS_RANK_RULE set
   void filter_option_changed() { drop_results(); }
+  // TE_OPT_NORMALS_ALGORITHM set (area <-> raster): the chain's results are the other method's, and so are normal layers a
+  // chain or TE_FILTER_NORMALS kept -- they stop counting as written until the next run writes them
+  void normals_algorithm_set() {
+    drop_results();
+    layers_written_ &= ~kNormalLayers;
+  }
 
   // ---- launches --------------------------------------------------------------------------------------------------------
   // A chain is about to be launched over the whole map or a region, with the TE_RUN_* flags it will run with.  Returns

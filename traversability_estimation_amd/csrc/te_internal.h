@@ -65,6 +65,7 @@ struct ChainParams {
   int same_rough_disc;  // roughness radius selects the same cells as the normals radius
   int axis;             // normal_vector_positive_axis
   int rank_rule;        // TE_OPT_NORMALS_RANK_RULE: a rank-deficient scatter matrix gives UnitZ (generic normals kernel)
+  int raster;           // TE_OPT_NORMALS_ALGORITHM = 1: the raster method (te_normals_raster.hip); the normals disc is not read
   double slope_crit, step_crit, rough_crit;
   int step_ncrit;
   float w_scale, w_slope, w_step, w_rough;
@@ -400,6 +401,10 @@ hipError_t normals_small(const Geo& g, const ChainParams& p, const Layers& L, bo
                          bool write_step, bool combine);
 // ... and the whole chain of a small whole-map launch in one kernel (k_chain_window)
 hipError_t chain_window(const Geo& g, const ChainParams& p, const Layers& L, bool keep_normals, const Region& r, bool combine, hipStream_t s);
+// te_normals_raster.hip: NormalVectorsFilter's raster method on every cell of every map: the three normal layers, and with
+// `slope` (the chain form; nullptr: the normals alone) traversability_slope
+hipError_t normals_raster(const Geo& g, int axis, double slope_crit, const float* elev, float* nx, float* ny, float* nz, float* slope,
+                          hipStream_t s);
 int normals_fast_max_blocks(const Geo& g);
 size_t normals_hole_queue_bytes();  // te_normals3.hip: scratch of the sparse-hole march for one device (any map, any batch)
 // The sum kernels of the circular footprint pass, each on the route plan_fp_route chose for it (false: the shape is not

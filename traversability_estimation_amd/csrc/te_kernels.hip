@@ -531,6 +531,7 @@ ChainRouteIn route_inputs(const Geo& g, const ChainParams& p, const Layers& L, c
   in.generic_kernels = (flags & TE_RUN_GENERIC_KERNELS) != 0;
   in.defer_combine = (flags & kDeferCombine) != 0;
   in.aux_stream = L.aux_stream != nullptr;
+  in.raster = p.raster != 0;
   in.sparse_holes = L.sparse_holes != 0;
   in.no_holes = L.no_holes != 0;
   in.skip_clean = L.skip_clean != 0;
@@ -618,6 +619,7 @@ hipError_t launch_normals(const Geo& g, const ChainParams& p, const Layers& L, c
       e = given ? normals_slide(g, p, L, p.rough, (int)in.rough.sii_runs, shape_form, true, true, false, rn, L.block_flags, s)
                 : normals_slide(g, p, L, p.normals, (int)in.normals.sii_runs, shape_form, false, rt.keep, na.combine != 0, rn, L.block_flags, s);
       break;
+    case kNormalsRaster:  // (launch_route's own stage)
     case kNormalsNone: return hipErrorInvalidValue;
   }
   if (e != hipSuccess || !rt.fixup) return e;
@@ -665,7 +667,19 @@ hipError_t launch_route(const Geo& g, const ChainParams& p, const Layers& L, con
     if ((e = launch_step_filter(g, p, L, rt, region_of(r, rt.r_step1), region_of(r, rt.r_step2), ss)) != hipSuccess) return e;
   }
   if (rt.two_streams) (void)hipEventRecord(L.ev_join, ss);
-  {
+  if (rt.normals == kNormalsRaster) {
+    // NormalVectorsFilter's raster method: one pass writes the normals (and the slope), RoughnessFilter follows on those
+    // normals by the route TE_FILTER_ROUGHNESS takes
+    TraceRange tr_raster("chain: raster normals + slope, roughness on given normals (+ fix-up)");
+    if ((e = normals_raster(g, p.axis, p.slope_crit, L.elev, L.nx, L.ny, L.nz, rt.raster_slope ? L.slope : nullptr, stream)) != hipSuccess) return e;
+    if (rt.rough != kNormalsNone) {
+      ChainRoute rr = rt;
+      rr.normals = rt.rough;
+      rr.fixup = rt.rough_fixup;
+      e = launch_normals(g, p, L, rr, in, normals_args(p, p.rough, p.rough, true, true, false), true, L.nx, L.ny, L.nz, region_of(r, rt.r_normals), stream);
+      if (e != hipSuccess) return e;
+    }
+  } else {
     TraceRange tr_normals("chain: normals + slope + roughness (+ fix-up)");
     const NormalsArgs na = normals_args(p, p.normals, p.rough, p.same_rough_disc != 0, false, rt.combine == kCombineInNormals);
     e = launch_normals(g, p, L, rt, in, na, false, rt.keep ? L.nx : nullptr, rt.keep ? L.ny : nullptr, rt.keep ? L.nz : nullptr,

@@ -319,12 +319,14 @@ void set_launch_hints(te_ctx* c) {
   c->L.hole_queue = c->cmem.hole_queue.as<char>();
   c->L.tie_scratch = c->lmem.tie_scratch.as<float>();
   c->cp.rank_rule = c->opt_rank_rule;
+  c->cp.raster = c->opt_normals_raster;
 }
 
 // TE_OPT_NORMALS_RANK_RULE decides on the rank of an exactly planar disc; on a normals disc above 32 cells the moment form's
 // pivot test and the oracle's (centred points, 3 eps) disagree on rounding noise, so the combination is refused
+// (The raster method has no disc and no rank: the rule has no effect there.)
 int refuse_rank_rule(te_ctx* c) {
-  if (c->opt_rank_rule && c->cp.normals.any)
+  if (c->opt_rank_rule && !c->opt_normals_raster && c->cp.normals.any)
     return fail(TE_ERR_UNSUPPORTED, "TE_OPT_NORMALS_RANK_RULE is not supported with a normals disc of the route of any radius (%d cells)",
                 c->cp.normals.R);
   return TE_OK;
@@ -642,7 +644,7 @@ int run_chain_locked(te_ctx* c, unsigned flags, const Region& r) {
   c->L.fb_walk = c->opt_fb_walk;
   c->L.fb_blocks_per_cu = c->opt_fb_blocks_per_cu;
   set_launch_hints(c);  // (run_whole_locked allocates their buffers before it captures)
-  if (c->opt_rank_rule) flags |= TE_RUN_GENERIC_KERNELS;  // (the rule lives in the generic normals kernel only)
+  if (c->opt_rank_rule && !c->opt_normals_raster) flags |= TE_RUN_GENERIC_KERNELS;  // (the rule lives in the generic normals kernel only)
   const hipError_t e = launch_chain(c->geo, c->cp, c->L, r, flags, c->stream);
   ROUTE_TRY(e, "te_run_chain");
   HIP_TRY(e);
@@ -679,7 +681,7 @@ int run_whole_locked(te_ctx* c, unsigned flags) {
   const bool large = c->opt_graph == 1 || (c->opt_graph == 0 && (size_t)c->geo.rows * c->geo.cols * c->geo.batch >= ((size_t)1 << 22));
   // (only the defined TE_RUN_* bits: the graph key below puts its own hints into the upper bits of the same word)
   flags &= TE_RUN_KEEP_NORMALS | TE_RUN_FOOTPRINT | TE_RUN_GENERIC_KERNELS | TE_RUN_FOOTPRINT_MEMO | TE_RUN_SEQUENTIAL | TE_RUN_NORMALS_ONLY;
-  if (c->opt_rank_rule) flags |= TE_RUN_GENERIC_KERNELS;
+  if (c->opt_rank_rule && !c->opt_normals_raster) flags |= TE_RUN_GENERIC_KERNELS;
   if (flags & TE_RUN_NORMALS_ONLY) flags &= ~(TE_RUN_FOOTPRINT | TE_RUN_FOOTPRINT_MEMO);
   if (!no_graph && large && !(flags & TE_RUN_NORMALS_ONLY) && c->graph_ok && c->have_params && c->have_geo && c->st.have_elev()) {
     if (!c->tables_ready) {
@@ -985,6 +987,12 @@ int te_set_option(te_ctx* c, int option, int value) {
       c->opt_rank_rule = value != 0;
       c->st.filter_option_changed();
       break;
+    case TE_OPT_NORMALS_ALGORITHM:
+      if (value < 0 || value > 1) return fail(TE_ERR_INVALID_ARG, "te_set_option: TE_OPT_NORMALS_ALGORITHM takes 0 (area) or 1 (raster)");
+      if (c->opt_normals_raster == value) return TE_OK;  // (the plugins set it before every update: nothing to drop)
+      c->opt_normals_raster = value;
+      c->st.normals_algorithm_set();
+      break;  // (the captured launches are dropped below)
     default:
       return fail(TE_ERR_INVALID_ARG, "te_set_option: unknown option %d", option);
   }
@@ -1096,7 +1104,7 @@ int te_run_filter(te_ctx* c, int filter, unsigned flags) {
     if (int rc = refuse_rank_rule(c)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   set_launch_hints(c);  // (as in the chain: never stale ones)
-  if (c->opt_rank_rule) flags |= TE_RUN_GENERIC_KERNELS;
+  if (c->opt_rank_rule && !c->opt_normals_raster) flags |= TE_RUN_GENERIC_KERNELS;
   const hipError_t e = launch_filter(c->geo, c->cp, c->L, filter, flags, c->stream);
   ROUTE_TRY(e, "te_run_filter");
   HIP_TRY(e);
@@ -1120,6 +1128,9 @@ int te_run_chain_region(te_ctx* c, unsigned flags, int map, int row0, int col0, 
   if (map < 0 || map >= c->geo.batch || row0 < 0 || col0 < 0 || h <= 0 || w <= 0 || row0 + h > c->geo.rows ||
       col0 + w > c->geo.cols)
     return fail(TE_ERR_INVALID_ARG, "te_run_chain_region: rectangle outside the map");
+  if (c->opt_normals_raster)
+    return fail(TE_ERR_UNSUPPORTED, "te_run_chain_region: not built under TE_OPT_NORMALS_ALGORITHM = 1 (raster): the roughness route on given "
+                                    "normals is whole-map only; run te_run_chain");
   if (!c->st.chain_done()) return fail(TE_ERR_NOT_READY, "te_run_chain_region: run the full chain once first");
   const Region r = {map, row0, col0, row0 + h, col0 + w};
   const bool want_fp = (flags & (TE_RUN_FOOTPRINT | TE_RUN_FOOTPRINT_MEMO)) != 0;

@@ -82,7 +82,9 @@ def _axis(v):
 
 
 def filter_chain_fields(doc, general_expression=False):
-    """te_params fields (plain dict) + {"keep_normals": bool} from the `traversability_map_filters` list.
+    """te_params fields (plain dict) + {"keep_normals": bool, "normals_algorithm": 0 | 1} from the `traversability_map_filters`
+    list.  normals_algorithm is NormalVectorsFilter's `algorithm` key (area: 0, the default; raster: 1), the value of
+    TE_OPT_NORMALS_ALGORITHM: an option of the context, no field of te_params.
     general_expression: an expression parse_weighted_sum refuses leaves the four weights out (their defaults hold) instead
     of raising: the caller hands the text to te_run_expression."""
     if not isinstance(doc, dict) or CHAIN_KEY not in doc:
@@ -107,16 +109,22 @@ def filter_chain_fields(doc, general_expression=False):
     prefix = str(nrm.get("output_layers_prefix", "surface_normal_"))
     if prefix != "surface_normal_":
         raise ParamsYamlError("NormalVectorsFilter: output_layers_prefix must be 'surface_normal_' (SlopeFilter.cpp:71 hard-codes it)")
-    if str(nrm.get("algorithm", "area")) != "area":
-        raise ParamsYamlError("NormalVectorsFilter: only the area method is built")
-    out = {"normals_radius": float(need(nrm, "radius", "Normal vectors filter")), "normals_axis": _axis(nrm.get("normal_vector_positive_axis", "z")),
+    try:
+        algorithm = {"area": 0, "raster": 1}[str(nrm.get("algorithm", "area"))]
+    except KeyError:
+        raise ParamsYamlError(f"NormalVectorsFilter: algorithm must be area or raster (got '{nrm.get('algorithm')}')")
+    out = {}
+    # (upstream reads `radius` for the area method only: a raster file may leave it out, and te_params_default's value stays)
+    if algorithm == 0 or "radius" in nrm:
+        out["normals_radius"] = float(need(nrm, "radius", "Normal vectors filter"))
+    out.update({"normals_axis": _axis(nrm.get("normal_vector_positive_axis", "z")),
            "slope_critical": float(need(slope, "critical_value", "SlopeFilter")),
            "step_critical": float(need(step, "critical_value", "Step filter")),
            "step_radius1": float(need(step, "first_window_radius", "Step filter")),
            "step_radius2": float(need(step, "second_window_radius", "Step filter")),
            "step_ncrit": int(need(step, "critical_cell_number", "Step filter")),
            "rough_critical": float(need(rough, "critical_value", "Roughness filter")),
-           "rough_radius": float(need(rough, "estimation_radius", "Roughness filter"))}
+           "rough_radius": float(need(rough, "estimation_radius", "Roughness filter"))})
     for d, dflt in ((slope, "traversability_slope"), (step, "traversability_step"), (rough, "traversability_roughness")):
         if str(d.get("map_type", dflt)) != dflt:
             raise ParamsYamlError(f"map_type must stay '{dflt}': the footprint checks read the layers by these names (TraversabilityMap.cpp:52-56)")
@@ -135,6 +143,7 @@ def filter_chain_fields(doc, general_expression=False):
         if extra:
             raise ParamsYamlError(f"DeletionFilter: only the normal layers can be dropped (got {sorted(extra)})")
     out["keep_normals"] = len(deleted) != 3
+    out["normals_algorithm"] = algorithm
     # criticalStepHeight_ of the footprint checks is the step filter's critical value (TraversabilityMap.cpp:104-111)
     out["fp_critical_step"] = out["step_critical"]
     return out
@@ -180,8 +189,15 @@ def chain_expression(filter_yaml):
         return text, False
 
 
-def fields_from_yaml(filter_yaml, footprint_yaml=None, robot_yaml=None, general_expression=False):
+def fields_from_yaml(filter_yaml, footprint_yaml=None, robot_yaml=None, general_expression=False, normals_algorithm=False):
+    """te_params fields + keep_normals.  normals_algorithm: also the key of that name (filter_chain_fields).  Without it a
+    file that says `algorithm: raster` is refused -- the dict would describe the area method's chain -- and the key is left
+    out: everything else in the dict is a field of te_params."""
     f = filter_chain_fields(_load(filter_yaml), general_expression)
+    if not normals_algorithm:
+        if f.pop("normals_algorithm"):
+            raise ParamsYamlError("NormalVectorsFilter: algorithm: raster is an option of the context (TE_OPT_NORMALS_ALGORITHM), not a field "
+                                  "of te_params: read the file with params_options_from_yaml")
     if footprint_yaml is not None:
         f.update(footprint_fields(_load(footprint_yaml)))
     if robot_yaml is not None:
@@ -196,6 +212,17 @@ def params_from_yaml(capi, filter_yaml, footprint_yaml=None, robot_yaml=None):
     p = capi.default_params(**f)
     capi.validate_params(p)
     return p, (capi.RUN_KEEP_NORMALS if keep else 0)
+
+
+def params_options_from_yaml(capi, filter_yaml, footprint_yaml=None, robot_yaml=None):
+    """(te_params, run flags, options): params_from_yaml for a file that may say `algorithm: raster`.  options is a dict
+    {option: value} for Context.set_option -- {capi.OPT_NORMALS_ALGORITHM: 0 | 1}."""
+    f = fields_from_yaml(filter_yaml, footprint_yaml, robot_yaml, normals_algorithm=True)
+    keep = f.pop("keep_normals")
+    algorithm = f.pop("normals_algorithm")
+    p = capi.default_params(**f)
+    capi.validate_params(p)
+    return p, (capi.RUN_KEEP_NORMALS if keep else 0), {capi.OPT_NORMALS_ALGORITHM: algorithm}
 
 
 def params_and_expression_from_yaml(capi, filter_yaml, footprint_yaml=None, robot_yaml=None):

@@ -17,6 +17,7 @@ SUBMAP_TEST = os.path.join(HERE, "plugin_submap_test")
 MEDIAN_TEST = os.path.join(HERE, "plugin_median_test")
 RADIUS_FILTER_TEST = os.path.join(HERE, "plugin_radius_filter_test")
 WINDOW_EXPRESSION_TEST = os.path.join(HERE, "plugin_window_expression_test")
+RASTER_TEST = os.path.join(HERE, "plugin_raster_test")
 SRCS = ["src/DeviceMap.cpp", "src/SlopeFilter.cpp", "src/StepFilter.cpp", "src/RoughnessFilter.cpp",
         "src/FusedChainFilter.cpp", "src/SurfaceNormalsFilter.cpp", "src/MedianFillFilter.cpp", "src/MeanInRadiusFilter.cpp", "src/MinInRadiusFilter.cpp", "src/SlidingWindowMathExpressionFilter.cpp", "src/TraversabilityMap.cpp", "stubs/pluginlib/registry.cpp"]
 
@@ -88,6 +89,12 @@ def build(verbose=False):
     # traversabilityFilters/SlidingWindowMathExpressionFilter (tests/test_plugins_window_expression.py)
     cmd = cmd[:cmd.index("-o")] + ["-o", WINDOW_EXPRESSION_TEST]
     cmd[cmd.index(os.path.join(HERE, "test", "plugin_radius_filter_test.cpp"))] = os.path.join(HERE, "test", "plugin_window_expression_test.cpp")
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    # SurfaceNormalsFilter and FusedChainFilter with `algorithm: raster` (tests/test_plugins_raster.py)
+    cmd = cmd[:cmd.index("-o")] + ["-o", RASTER_TEST]
+    cmd[cmd.index(os.path.join(HERE, "test", "plugin_window_expression_test.cpp"))] = os.path.join(HERE, "test", "plugin_raster_test.cpp")
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

@@ -33,6 +33,7 @@ class FusedChainFilter : public FilterBase<T> {
   te_params params_;
   int keepNormals_;
   int rankRule_;  // unit_z_for_planar_discs (TE_OPT_NORMALS_RANK_RULE)
+  int raster_;    // algorithm: raster (TE_OPT_NORMALS_ALGORITHM)
   std::string expression_;  // empty: the weighted sum of the chain
 };
 

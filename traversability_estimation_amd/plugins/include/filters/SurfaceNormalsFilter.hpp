@@ -28,6 +28,7 @@ class SurfaceNormalsFilter : public FilterBase<T> {
   double radius_;
   int axis_;
   int rankRule_;  // unit_z_for_planar_discs (TE_OPT_NORMALS_RANK_RULE)
+  int raster_;    // algorithm: raster (TE_OPT_NORMALS_ALGORITHM)
   std::string inputLayer_, prefix_;
 };
 

@@ -63,6 +63,10 @@ class TraversabilityMap {
    *  elevation map, after the hole filling of setFillHoles -- and the chain sees the smoothed layer.  0 switches it off again
    *  (the default).  false (and nothing changed) for a radius that is negative or not finite. */
   bool setSmoothElevation(double radius);
+  /*! NormalVectorsFilter's `algorithm` of robot_filter_parameter.yaml: false the area method (the default), true the raster
+   *  method (te_set_option TE_OPT_NORMALS_ALGORITHM: the normal from the finite differences of a cell's four neighbours;
+   *  normals_radius then plays no part).  The next computeTraversability() runs it; results computed so far are dropped. */
+  bool setNormalsAlgorithm(bool raster);
   /*! traversabilityFootprint(radius, offset) (:307-318): layer traversability_footprint. */
   bool traversabilityFootprint(const double& radius, const double& offset);
   /*! traversabilityFootprint(footprintYaw) (:239-305): layers traversability_x / traversability_rot. */

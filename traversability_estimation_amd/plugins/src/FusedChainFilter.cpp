@@ -13,7 +13,7 @@ using travgpu_plugins::DeviceMap;
 namespace filters {
 
 template <typename T>
-FusedChainFilter<T>::FusedChainFilter() : keepNormals_(0), rankRule_(0) {
+FusedChainFilter<T>::FusedChainFilter() : keepNormals_(0), rankRule_(0), raster_(0) {
   te_params_default(&params_);
 }
 
@@ -33,6 +33,14 @@ bool FusedChainFilter<T>::configure() {
   FilterBase<T>::getParam(std::string("estimation_radius"), params_.rough_radius);
   FilterBase<T>::getParam(std::string("keep_surface_normals"), keepNormals_);
   FilterBase<T>::getParam(std::string("unit_z_for_planar_discs"), rankRule_);  // TE_OPT_NORMALS_RANK_RULE (see SurfaceNormalsFilter)
+  // NormalVectorsFilter's `algorithm`: area (the default) or raster (TE_OPT_NORMALS_ALGORITHM; normals_radius then plays no part)
+  std::string algorithm("area");
+  FilterBase<T>::getParam(std::string("algorithm"), algorithm);
+  if (algorithm != "area" && algorithm != "raster") {
+    ROS_ERROR("FusedChainFilter: algorithm must be area or raster (got '%s')", algorithm.c_str());
+    return false;
+  }
+  raster_ = algorithm == "raster" ? 1 : 0;
   // the MathExpressionFilter's expression when it is not the weighted sum: compiled here, run behind the chain
   expression_.clear();
   FilterBase<T>::getParam(std::string("expression"), expression_);
@@ -57,7 +65,7 @@ bool FusedChainFilter<T>::update(const T& mapIn, T& mapOut) {
   DeviceMap& dev = DeviceMap::instance();
   std::lock_guard<std::mutex> lock(dev.mutex());
   bool ok = dev.prepare(mapOut) && dev.setParams(params_) && dev.setOption(TE_OPT_NORMALS_RANK_RULE, rankRule_ ? 1 : 0) &&
-            dev.upload(mapOut, "elevation", TE_LAYER_ELEVATION) &&
+            dev.setOption(TE_OPT_NORMALS_ALGORITHM, raster_) && dev.upload(mapOut, "elevation", TE_LAYER_ELEVATION) &&
             dev.runChain(keepNormals_ ? TE_RUN_KEEP_NORMALS : 0u) && (expression_.empty() || dev.runExpression(expression_));
   for (int k = 0; ok && k < 4; ++k) {
     mapOut.add(kOut[k]);

@@ -13,14 +13,23 @@ using travgpu_plugins::DeviceMap;
 namespace filters {
 
 template <typename T>
-SurfaceNormalsFilter<T>::SurfaceNormalsFilter() : radius_(0.05), axis_(2), rankRule_(0), inputLayer_("elevation"), prefix_("surface_normal_") {}
+SurfaceNormalsFilter<T>::SurfaceNormalsFilter() : radius_(0.05), axis_(2), rankRule_(0), raster_(0), inputLayer_("elevation"), prefix_("surface_normal_") {}
 
 template <typename T>
 SurfaceNormalsFilter<T>::~SurfaceNormalsFilter() {}
 
 template <typename T>
 bool SurfaceNormalsFilter<T>::configure() {
-  if (!FilterBase<T>::getParam(std::string("radius"), radius_)) {
+  // NormalVectorsFilter's `algorithm`: area (the default) or raster (travgpu.h TE_OPT_NORMALS_ALGORITHM); upstream reads
+  // `radius` for the area method only, so a raster entry may leave it out (the default stays: it plays no part)
+  std::string algorithm("area");
+  FilterBase<T>::getParam(std::string("algorithm"), algorithm);
+  if (algorithm != "area" && algorithm != "raster") {
+    ROS_ERROR("SurfaceNormalsFilter: algorithm must be area or raster (got '%s')", algorithm.c_str());
+    return false;
+  }
+  raster_ = algorithm == "raster" ? 1 : 0;
+  if (!FilterBase<T>::getParam(std::string("radius"), radius_) && !raster_) {
     ROS_ERROR("SurfaceNormalsFilter did not find param radius");
     return false;
   }
@@ -60,7 +69,8 @@ bool SurfaceNormalsFilter<T>::update(const T& mapIn, T& mapOut) {
   if (ok) {
     p.normals_radius = radius_;
     p.normals_axis = axis_;
-    ok = dev.setParams(p) && dev.setOption(TE_OPT_NORMALS_RANK_RULE, rankRule_ ? 1 : 0) && dev.upload(mapOut, inputLayer_, TE_LAYER_ELEVATION) &&
+    ok = dev.setParams(p) && dev.setOption(TE_OPT_NORMALS_RANK_RULE, rankRule_ ? 1 : 0) &&
+         dev.setOption(TE_OPT_NORMALS_ALGORITHM, raster_) && dev.upload(mapOut, inputLayer_, TE_LAYER_ELEVATION) &&
          dev.runFilter(TE_FILTER_NORMALS);
   }
   for (int k = 0; ok && k < 3; ++k) {

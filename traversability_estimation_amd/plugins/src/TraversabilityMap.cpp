@@ -168,6 +168,13 @@ bool TraversabilityMap::setSmoothElevation(double radius) {
   return true;
 }
 
+bool TraversabilityMap::setNormalsAlgorithm(bool raster) {
+  std::lock_guard<std::mutex> lock(mutex_);
+  if (!ctx_ || !check(te_set_option(ctx_, TE_OPT_NORMALS_ALGORITHM, raster ? 1 : 0))) return false;
+  traversabilityMapInitialized_ = false;  // conservative: computeTraversability() has to run again
+  return true;
+}
+
 bool TraversabilityMap::computeTraversability() {
   std::lock_guard<std::mutex> lock(mutex_);
   if (!elevationMapInitialized_) {  // :228-231
