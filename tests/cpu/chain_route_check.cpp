@@ -8,6 +8,10 @@
 //   chain_route_check filter        reads "rows cols batch res filter radius-cells second-radius-cells generic any hole-fraction
 //                                   clustered" per line (filter: TE_FILTER_STEP, _ROUGHNESS or _NORMALS; the second radius is the step
 //                                   filter's second window), prints plan_filter_route's route: the two step passes, or the normals kernel
+//   chain_route_check params        reads "name rows cols batch res normals-cells roughness-cells step1-cells step2-cells axis kept generic
+//                                   any footprint hole-fraction clustered region i0 j0 i1 j1 filter" per line (any: the value of
+//                                   TE_OPT_FILTER_ANY_RADIUS; footprint: the mask kernel combines; region: 0 a whole-map run, 1 the
+//                                   half-open rectangle that follows; filter: 0 the chain, else TE_FILTER_*), prints the plan as `cases` does
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -172,6 +176,10 @@ static int check(const ChainRouteIn& in, const ChainRoute& r, const Case& c, con
   if (c.filter == 0 && r.normals != kNormalsGeneric && r.normals != kNormalsAny && r.whole == kWholeNone)
     req(!in.generic_kernels && in.same_rough_disc && in.axis == 2, "a shape-specialised normals kernel: same disc, axis z");
   if (c.filter == 0 && r.whole == kWholeNone) req((r.normals == kNormalsAny) == ((in.normals.any || in.rough.any)), "a disc marked any takes the route of any radius for its stage");
+  // normal_vector_positive_axis x or y: only the kernels that read the axis
+  if (in.axis != 2 && (c.filter == 0 || c.filter == kFilterNormals))
+    req(r.whole == kWholeNone && (r.normals == kNormalsGeneric || r.normals == kNormalsAny || r.normals == kNormalsRaster) && !r.fixup,
+        "axis x / y: no one-kernel chain, and k_normals, the route of any radius or raster");
   const StepRoute* st[2] = {&r.step_height, &r.step_score};
   const DiscSummary* sd[2] = {&in.step1, &in.step2};
   const ChainRect* sr[2] = {&r.r_step1, &r.r_step2};
@@ -438,6 +446,25 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  fprintf(stderr, "usage: %s cases | sweep N SEED | conditioning < lines | filter < lines\n", argv[0]);
+  if (argc >= 2 && !strcmp(argv[1], "params")) {
+    char name[128];
+    Case c;
+    int kept, generic, any, footprint, clustered, region;
+    while (scanf("%127s %d %d %d %lf %lf %lf %lf %lf %d %d %d %d %d %lf %d %d %d %d %d %d %d", name, &c.rows, &c.cols, &c.batch, &c.res, &c.rn, &c.rr, &c.s1, &c.s2,
+                 &c.axis, &kept, &generic, &any, &footprint, &c.hole_fraction, &clustered, &region, &c.rect.i0, &c.rect.j0, &c.rect.i1, &c.rect.j1,
+                 &c.filter) == 22) {
+      if (c.axis < 0 || c.axis > 2 || c.filter < 0 || c.filter > kFilterNormals) return 1;
+      if (region && !(c.rect.i0 >= 0 && c.rect.j0 >= 0 && c.rect.i0 < c.rect.i1 && c.rect.j0 < c.rect.j1 && c.rect.i1 <= c.rows && c.rect.j1 <= c.cols)) return 1;
+      c.keep = kept != 0;
+      c.generic = generic != 0;
+      c.defer = footprint != 0;
+      c.clustered = clustered != 0;
+      c.region = region != 0;
+      for (bool& a : c.any) a = any == 2;  // (option 1: only the discs build_disc refuses, which summary() marks)
+      named(name, c);
+    }
+    return 0;
+  }
+  fprintf(stderr, "usage: %s cases | sweep N SEED | conditioning < lines | filter < lines | params < lines\n", argv[0]);
   return 2;
 }

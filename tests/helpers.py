@@ -51,3 +51,19 @@ def to_te_params(capi, op):
     for f, _ in op._fields_:
         setattr(p, f, getattr(op, f))
     return p
+
+
+def orient_axis_normals(layers, ref, free):
+    """orient_horizontal_normals for any normal_vector_positive_axis: NormalVectorsFilter flips a normal only where its component
+    on that axis is negative, so where that component is zero to within the eigen-solver's noise (`free`: a flat bool array
+    of those cells, decided on the reference alone) rounding decides between n and -n.  Returns copies of the three normal
+    layers with the whole normal of every such cell turned so that the component that is largest in `ref` is positive."""
+    names = ("surface_normal_x", "surface_normal_y", "surface_normal_z")
+    r = np.stack([np.asarray(ref[k], np.float32).reshape(-1) for k in names])
+    n = np.stack([np.array(layers[k], np.float32).reshape(-1) for k in names])
+    lead = np.take_along_axis(n, np.argmax(np.abs(np.nan_to_num(r)), axis=0)[None, :], axis=0)[0]
+    sgn = np.where(np.asarray(free, bool).reshape(-1) & (lead < 0), -1.0, 1.0).astype(np.float32)
+    out = dict(layers)
+    for k, name in enumerate(names):
+        out[name] = n[k] * sgn
+    return out

@@ -165,8 +165,45 @@ def test_plugin_filter_cases_take_the_routes_they_claim(exe):
         assert {w for r in rows if r[1] == f for w in r[2].split()} == names, f
 
 
+def _param_routes(exe):
+    """(case, planned route, claimed route) of every case of tests/param_route_cases.py, asked of the chain plan (`params` mode)."""
+    from tests import param_route_cases as P
+    r = subprocess.run([exe, "params"], input="\n".join(P.route_line(c, P.elevation(c)) for c in P.ALL) + "\n", capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    got, _ = _cases(r.stdout)
+    assert len(got) == len(P.ALL)  # (the ids are distinct)
+    return [(c, got[P.case_id(c)][:6], c.route) for c in P.ALL]
+
+
+def test_param_route_cases_take_the_routes_they_claim(exe):
+    """tests/test_gpu_param_routes.py names a route for every case: it is the one the plan gives that shape, those radii, flags,
+    axis and hole counts (a region case: its region launch; the te_run_filter case: TE_FILTER_NORMALS); under axis x / y that is
+    never a one-kernel chain and always k_normals."""
+    from tests import param_route_cases as P
+    rows = _param_routes(exe)
+    wrong = [(c.name, p, w) for c, p, w in rows if p != w]
+    assert not wrong, wrong
+    axis = [(c, p) for c, p, _ in rows if c.axis != 2]
+    assert [c for c, _ in axis] == P.AXIS and all(p[0] == "none" and p[3] in ("k_normals", "any") for _, p in axis)
+
+
+def test_weight_cases_reach_every_combine_and_every_normals_kernel(exe):
+    """Between them the weight cases run every kind of combine and every normals kernel that can precede one; and every place
+    that writes the weighted sum has its cases, under both weight sets."""
+    from tests import param_route_cases as P
+    rows = [(c, p) for c, p, _ in _param_routes(exe) if c.axis == 2 and c.gap is None]
+    assert [c for c, _ in rows] == P.WEIGHTS
+    assert {p[5] for _, p in rows} == P.WEIGHT_COMBINES
+    assert {p[0] if p[0] != "none" else p[3] for _, p in rows} == P.WEIGHT_KERNELS
+    names = {c.name for c in P.WEIGHTS}
+    for site, cases in P.SITES.items():
+        assert len(cases) >= 2 and set(cases) <= names, site
+        assert {n.rsplit(", ", 1)[1] for n in cases} == {"dyadic weights", "rounding weights"}, site
+
+
 def test_under_sanitizers(tmp_path_factory):
-    """The same program with -fsanitize=address,undefined, stand-alone: the named cases, one sweep and the plugin cases."""
+    """The same program with -fsanitize=address,undefined, stand-alone: the named cases, one sweep, the plugin cases and the
+    parameter cases."""
     exe = _build(tmp_path_factory, "chain_route_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
     r = subprocess.run([exe, "cases"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -174,4 +211,6 @@ def test_under_sanitizers(tmp_path_factory):
     r = subprocess.run([exe, "sweep", "1000", "3"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "1000 cases, 0 failed checks" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
     wrong = [r for r in _plugin_routes(exe) if r[2] != r[3]]
+    assert not wrong, wrong
+    wrong = [(c.name, p, w) for c, p, w in _param_routes(exe) if p != w]
     assert not wrong, wrong
