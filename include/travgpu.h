@@ -54,10 +54,10 @@
  *                        <- the get_traversability service, TraversabilityEstimation.cpp:297-316:
  *                           GridMap::getSubmap(position, length) of the traversability map and toMessage(subMap, layers);
  *                           the rectangle of the requested layers is packed on the device and crosses PCIe in one transfer
- *   te_run_median_fill / te_download_fill_mask
+ *   te_run_median_fill / te_run_median_fill_region / te_download_fill_mask
  *                        <- gridMapFilters/MedianFillFilter (grid_map_filters; not in the reference tree: restated, see below),
  *                           the hole filling a grid_map pipeline puts in front of the chain
- *   te_run_radius_filter / te_radius_filter_stats
+ *   te_run_radius_filter / te_run_radius_filter_region / te_radius_filter_stats
  *                        <- gridMapFilters/MeanInRadiusFilter and MinInRadiusFilter (grid_map_filters; restated, see below):
  *                           the radial blur between the fill and the normals, and the conservative lower surface
  *   te_run_window_expression / te_window_expr_check / te_window_expression_stats
@@ -284,6 +284,11 @@ int te_set_layer_present(te_ctx* ctx, int layer, int present);
 
 /* Host -> device copy of any layer (e.g. surface_normal_z for TE_FILTER_SLOPE); elevation marks the context ready. */
 int te_upload_layer(te_ctx* ctx, int layer, const float* host, int map0, int nmaps);
+/* te_upload_tile for any layer that has memory: the same packed column-major h x w tile, the same checks.  TE_LAYER_ELEVATION
+ * IS te_upload_tile (the done-flags stay, counts and face flags are unknown until the next whole upload); any other layer is
+ * afterwards what te_upload_layer of the patched values leaves.  Synchronous.  With it unfiltered elevation tiles go into a
+ * holding layer, in front of te_run_median_fill_region / te_run_radius_filter_region. */
+int te_upload_layer_tile(te_ctx* ctx, int layer, const float* host_tile, int map, int row0, int col0, int h, int w);
 /* The same for a layer in GridMap's circular-buffer order: logical cell (i, j) is stored at ((i + start_row) % rows,
  * (j + start_col) % cols) (grid_map_core getBufferIndexFromIndex; start index = GridMap::getStartIndex(), non-zero after
  * GridMap::move).  The reference's filters see maps in this form: their iterators (StepFilter.cpp:112,124) hide the
@@ -854,6 +859,24 @@ int te_median_fill_params_validate(const te_median_fill_params* p);
  *     robot_slope: present; a score layer: the footprint mask is stale).
  *   A prefetch in flight that writes either layer is joined first. */
 int te_run_median_fill(te_ctx* ctx, const te_median_fill_params* p, int in_layer, int out_layer, int map0, int nmaps);
+/* The fill after in_layer changed inside the rectangle (row0, col0) + (h, w) of map `map` only (te_upload_layer_tile).
+ *   Precondition: out_layer holds te_run_median_fill(p, in_layer, out_layer) of the EARLIER contents of in_layer -- from the
+ *     whole-map call or from region calls since.  Postcondition: out_layer of that map equals, bit for bit, what the whole-map
+ *     call would write now.  Only the cells of out_rect = {row0, col0, h, w} of the rectangle written are touched: the input
+ *     rectangle grown by the reach and clamped to the map; other maps are untouched.  Reach, a Chebyshev distance:
+ *     max(r_fill + 2 k, r_existing if filter_existing_values else 0), k = num_erode_dilation_iterations (k erosions and k
+ *     dilations carry a change of V 2 k cells; cells outside the MAP do not vote, the region border is no map border).
+ *     csrc/te_region_plan.h has every stage's rectangle.  Work and traffic are those of the region: nothing is sized by the map.
+ *   te_download_fill_mask afterwards returns the whole-map mask of the updated input (the call refreshes out_rect of the stored
+ *     mask) -- TE_ERR_NOT_READY if no te_run_median_fill of that map preceded: there is no mask to refresh.
+ *   in_layer == out_layer: TE_ERR_INVALID_ARG -- in place the earlier input of the neighbouring cells is gone.  A rectangle
+ *     outside the map, a bad map: TE_ERR_INVALID_ARG as te_run_chain_region.  Every other error as te_run_median_fill.
+ *   Afterwards: out_layer == TE_LAYER_ELEVATION leaves exactly what te_upload_tile of out_rect leaves -- the done-flags stay,
+ *     face flags and hole counts are unknown until the next whole upload -- and the next call is te_run_chain_region on out_rect.
+ *     Any other out_layer: as te_upload_layer.  Asynchronous on the context's stream; a prefetch that writes either layer is
+ *     joined first.  TE_OPT_MEDIAN_ROUTE steers it as it steers the whole-map call. */
+int te_run_median_fill_region(te_ctx* ctx, const te_median_fill_params* p, int in_layer, int out_layer, int map, int row0, int col0, int h, int w,
+                              int out_rect[4]);
 /* shouldFill (4.) of the last te_run_median_fill that covered `map`: rows * cols bytes (exactly `bytes`) of 0 / 1, column-major
  * like the layers.  TE_ERR_NOT_READY before any such call and after every te_set_geometry. */
 int te_download_fill_mask(te_ctx* ctx, int map, unsigned char* out, size_t bytes);
@@ -892,6 +915,14 @@ int te_time_median_fill_samples(te_ctx* ctx, const te_median_fill_params* p, int
  *   the joining of a prefetch: as te_run_median_fill.  TE_ERR_UNSUPPORTED: the window table or the copy of the input layer does
  *   not fit in device memory. */
 int te_run_radius_filter(te_ctx* ctx, int op, double radius, int in_layer, int out_layer, int map0, int nmaps);
+/* The Mean / Min after in_layer changed inside the rectangle of map `map` only: the contract of te_run_median_fill_region with
+ * te_run_radius_filter in the place of the fill.  Reach: that of the disc table the whole-map call builds for `radius`
+ * (csrc/te_disc_table.h; 0, 1, 2, 3, 9 cells at 0, 1.5, 2.0, 3 and 9 cells of radius); the table is kept from call to call.  The
+ * sliding Mean decides order_free per workgroup of ITS tiling, which starts at out_rect's corner; a workgroup that passes adds
+ * exactly, so the bits are the whole-map call's.  te_radius_filter_stats counts the region call's workgroups.
+ * TE_OPT_RADIUS_ROUTE steers it as it steers the whole-map call. */
+int te_run_radius_filter_region(te_ctx* ctx, int op, double radius, int in_layer, int out_layer, int map, int row0, int col0, int h, int w,
+                                int out_rect[4]);
 /* Which kernel the last te_run_radius_filter ran: counts[0] = workgroups the sliding kernel settled, counts[1] = workgroups the
  * in-order gather settled (the gather kernel's own, and those of the sliding Mean that failed the predicate).  Waits for the
  * call.  TE_ERR_NOT_READY before any call. */

@@ -44,7 +44,7 @@ OPT_FILTER_ANY_RADIUS = 8  # filter discs: 0 up to 32 cells (TE_ERR_UNSUPPORTED 
 SYMBOLS = ["te_params_default", "te_params_validate", "te_device_count", "te_create", "te_destroy",
            "te_set_params", "te_get_params", "te_set_option", "te_download_face_flags", "te_set_geometry", "te_upload_elevation", "te_upload_tile", "te_download_tile",
            "te_upload_tile_async", "te_download_tile_async",
-           "te_device_ptr", "te_set_layer_present", "te_upload_layer", "te_prefetch_layers", "te_wait_prefetch", "te_upload_layer_circular", "te_download_layer_circular", "te_run_filter", "te_run_chain", "te_run_chain_region", "te_run_footprint", "te_check_footprint_paths", "te_check_footprint_paths_radius",
+           "te_device_ptr", "te_set_layer_present", "te_upload_layer", "te_upload_layer_tile", "te_prefetch_layers", "te_wait_prefetch", "te_upload_layer_circular", "te_download_layer_circular", "te_run_filter", "te_run_chain", "te_run_chain_region", "te_run_footprint", "te_check_footprint_paths", "te_check_footprint_paths_radius",
            "te_sync",
            "te_download_layer", "te_time_chain", "te_time_chain_samples", "te_last_error", "te_version",
            "te_msg_parse", "te_msg_layer", "te_msg_write", "te_upload_msg", "te_download_msg", "te_bag_find_message",
@@ -57,9 +57,9 @@ SYMBOLS = ["te_params_default", "te_params_validate", "te_device_count", "te_cre
            "te_download_cloud", "te_download_cloud_msg", "te_cloud_msg_write", "te_cloud_parse", "te_cloud_field", "te_cloud_spans",
            "te_submap_geometry", "te_download_submap", "te_download_submap_msg",
            "te_expr_check", "te_run_expression", "te_time_expression_samples",
-           "te_median_fill_params_default", "te_median_fill_params_validate", "te_run_median_fill", "te_download_fill_mask",
+           "te_median_fill_params_default", "te_median_fill_params_validate", "te_run_median_fill", "te_run_median_fill_region", "te_download_fill_mask",
            "te_time_median_fill_samples",
-           "te_run_radius_filter", "te_radius_filter_stats", "te_time_radius_filter_samples",
+           "te_run_radius_filter", "te_run_radius_filter_region", "te_radius_filter_stats", "te_time_radius_filter_samples",
            "te_window_expr_params_default", "te_window_expr_params_validate", "te_window_expr_check", "te_run_window_expression",
            "te_window_expression_stats", "te_time_window_expression_samples"]
 MSG_MAX_NAME = 64
@@ -295,6 +295,9 @@ def load():
         L.te_median_fill_params_default.argtypes = [mp]
         L.te_median_fill_params_validate.argtypes = [mp]
         L.te_run_median_fill.argtypes = [vp, mp, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.te_upload_layer_tile.argtypes = [vp, C.c_int, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.te_run_median_fill_region.argtypes = [vp, mp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.te_run_radius_filter_region.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.te_download_fill_mask.argtypes = [vp, C.c_int, C.POINTER(C.c_ubyte), C.c_size_t]
         L.te_time_median_fill_samples.argtypes = [vp, mp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.te_run_radius_filter.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -690,6 +693,13 @@ class Context:
         _check(load().te_upload_layer(self._h, LAYERS[layer] if isinstance(layer, str) else int(layer),
                                       a.ctypes.data_as(C.POINTER(C.c_float)), int(map0), a.size // per))
 
+    def upload_layer_tile(self, layer, tile, map_index, row0, col0):
+        """upload_tile for any layer that has memory (te_upload_layer_tile); tile: array of shape (w, h) == [col][row]."""
+        t = np.ascontiguousarray(tile, dtype=np.float32)
+        w, h = t.shape
+        _check(load().te_upload_layer_tile(self._h, LAYERS[layer] if isinstance(layer, str) else int(layer), t.ctypes.data_as(C.POINTER(C.c_float)),
+                                           int(map_index), int(row0), int(col0), int(h), int(w)))
+
     def prefetch_layers(self, layers):
         """{layer: array}: whole-layer uploads that run beside the calls that follow, until wait_prefetch() (te_prefetch_layers).
         The arrays are kept alive by this object until then."""
@@ -748,6 +758,15 @@ class Context:
         nmaps = self.batch - map0 if nmaps is None else nmaps
         _check(load().te_run_median_fill(self._h, C.byref(p), lid(layer), lid(layer if out is None else out), int(map0), int(nmaps)))
 
+    def run_median_fill_region(self, params, layer, out, map_index, row0, col0, h, w):
+        """te_run_median_fill_region: `out` = the fill of `layer` after it changed inside the rectangle only; `out` held the fill of
+        the earlier contents.  Returns (row0, col0, h, w) of the rectangle written."""
+        p = default_median_fill_params() if params is None else params
+        lid = lambda name: LAYERS[name] if isinstance(name, str) else int(name)
+        rect = (C.c_int * 4)()
+        _check(load().te_run_median_fill_region(self._h, C.byref(p), lid(layer), lid(out), int(map_index), int(row0), int(col0), int(h), int(w), rect))
+        return tuple(int(v) for v in rect)
+
     def download_fill_mask(self, map_index=0):
         """(cols, rows) uint8: shouldFill of the last run_median_fill that covered the map."""
         out = np.empty((self.cols, self.rows), np.uint8)
@@ -777,6 +796,16 @@ class Context:
         nmaps = self.batch - map0 if nmaps is None else nmaps
         _check(load().te_run_radius_filter(self._h, int(op), float(radius), lid(in_layer), lid(in_layer if out_layer is None else out_layer),
                                            int(map0), int(nmaps)))
+
+    def run_radius_filter_region(self, op, radius, in_layer, out_layer, map_index, row0, col0, h, w):
+        """te_run_radius_filter_region: `out_layer` = the mean / minimum of `in_layer` after it changed inside the rectangle only.
+        Returns (row0, col0, h, w) of the rectangle written."""
+        op = {"mean": RADIUS_MEAN, "min": RADIUS_MIN}.get(op, op)
+        lid = lambda name: LAYERS[name] if isinstance(name, str) else int(name)
+        rect = (C.c_int * 4)()
+        _check(load().te_run_radius_filter_region(self._h, int(op), float(radius), lid(in_layer), lid(out_layer), int(map_index), int(row0), int(col0),
+                                                  int(h), int(w), rect))
+        return tuple(int(v) for v in rect)
 
     def radius_filter_stats(self):
         """(workgroups the sliding kernel settled, workgroups the in-order gather settled) of the last run_radius_filter."""

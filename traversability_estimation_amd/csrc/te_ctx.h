@@ -222,6 +222,10 @@ int ensure_input_layer(te_ctx* c, int layer);
 int filter_input_layer(const char* who, te_ctx* c, int id, const float** out);
 int reserve_scratch(const char* who, te::DevBuf& b, size_t bytes, hipStream_t stream, const char* what);
 int note_layer_written(te_ctx* c, int out_layer);
+// ... and of the region filters: their checks for one map and one rectangle (the cells of the map behind *in / *out), and the
+// facts of te_upload_tile (the elevation) or te_upload_layer (any other layer) afterwards
+int region_filter_layers(const char* who, te_ctx* c, int in_layer, int out_layer, int map, int row0, int col0, int h, int w, const float** in, float** out);
+void note_region_written(te_ctx* c, int out_layer);
 int rebuild_tables(te_ctx* c);
 void rebuild_footprint_tables(te_ctx* c);
 int sync_tiles(te_ctx* c);  // waits for the copy streams of the streaming-tile calls

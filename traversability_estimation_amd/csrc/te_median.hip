@@ -13,6 +13,11 @@
 //                    counts are wave-wide ballots.  Same bisection, same result.
 // No atomics, no floating-point arithmetic on the values: the output is a function of the input alone.
 //
+// Region form (te_run_median_fill_region; the rectangles: te_region_plan.h): the k_*_rect mask passes run one lane per cell
+// of the rectangle their stage is planned on, in map coordinates on the same scratch; k_median_tile takes the origin of its
+// tile grid and the end of the cells it owns (the whole-map launch passes the map's), and the general route compacts the
+// cells of the rectangle alone (k_any_count / k_any_list with RECT).  Nothing in a region launch is sized by the map.
+//
 // Bounds: every global index is formed from a cell (i, j) with 0 <= i < rows, 0 <= j < cols checked where it is formed, and
 // a map index below nmaps; LDS indices lie in the staged rectangle because a listed cell is a tile cell and rr <= r.
 #include "te_median.h"
@@ -32,14 +37,7 @@ __global__ __launch_bounds__(kMaskBlock) void k_mask_valid(const float* __restri
 }
 
 // erode: a cell stays set if all of its in-map 3x3 neighbours are set; dilate: a cell is set if any of them is
-__global__ __launch_bounds__(kMaskBlock) void k_mask_morph(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int rows, int cols,
-                                                           size_t total, int erode) {
-  const size_t idx = (size_t)blockIdx.x * kMaskBlock + threadIdx.x;
-  if (idx >= total) return;
-  const size_t cells = (size_t)rows * cols;
-  const size_t cell = idx % cells;
-  const uint8_t* const s = src + (idx - cell);
-  const int i = (int)(cell % rows), j = (int)(cell / rows);
+__device__ __forceinline__ uint8_t morph_cell(const uint8_t* __restrict__ s, int rows, int cols, int i, int j, int erode) {
   const int i0 = i > 0 ? i - 1 : 0, i1 = i < rows - 1 ? i + 1 : rows - 1;
   const int j0 = j > 0 ? j - 1 : 0, j1 = j < cols - 1 ? j + 1 : cols - 1;
   int all = 1, any = 0;
@@ -49,18 +47,19 @@ __global__ __launch_bounds__(kMaskBlock) void k_mask_morph(const uint8_t* __rest
       all &= b;
       any |= b;
     }
-  dst[idx] = (uint8_t)(erode ? all : any);
+  return (uint8_t)(erode ? all : any);
 }
-
-// dst = OR of src over [x - r, x + r] clamped, x the row index (along_rows) or the column index
-__global__ __launch_bounds__(kMaskBlock) void k_mask_or(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int rows, int cols, size_t total,
-                                                        int r, int along_rows) {
+__global__ __launch_bounds__(kMaskBlock) void k_mask_morph(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int rows, int cols,
+                                                           size_t total, int erode) {
   const size_t idx = (size_t)blockIdx.x * kMaskBlock + threadIdx.x;
   if (idx >= total) return;
   const size_t cells = (size_t)rows * cols;
   const size_t cell = idx % cells;
-  const uint8_t* const s = src + (idx - cell);
-  const int i = (int)(cell % rows), j = (int)(cell / rows);
+  dst[idx] = morph_cell(src + (idx - cell), rows, cols, (int)(cell % rows), (int)(cell / rows), erode);
+}
+
+// OR of s over [x - r, x + r] clamped, x the row index (along_rows) or the column index
+__device__ __forceinline__ uint8_t or_cell(const uint8_t* __restrict__ s, int rows, int cols, int i, int j, int r, int along_rows) {
   int any = 0;
   if (along_rows) {
     const int i0 = i > r ? i - r : 0, i1 = (rows - 1 - i > r) ? i + r : rows - 1;
@@ -70,7 +69,36 @@ __global__ __launch_bounds__(kMaskBlock) void k_mask_or(const uint8_t* __restric
     const int j0 = j > r ? j - r : 0, j1 = (cols - 1 - j > r) ? j + r : cols - 1;
     for (int jj = j0; jj <= j1 && !any; ++jj) any = s[(size_t)jj * rows + i] != 0;
   }
-  dst[idx] = (uint8_t)any;
+  return (uint8_t)any;
+}
+__global__ __launch_bounds__(kMaskBlock) void k_mask_or(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int rows, int cols, size_t total,
+                                                        int r, int along_rows) {
+  const size_t idx = (size_t)blockIdx.x * kMaskBlock + threadIdx.x;
+  if (idx >= total) return;
+  const size_t cells = (size_t)rows * cols;
+  const size_t cell = idx % cells;
+  dst[idx] = or_cell(src + (idx - cell), rows, cols, (int)(cell % rows), (int)(cell / rows), r, along_rows);
+}
+
+// The same passes over one rectangle of one map (te_region_plan.h), one lane per cell of `q`, which lies in the map: src
+// and dst are that map's bytes, indexed by map cell.  what: 0 V of `in`, 1 an erosion, 2 a dilation, 3 / 4 the OR along the
+// rows / the columns.
+__global__ __launch_bounds__(kMaskBlock) void k_mask_rect(const float* __restrict__ in, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int rows,
+                                                          int cols, region::Rect q, int what, int r) {
+  const size_t k = (size_t)blockIdx.x * kMaskBlock + threadIdx.x;
+  if (k >= region::cells(q)) return;
+  int i, j;
+  region::cell_of(q, k, &i, &j);
+  if (i < 0 || i >= rows || j < 0 || j >= cols) return;  // (never: q lies in the map)
+  const size_t g = (size_t)j * rows + i;
+  uint8_t v;
+  if (what == 0)
+    v = finite_bits(float_bits(in[g])) ? 1 : 0;
+  else if (what <= 2)
+    v = morph_cell(src, rows, cols, i, j, what == 1);
+  else
+    v = or_cell(src, rows, cols, i, j, r, what == 3);
+  dst[g] = v;
 }
 
 // what a cell does, from its value and its mask byte: 0 keeps its value, 1 takes the median of its window
@@ -79,7 +107,8 @@ __device__ __forceinline__ bool needs_median(uint32_t bits, uint8_t should_fill,
 }
 
 __global__ __launch_bounds__(kTileThreads) void k_median_tile(const float* __restrict__ in, float* __restrict__ out, const uint8_t* __restrict__ mask,
-                                                              int rows, int cols, int tiles_x, int tiles_y, int r, int r_fill, int r_exist) {
+                                                              int rows, int cols, int tiles_x, int tiles_y, int r, int r_fill, int r_exist,
+                                                              int oi0, int oj0, int i_end, int j_end) {
   extern __shared__ uint32_t s_keys[];  // [h][w], w along the rows; then the list
   __shared__ int s_cnt[16];
   const int w = kTileRows + 2 * r, h = kTileCols + 2 * r;
@@ -94,7 +123,7 @@ __global__ __launch_bounds__(kTileThreads) void k_median_tile(const float* __res
   const int tid = (int)threadIdx.x;
 
   // the tile and its halo as keys; cells outside the map hold kNoKey like every cell that is not finite
-  const int gi0 = tx * kTileRows - r, gj0 = ty * kTileCols - r;
+  const int gi0 = oi0 + tx * kTileRows - r, gj0 = oj0 + ty * kTileCols - r;
   for (int e = tid; e < w * h; e += kTileThreads) {
     const int li = e % w, lj = e / w;
     const int gi = gi0 + li, gj = gj0 + lj;
@@ -105,15 +134,15 @@ __global__ __launch_bounds__(kTileThreads) void k_median_tile(const float* __res
 
   // every lane owns four tile cells (row li, columns wave + 4 q): copy through, or vote for the list
   const int li = tid & 63, wave = tid >> 6;
-  const int gi = tx * kTileRows + li;
+  const int gi = oi0 + tx * kTileRows + li;  // (the tile grid starts at (oi0, oj0) and owns cells below (i_end, j_end) <= (rows, cols))
   unsigned long long votes[4];
   bool need[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int lj = wave + 4 * q;
-    const int gj = ty * kTileCols + lj;
+    const int gj = oj0 + ty * kTileCols + lj;
     need[q] = false;
-    if (gi < rows && gj < cols) {
+    if (gi < i_end && gj < j_end) {
       const size_t g = (size_t)gj * rows + gi;
       const float v = in[g];
       need[q] = needs_median(float_bits(v), mask[g], r_exist);
@@ -152,22 +181,32 @@ __global__ __launch_bounds__(kTileThreads) void k_median_tile(const float* __res
       }
       return n;
     });
-    out[(size_t)(ty * kTileCols + cj) * rows + (tx * kTileRows + ci)] = m;
+    out[(size_t)(oj0 + ty * kTileCols + cj) * rows + (oi0 + tx * kTileRows + ci)] = m;
   }
 }
 
 // ---- the general route, one map per launch ----
 
 // copies through the cells that keep their value and counts the others per 256 cells
+// (RECT: `cells` are those of the rectangle q of the map, rows fastest, and a cell's index in the layer comes from q)
+template <bool RECT>
+__device__ __forceinline__ size_t any_cell(size_t idx, int rows, const region::Rect& q) {
+  if (!RECT) return idx;
+  int i, j;
+  region::cell_of(q, idx, &i, &j);
+  return (size_t)j * rows + i;
+}
+template <bool RECT>
 __global__ __launch_bounds__(kAnyBlock) void k_any_count(const float* __restrict__ in, float* __restrict__ out, const uint8_t* __restrict__ mask,
-                                                         size_t cells, int r_exist, unsigned* __restrict__ counts) {
+                                                         size_t cells, int r_exist, unsigned* __restrict__ counts, int rows, region::Rect q) {
   __shared__ int s_cnt[kAnyBlock / 64];
   const size_t idx = (size_t)blockIdx.x * kAnyBlock + threadIdx.x;
   bool need = false;
   if (idx < cells) {
-    const float v = in[idx];
-    need = needs_median(float_bits(v), mask[idx], r_exist);
-    if (!need) out[idx] = v;
+    const size_t g = any_cell<RECT>(idx, rows, q);
+    const float v = in[g];
+    need = needs_median(float_bits(v), mask[g], r_exist);
+    if (!need) out[g] = v;
   }
   const unsigned long long votes = __ballot(need);
   if (lane_id() == 0) s_cnt[threadIdx.x >> 6] = __popcll(votes);
@@ -204,11 +243,13 @@ __global__ __launch_bounds__(kAnyBlock) void k_any_scan(unsigned* __restrict__ c
 }
 
 // the cells that need a median, in memory order
+template <bool RECT>
 __global__ __launch_bounds__(kAnyBlock) void k_any_list(const float* __restrict__ in, const uint8_t* __restrict__ mask, size_t cells, int r_exist,
-                                                        const unsigned* __restrict__ offsets, unsigned* __restrict__ list) {
+                                                        const unsigned* __restrict__ offsets, unsigned* __restrict__ list, int rows, region::Rect q) {
   __shared__ int s_cnt[kAnyBlock / 64];
   const size_t idx = (size_t)blockIdx.x * kAnyBlock + threadIdx.x;
-  const bool need = idx < cells && needs_median(float_bits(in[idx]), mask[idx], r_exist);
+  const size_t g = idx < cells ? any_cell<RECT>(idx, rows, q) : 0;
+  const bool need = idx < cells && needs_median(float_bits(in[g]), mask[g], r_exist);
   const unsigned long long votes = __ballot(need);
   const int wave = (int)(threadIdx.x >> 6);
   if (lane_id() == 0) s_cnt[wave] = __popcll(votes);
@@ -217,7 +258,7 @@ __global__ __launch_bounds__(kAnyBlock) void k_any_list(const float* __restrict_
   unsigned pos = offsets[blockIdx.x];
   for (int k = 0; k < wave; ++k) pos += (unsigned)s_cnt[k];
   pos += (unsigned)__popcll(votes & ((1ull << lane_id()) - 1ull));
-  if (pos < cells) list[pos] = (unsigned)idx;  // (pos < the total <= cells: the prefix sums say so)
+  if (pos < cells) list[pos] = (unsigned)g;  // (pos < the total <= cells: the prefix sums say so)
 }
 
 // one wavefront per listed cell; n_list: the total behind the counts
@@ -276,25 +317,61 @@ hipError_t launch(const Args& a, const Plan& p, hipStream_t stream) {
 
   if (p.route == kRouteTile) {
     hipLaunchKernelGGL(k_median_tile, dim3((unsigned)p.blocks), dim3(kTileThreads), p.lds_bytes, stream, a.in, a.out, a.mask, a.rows, a.cols, p.tiles_x,
-                       p.tiles_y, p.r, a.r_fill, a.r_exist);
+                       p.tiles_y, p.r, a.r_fill, a.r_exist, 0, 0, a.rows, a.cols);
     return hipGetLastError();
   }
   const size_t nb = any_blocks(cells);
   if (nb > 0x7fffffffull) return hipErrorInvalidValue;
   const size_t want_waves = cells < 8192 ? cells : 8192;  // (the list is at most `cells` long; a grid-stride loop takes the rest)
   const unsigned any_grid = (unsigned)((want_waves + kAnyBlock / 64 - 1) / (kAnyBlock / 64));
+  const region::Rect whole = {0, 0, a.rows, a.cols};
   for (int m = 0; m < a.nmaps; ++m) {
     const float* const in = a.in + (size_t)m * cells;
     float* const out = a.out + (size_t)m * cells;
     const uint8_t* const mask = a.mask + (size_t)m * cells;
-    hipLaunchKernelGGL(k_any_count, dim3((unsigned)nb), dim3(kAnyBlock), 0, stream, in, out, mask, cells, a.r_exist, a.any_counts);
+    hipLaunchKernelGGL(k_any_count<false>, dim3((unsigned)nb), dim3(kAnyBlock), 0, stream, in, out, mask, cells, a.r_exist, a.any_counts, a.rows, whole);
     hipLaunchKernelGGL(k_any_scan, dim3(1), dim3(kAnyBlock), 0, stream, a.any_counts, nb);
-    hipLaunchKernelGGL(k_any_list, dim3((unsigned)nb), dim3(kAnyBlock), 0, stream, in, mask, cells, a.r_exist, a.any_counts, a.any_list);
+    hipLaunchKernelGGL(k_any_list<false>, dim3((unsigned)nb), dim3(kAnyBlock), 0, stream, in, mask, cells, a.r_exist, a.any_counts, a.any_list, a.rows, whole);
     hipLaunchKernelGGL(k_median_any, dim3(any_grid), dim3(kAnyBlock), 0, stream, in, out, a.rows, a.cols, a.any_list, a.any_counts + nb, a.r_fill, a.r_exist);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+// One map: a.in / a.out / a.mask / a.tmp point at that map's cells (a.nmaps is not read); every launch is sized by a
+// rectangle of p.
+hipError_t launch_region(const Args& a, const RegionPlan& p, hipStream_t stream) {
+  const region::Rect out = p.out;
+  if (region::cells(out) == 0 || out.i0 < 0 || out.j0 < 0 || out.i1 > a.rows || out.j1 > a.cols) return hipErrorInvalidValue;
+  const auto mask_pass = [&](const uint8_t* src, uint8_t* dst, const region::Rect& q, int what) {
+    hipLaunchKernelGGL(k_mask_rect, dim3(blocks_of(region::cells(q), kMaskBlock)), dim3(kMaskBlock), 0, stream, a.in, src, dst, a.rows, a.cols, q, what, a.r_fill);
+  };
+  mask_pass(nullptr, a.tmp[0], mask_stage_rect(p, 0), 0);
+  int cur = 0;
+  for (int k = 0; k < 2 * a.iterations; ++k) {
+    mask_pass(a.tmp[cur], a.tmp[cur ^ 1], mask_stage_rect(p, k + 1), k < a.iterations ? 1 : 2);
+    cur ^= 1;
+  }
+  mask_pass(a.tmp[cur], a.tmp[cur ^ 1], row_or_rect(p), 3);
+  mask_pass(a.tmp[cur ^ 1], a.mask, out, 4);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+
+  if (p.k.route == kRouteTile) {
+    hipLaunchKernelGGL(k_median_tile, dim3((unsigned)p.k.blocks), dim3(kTileThreads), p.k.lds_bytes, stream, a.in, a.out, a.mask, a.rows, a.cols, p.k.tiles_x,
+                       p.k.tiles_y, p.k.r, a.r_fill, a.r_exist, out.i0, out.j0, out.i1, out.j1);
+    return hipGetLastError();
+  }
+  const size_t oc = region::cells(out), nb = p.any_blocks;
+  if (nb > 0x7fffffffull) return hipErrorInvalidValue;
+  const size_t want_waves = oc < 8192 ? oc : 8192;
+  const unsigned any_grid = (unsigned)((want_waves + kAnyBlock / 64 - 1) / (kAnyBlock / 64));
+  hipLaunchKernelGGL(k_any_count<true>, dim3((unsigned)nb), dim3(kAnyBlock), 0, stream, a.in, a.out, a.mask, oc, a.r_exist, a.any_counts, a.rows, out);
+  hipLaunchKernelGGL(k_any_scan, dim3(1), dim3(kAnyBlock), 0, stream, a.any_counts, nb);
+  hipLaunchKernelGGL(k_any_list<true>, dim3((unsigned)nb), dim3(kAnyBlock), 0, stream, a.in, a.mask, oc, a.r_exist, a.any_counts, a.any_list, a.rows, out);
+  hipLaunchKernelGGL(k_median_any, dim3(any_grid), dim3(kAnyBlock), 0, stream, a.in, a.out, a.rows, a.cols, a.any_list, a.any_counts + nb, a.r_fill, a.r_exist);
+  return hipGetLastError();
 }
 
 }  // namespace median

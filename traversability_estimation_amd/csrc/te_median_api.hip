@@ -43,6 +43,38 @@ int note_layer_written(te_ctx* c, int out_layer) {
   return TE_OK;
 }
 
+// The checks of a region filter (te_run_median_fill_region, te_run_radius_filter_region) in the order of the whole-map
+// calls (te_layer_call.h) for the one map, then the two of their own: the layers differ, the rectangle lies in the map.
+// On success *in / *out point at the cells of `map`.  Nothing is touched before every check has passed.
+int region_filter_layers(const char* who, te_ctx* c, int in_layer, int out_layer, int map, int row0, int col0, int h, int w, const float** in, float** out) {
+  if (!c->have_geo) return fail(TE_ERR_NOT_READY, "%s: geometry not set", who);
+  if (out_layer < 0 || out_layer >= TE_LAYER_COUNT) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
+  if (map < 0 || map >= c->geo.batch) return fail(TE_ERR_INVALID_ARG, "%s: map %d of batch %d", who, map, c->geo.batch);
+  const float* src = nullptr;
+  if (const int rc = filter_input_layer(who, c, in_layer, &src)) return rc;
+  if (out_layer != TE_LAYER_ROBOT_SLOPE && !layer_ptr(c, out_layer))
+    return fail(TE_ERR_INVALID_ARG, "%s: the output layer %d has no memory yet", who, out_layer);
+  if (in_layer == out_layer)
+    return fail(TE_ERR_INVALID_ARG, "%s: in_layer == out_layer (%d): a region call reads the neighbours of the rectangle as they were before "
+                                    "the filter, and in place their earlier input is gone; keep the unfiltered values in a layer of their own", who, in_layer);
+  if (!region::valid_rect(c->geo.rows, c->geo.cols, row0, col0, h, w))
+    return fail(TE_ERR_INVALID_ARG, "%s: rectangle (%d,%d)+(%d,%d) outside %dx%d", who, row0, col0, h, w, c->geo.rows, c->geo.cols);
+  if (const int rc = ensure_input_layer(c, out_layer)) return rc;  // (robot_slope exists from its first write on)
+  const size_t cells = (size_t)c->geo.rows * c->geo.cols;
+  *in = src + cells * (size_t)map;
+  *out = layer_ptr(c, out_layer) + cells * (size_t)map;
+  return TE_OK;
+}
+
+// the context's facts after a region filter wrote `out_layer`: the elevation as te_upload_tile leaves it (the done-flags stay,
+// counts and face flags are unknown: te_ctx_state.h, elevation_tile_written), any other layer as te_upload_layer
+void note_region_written(te_ctx* c, int out_layer) {
+  if (out_layer == TE_LAYER_ELEVATION)
+    c->st.elevation_tile_written();
+  else
+    c->st.layer_written(out_layer, CtxState::kUploaded);
+}
+
 }  // namespace shim
 }  // namespace te
 
@@ -150,6 +182,59 @@ int te_run_median_fill(te_ctx* c, const te_median_fill_params* p, int in_layer, 
   if (c->fill_mask_valid.size() != (size_t)c->geo.batch) c->fill_mask_valid.assign((size_t)c->geo.batch, 0);
   for (int m = map0; m < map0 + nmaps; ++m) c->fill_mask_valid[(size_t)m] = 1;
   return note_layer_written(c, out_layer);
+}
+
+int te_run_median_fill_region(te_ctx* c, const te_median_fill_params* p, int in_layer, int out_layer, int map, int row0, int col0, int h, int w, int out_rect[4]) {
+  const char* const who = "te_run_median_fill_region";
+  if (!c || !p || !out_rect) return fail(TE_ERR_INVALID_ARG, "%s: NULL", who);
+  if (const int rc = te_median_fill_params_validate(p)) return rc;
+  TraceRange tr(who);
+  CtxLock lk(c, /*beside_prefetch*/ true, bit(in_layer) | bit(out_layer));
+  if (c->have_geo) HIP_TRY(hipSetDevice(c->device));
+  const float* in = nullptr;
+  float* out = nullptr;
+  if (const int rc = region_filter_layers(who, c, in_layer, out_layer, map, row0, col0, h, w, &in, &out)) return rc;
+  const int rows = c->geo.rows, cols = c->geo.cols;
+  const size_t cells = (size_t)rows * cols, batch_cells = cells * (size_t)c->geo.batch;
+  const int r_fill = median::radius_cells(p->fill_hole_radius, c->geo.res, rows, cols);
+  int r_exist = -1;
+  if (p->filter_existing_values) {
+    r_exist = median::radius_cells(p->existing_value_radius, c->geo.res, rows, cols);
+    if (r_exist == 0) r_exist = -1;
+  }
+  const region::Rect dirty = {row0, col0, row0 + h, col0 + w};
+  const median::RegionPlan plan = median::region_plan(rows, cols, r_fill, r_exist, p->num_erode_dilation_iterations, c->opt_median_route, dirty);
+  if (plan.k.route == median::kRouteAny && cells >= ((size_t)1 << 32))
+    return fail(TE_ERR_UNSUPPORTED, "%s: a window radius of %d cells takes the general kernel, which lists cells in 32 bits: %zu cells per map are too many", who, plan.k.r, cells);
+  // the stored mask and the scratch masks are addressed by map cell: the allocations of the whole-map call, made here if
+  // none preceded (the mask then holds nothing to refresh: fill_mask_valid stays as it is); the list is sized by the region
+  te_ctx::LayerMem& m = c->lmem;
+  if (const int rc = reserve_scratch(who, m.median_mask, batch_cells, c->stream, "the fill mask")) return rc;
+  if (const int rc = reserve_scratch(who, m.median_tmp, 2 * batch_cells, c->stream, "the scratch masks")) return rc;
+  if (plan.k.route == median::kRouteAny)
+    if (const int rc = reserve_scratch(who, m.median_any, (plan.any_blocks + 1 + region::cells(plan.out)) * sizeof(unsigned), c->stream, "the list of cells")) return rc;
+  median::Args a;
+  memset(&a, 0, sizeof(a));
+  a.in = in;
+  a.out = out;
+  a.mask = m.median_mask.as<uint8_t>() + cells * (size_t)map;
+  a.tmp[0] = m.median_tmp.as<uint8_t>();
+  a.tmp[1] = m.median_tmp.as<uint8_t>() + batch_cells;
+  a.any_counts = m.median_any.as<unsigned>();
+  a.any_list = a.any_counts ? a.any_counts + plan.any_blocks + 1 : nullptr;
+  a.rows = rows;
+  a.cols = cols;
+  a.nmaps = 1;
+  a.r_fill = r_fill;
+  a.r_exist = r_exist;
+  a.iterations = p->num_erode_dilation_iterations;
+  HIP_TRY(median::launch_region(a, plan, c->stream));
+  out_rect[0] = plan.out.i0;
+  out_rect[1] = plan.out.j0;
+  out_rect[2] = region::height(plan.out);
+  out_rect[3] = region::width(plan.out);
+  note_region_written(c, out_layer);
+  return TE_OK;
 }
 
 int te_download_fill_mask(te_ctx* c, int map, unsigned char* out, size_t bytes) {

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "te_median_plan.h"
+#include "te_region_plan.h"
 
 namespace te {
 namespace median {
@@ -29,6 +30,9 @@ inline size_t any_blocks(size_t cells) { return (cells + kAnyBlock - 1) / kAnyBl
 
 // the launches of one call in order on `stream`: the mask passes, then the route the plan names
 hipError_t launch(const Args& a, const Plan& p, hipStream_t stream);
+// te_run_median_fill_region: the same on the rectangles of `p`, for ONE map -- in, out, mask and tmp point at that map's cells
+// (tmp: rows * cols bytes each), any_counts holds p.any_blocks + 1 entries and any_list as many as p.out has cells
+hipError_t launch_region(const Args& a, const RegionPlan& p, hipStream_t stream);
 
 }  // namespace median
 }  // namespace te

@@ -13,6 +13,9 @@
 //                    column segment, a run is a difference of two prefixes; taken only by a workgroup for whose cells
 //                    order_free() holds (decided over every cell it can read, ties included, before it stages anything),
 //                    otherwise the workgroup runs gather_cell for its centres.  The branch is uniform over the workgroup.
+// Both kernels take the rectangle of centres they own (region::Rect): the whole map, or the output rectangle of
+// te_run_radius_filter_region (te_region_plan.h), whose workgroup tiles start at its corner.  What a centre READS is bounded by
+// the map alone.
 // Built with -ffp-contract=off like every source of the library.
 #include "te_radius_launch.h"
 
@@ -102,13 +105,13 @@ __device__ float gather_cell(const Geo& g, const Window& w, const float* __restr
 }
 
 template <int OP>
-__global__ __launch_bounds__(kThreads) void k_radius_gather(Geo g, Window w, const float* __restrict__ in, float* __restrict__ out,
+__global__ __launch_bounds__(kThreads) void k_radius_gather(Geo g, Window w, region::Rect own, const float* __restrict__ in, float* __restrict__ out,
                                                            unsigned long long* __restrict__ counts) {
   const size_t mo = (size_t)blockIdx.z * g.rows * g.cols;
-  const int i = blockIdx.x * kTX + threadIdx.x;
+  const int i = own.i0 + blockIdx.x * kTX + threadIdx.x;
   if (threadIdx.x == 0 && threadIdx.y == 0) atomicAdd(&counts[1], 1ull);
-  if (i >= g.rows) return;
-  for (long long j = (long long)blockIdx.y * kWaves + threadIdx.y; j < g.cols; j += (long long)gridDim.y * kWaves)
+  if (i >= own.i1) return;  // (own lies in the map)
+  for (long long j = (long long)own.j0 + (long long)blockIdx.y * kWaves + threadIdx.y; j < own.j1; j += (long long)gridDim.y * kWaves)
     out[mo + (size_t)j * g.rows + i] = gather_cell<OP>(g, w, in + mo, i, (int)j);
 }
 
@@ -118,14 +121,14 @@ constexpr int kCPT = kTY / kWaves;  // centres per lane
 
 // `seg`: rows of a staged segment (te_radius_plan.h: segment_len); levels: of the Min tables; log2n: of the predicate
 template <int OP>
-__global__ __launch_bounds__(kThreads) void k_radius_slide(Geo g, Window w, int seg, int levels, int log2n, const float* __restrict__ in_all,
+__global__ __launch_bounds__(kThreads) void k_radius_slide(Geo g, Window w, region::Rect own, int seg, int levels, int log2n, const float* __restrict__ in_all,
                                                           float* __restrict__ out_all, unsigned long long* __restrict__ counts) {
   extern __shared__ double lds_d[];
   const size_t mo = (size_t)blockIdx.z * g.rows * g.cols;
   const float* __restrict__ in = in_all + mo;
   float* __restrict__ out = out_all + mo;
   const int tid = threadIdx.y * kTX + threadIdx.x;
-  const int i0 = blockIdx.x * kTX, j0 = blockIdx.y * kTY;
+  const int i0 = own.i0 + blockIdx.x * kTX, j0 = own.j0 + blockIdx.y * kTY;  // (own lies in the map: i0 < rows, j0 < cols)
   const int i = i0 + threadIdx.x;
   const int H = w.hw0;
   const int sa = i0 - H < 0 ? 0 : i0 - H;
@@ -154,7 +157,7 @@ __global__ __launch_bounds__(kThreads) void k_radius_slide(Geo g, Window w, int 
       for (int c = 0; c < kCPT; ++c) {
         const int j = j0 + threadIdx.y + c * kWaves;
         const int b = j > jp ? j - jp : jp - j;
-        if (i >= g.rows || j >= g.cols || b > w.R) continue;
+        if (i >= own.i1 || j >= own.j1 || b > w.R) continue;
         const int h = w.tab[b];
         if (h < 0) continue;
         const int lo = (i - h < sa ? sa : i - h) - sa, hi = (i + h >= sb ? sb - 1 : i + h) - sa;  // lo <= i - sa <= hi
@@ -165,7 +168,7 @@ __global__ __launch_bounds__(kThreads) void k_radius_slide(Geo g, Window w, int 
 #pragma unroll
     for (int c = 0; c < kCPT; ++c) {
       const int j = j0 + threadIdx.y + c * kWaves;
-      if (i >= g.rows || j >= g.cols) continue;
+      if (i >= own.i1 || j >= own.j1) continue;
       Acc a = {0.0, 0, mn[c]};
       for (int t = 0; t < w.n_ties; ++t) take_tie<kMin>(a, g, w, in, i, j, t);
       out[(size_t)j * g.rows + i] = a.mn;
@@ -218,7 +221,7 @@ __global__ __launch_bounds__(kThreads) void k_radius_slide(Geo g, Window w, int 
 #pragma unroll 1
     for (int c = 0; c < kCPT; ++c) {
       const int j = j0 + threadIdx.y + c * kWaves;
-      if (i < g.rows && j < g.cols) out[(size_t)j * g.rows + i] = gather_cell<kMean>(g, w, in, i, j);
+      if (i < own.i1 && j < own.j1) out[(size_t)j * g.rows + i] = gather_cell<kMean>(g, w, in, i, j);
     }
     return;
   }
@@ -270,7 +273,7 @@ __global__ __launch_bounds__(kThreads) void k_radius_slide(Geo g, Window w, int 
     for (int c = 0; c < kCPT; ++c) {
       const int j = j0 + threadIdx.y + c * kWaves;
       const int b = j > jp ? j - jp : jp - j;
-      if (i >= g.rows || j >= g.cols || b > w.R) continue;
+      if (i >= own.i1 || j >= own.j1 || b > w.R) continue;
       const int h = w.tab[b];
       if (h < 0) continue;
       const int lo = (i - h < sa ? sa : i - h) - sa, hi = (i + h >= sb ? sb - 1 : i + h) - sa;  // 0 <= lo <= hi < n
@@ -281,7 +284,7 @@ __global__ __launch_bounds__(kThreads) void k_radius_slide(Geo g, Window w, int 
 #pragma unroll
   for (int c = 0; c < kCPT; ++c) {
     const int j = j0 + threadIdx.y + c * kWaves;
-    if (i >= g.rows || j >= g.cols) continue;
+    if (i >= own.i1 || j >= own.j1) continue;
     Acc a = {sum[c], cnt[c], 0.0f};
     for (int t = 0; t < w.n_ties; ++t) take_tie<kMean>(a, g, w, in, i, j, t);
     out[(size_t)j * g.rows + i] = result<kMean>(a);
@@ -290,21 +293,32 @@ __global__ __launch_bounds__(kThreads) void k_radius_slide(Geo g, Window w, int 
 
 }  // namespace
 
-hipError_t launch(const Geo& g, const Window& w, const Args& a, const Plan& p, hipStream_t stream) {
-  if (a.nmaps <= 0) return hipSuccess;
-  const dim3 grid(p.grid_x, p.grid_y, (unsigned)a.nmaps), block(kTX, kWaves);
+static hipError_t launch_on(const Geo& g, const Window& w, const Args& a, const Plan& p, const region::Rect& own, unsigned nmaps, hipStream_t stream) {
+  const dim3 grid(p.grid_x, p.grid_y, nmaps), block(kTX, kWaves);
   if (p.route == kRouteSlide) {
     if (a.op == kMean)
-      hipLaunchKernelGGL(k_radius_slide<kMean>, grid, block, p.lds_bytes, stream, g, w, p.seg, p.levels, p.log2n, a.in, a.out, a.counts);
+      hipLaunchKernelGGL(k_radius_slide<kMean>, grid, block, p.lds_bytes, stream, g, w, own, p.seg, p.levels, p.log2n, a.in, a.out, a.counts);
     else
-      hipLaunchKernelGGL(k_radius_slide<kMin>, grid, block, p.lds_bytes, stream, g, w, p.seg, p.levels, p.log2n, a.in, a.out, a.counts);
+      hipLaunchKernelGGL(k_radius_slide<kMin>, grid, block, p.lds_bytes, stream, g, w, own, p.seg, p.levels, p.log2n, a.in, a.out, a.counts);
   } else {
     if (a.op == kMean)
-      hipLaunchKernelGGL(k_radius_gather<kMean>, grid, block, 0, stream, g, w, a.in, a.out, a.counts);
+      hipLaunchKernelGGL(k_radius_gather<kMean>, grid, block, 0, stream, g, w, own, a.in, a.out, a.counts);
     else
-      hipLaunchKernelGGL(k_radius_gather<kMin>, grid, block, 0, stream, g, w, a.in, a.out, a.counts);
+      hipLaunchKernelGGL(k_radius_gather<kMin>, grid, block, 0, stream, g, w, own, a.in, a.out, a.counts);
   }
   return hipGetLastError();
+}
+
+hipError_t launch(const Geo& g, const Window& w, const Args& a, const Plan& p, hipStream_t stream) {
+  if (a.nmaps <= 0) return hipSuccess;
+  const region::Rect whole = {0, 0, g.rows, g.cols};
+  return launch_on(g, w, a, p, whole, (unsigned)a.nmaps, stream);
+}
+
+hipError_t launch_region(const Geo& g, const Window& w, const Args& a, const RegionPlan& p, hipStream_t stream) {
+  const region::Rect& o = p.out;
+  if (o.i0 < 0 || o.j0 < 0 || o.i0 >= o.i1 || o.j0 >= o.j1 || o.i1 > g.rows || o.j1 > g.cols) return hipErrorInvalidValue;
+  return launch_on(g, w, a, p.k, o, 1u, stream);
 }
 
 }  // namespace radius

@@ -115,6 +115,41 @@ int te_run_radius_filter(te_ctx* c, int op, double rad, int in_layer, int out_la
   return note_layer_written(c, out_layer);
 }
 
+int te_run_radius_filter_region(te_ctx* c, int op, double rad, int in_layer, int out_layer, int map, int row0, int col0, int h, int w, int out_rect[4]) {
+  const char* const who = "te_run_radius_filter_region";
+  if (!c || !out_rect) return fail(TE_ERR_INVALID_ARG, "%s: NULL", who);
+  if (const int rc = check_args(who, op, rad, false)) return rc;
+  TraceRange tr(who);
+  CtxLock lk(c, /*beside_prefetch*/ true, bit(in_layer) | bit(out_layer));
+  if (c->have_geo) HIP_TRY(hipSetDevice(c->device));
+  const float* in = nullptr;
+  float* out = nullptr;
+  if (const int rc = region_filter_layers(who, c, in_layer, out_layer, map, row0, col0, h, w, &in, &out)) return rc;
+  const int rows = c->geo.rows, cols = c->geo.cols;
+  // (the table of the last call with this radius and resolution is kept: nothing is rebuilt from tick to tick)
+  Call call;
+  radius::Shape shape;
+  if (const int rc = window_table(who, c, radius::bounded_radius(rad, c->geo.res, rows, cols), &call.w, &shape)) return rc;
+  const region::Rect dirty = {row0, col0, row0 + h, col0 + w};
+  const radius::RegionPlan plan = radius::region_plan(op, rows, cols, shape, c->opt_radius_route, dirty);
+  HIP_TRY(c->cmem.radius_counts.once(2 * sizeof(unsigned long long)));
+  call.a.in = in;
+  call.a.out = out;
+  call.a.counts = c->cmem.radius_counts.as<unsigned long long>();
+  call.a.nmaps = 1;
+  call.a.op = op;
+  c->radius_counts_valid = false;
+  HIP_TRY(hipMemsetAsync(call.a.counts, 0, 2 * sizeof(unsigned long long), c->stream));
+  HIP_TRY(radius::launch_region(c->geo, call.w, call.a, plan, c->stream));
+  c->radius_counts_valid = true;
+  out_rect[0] = plan.out.i0;
+  out_rect[1] = plan.out.j0;
+  out_rect[2] = region::height(plan.out);
+  out_rect[3] = region::width(plan.out);
+  note_region_written(c, out_layer);
+  return TE_OK;
+}
+
 int te_radius_filter_stats(te_ctx* c, uint64_t counts[2]) {
   if (!c || !counts) return fail(TE_ERR_INVALID_ARG, "te_radius_filter_stats: NULL");
   CtxLock lk(c);

@@ -5,6 +5,7 @@
 
 #include "te_internal.h"
 #include "te_radius_plan.h"
+#include "te_region_plan.h"
 
 namespace te {
 namespace radius {
@@ -26,6 +27,8 @@ struct Args {
 };
 
 hipError_t launch(const Geo& g, const Window& w, const Args& a, const Plan& p, hipStream_t stream);
+// te_run_radius_filter_region: the centres of p.out of ONE map -- in and out point at that map's cells (a.nmaps is not read)
+hipError_t launch_region(const Geo& g, const Window& w, const Args& a, const RegionPlan& p, hipStream_t stream);
 
 }  // namespace radius
 }  // namespace te

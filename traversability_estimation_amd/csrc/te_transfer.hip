@@ -71,6 +71,23 @@ int tile_streams(te_ctx* c) {
 
 }  // namespace
 
+int te_upload_layer_tile(te_ctx* c, int layer, const float* host_tile, int map, int row0, int col0, int h, int w) {
+  if (layer == TE_LAYER_ELEVATION) return te_upload_tile(c, host_tile, map, row0, col0, h, w);
+  if (!c || !host_tile) return fail(TE_ERR_INVALID_ARG, "te_upload_layer_tile: NULL");
+  CtxLock lk(c);
+  if (const int rc = check_tile(c, "te_upload_layer_tile", map, row0, col0, h, w)) return rc;
+  if (layer < 0 || layer >= TE_LAYER_COUNT || (layer != TE_LAYER_ROBOT_SLOPE && !layer_ptr(c, layer)))
+    return fail(TE_ERR_INVALID_ARG, "te_upload_layer_tile: bad layer %d", layer);
+  if (const int rc = ensure_input_layer(c, layer)) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  float* dst = layer_ptr(c, layer) + (size_t)map * c->geo.rows * c->geo.cols + (size_t)col0 * c->geo.rows + row0;
+  HIP_TRY(hipMemcpy2DAsync(dst, (size_t)c->geo.rows * sizeof(float), host_tile, (size_t)h * sizeof(float), (size_t)h * sizeof(float), (size_t)w,
+                           hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->st.layer_written(layer, CtxState::kUploaded);
+  return TE_OK;
+}
+
 int te_download_tile(te_ctx* c, int layer, int map, int row0, int col0, int h, int w, float* host_tile) {
   if (!c || !host_tile) return fail(TE_ERR_INVALID_ARG, "te_download_tile: NULL");
   CtxLock lk(c);
