@@ -748,6 +748,68 @@ int te_download_submap_msg(te_ctx* ctx, const te_msg_info* info_in, double req_x
                            double req_len_y, int n_layers, const int* layers, const char* const* names, int n_basic,
                            const char* const* basic_names, te_submap_info* info, void* out, size_t cap, size_t* written);
 
+/* ---- moving a resident map: GridMap::move for the device layers ----
+ * elevation_mapping's map is robot-centric: it move()s whenever the robot has crossed a cell.  te_move_map shifts what the
+ * context holds instead of dropping it (te_set_geometry to a new position drops every result and the caller uploads the
+ * whole map again).  Device layers stay in logical order; there is no start index.
+ *
+ * Semantics = GridMap::move's index shift (RESTATED from memory of grid_map_core, not pinned: DESIGN.md section 7), per axis:
+ *     s = (requested - held) / resolution;  shift = (int)(s + 0.5 * sign(s))      (halves round away from zero; |s| is
+ *     clamped to 2^30 cells before the cast);  new position = held + shift * resolution -- the ALIGNED shift, not the request.
+ *   A map moved by +k cells in x holds its old cell i at i + k (x(i) = ax - resolution * i); likewise y and the columns.
+ *   A zero shift on both axes changes nothing, not even the position (n_rects = 0, results_kept = 1).
+ *   A shift of at least the map's extent on an axis exposes every cell (all_exposed = 1, one rectangle: the map).
+ * rects: up to four rectangles (row0, col0, h, w), in this order, each present only where it applies:
+ *   1. exposed (rect_exposed = 1): the full-width band of rows whose source lies outside the old window;
+ *   2. exposed: the band of such columns, without the rows of 1. -- no cell is in both;
+ *   3. trailing line (rect_exposed = 0): on a row shift, the one-row line of the map along the border OPPOSITE to band 1;
+ *   4. trailing line: on a column shift, the one-column line along the border opposite to band 2.
+ *   The exposed cells hold NaN (0 in the stored fill mask) until the caller uploads them.  The trailing lines carry no new
+ *   data, but cells near them were interior before the move: their filter discs and footprints reached cells that have
+ *   left the map, and the reference clips every iterator to the map, so their results are stale.  te_run_chain_region on the
+ *   line re-filters exactly the cells within reach of that border.  Lines may cross each other and touch the exposed bands.
+ * results_kept (CAVEAT 1, tie radii): a cell exactly on a disc's circle is decided from the rounded double positions of the
+ *   cells, centre by centre, so results computed at the old position can differ from results at the new one by a whole step.
+ *   If one of the five discs of the parameters (normals, roughness, both step windows, footprint radius + offset) has cells
+ *   on its circle -- the classification of te_disc.h that routes the kernels, erring towards "tie" -- or no parameters are
+ *   set, or TE_OPT_NORMALS_ALGORITHM = 1 (region runs are refused there), results_kept = 0: the layers are still shifted and
+ *   the inputs valid, but the context is as after a whole te_upload_elevation; upload the exposed rectangles and run
+ *   te_run_chain.  The move then costs a whole-map run but no whole-map upload.  Otherwise results_kept = 1 (CAVEAT 2, the
+ *   trailing lines): the context is as after te_upload_tile -- chain, footprint and present flags stay -- and every
+ *   rectangle, trailing lines included, must be handed to te_run_chain_region (an exposed one after its te_upload_tile)
+ *   before the results are read; the untraversable mask counts as not built until a whole pass or a path check rebuilds it.
+ *   CAVEAT 3, the footprint layer: the footprint checks' own windows, circle(3 res) of checkForSlope / checkForRoughness and
+ *   circle(2.5 res) of checkForStep, have cells on their circle at EVERY resolution, so isTraversableForFilters -- and with it
+ *   traversability_footprint -- of a few cells depends on the position whatever the parameters (measured on the CPU oracle
+ *   alone: 10 of 49 152 cells of a 256 x 192 window moved by (+7, -3) cells).  The four chain layers do not.  A caller that
+ *   wants the footprint layer of the new position bit for bit passes the rectangles to te_run_chain_region WITHOUT the
+ *   footprint flags and runs te_run_footprint once behind them: a whole-map footprint pass, no whole-map chain and no
+ *   whole-map upload (capi's Context.refresh_moved does so).  With the footprint flags on the region
+ *   runs the layer is the old position's on those cells.
+ * te_move_map moves EVERY layer that has memory (all TE_LAYER_*, borrowed holding layers included, robot_slope and the polygon
+ * layers once they exist), every map of the batch (one position), the stored fill mask of te_run_median_fill and the
+ * untraversable mask.  Each layer is shifted out of place into a scratch of one layer of one map -- no workgroup reads what
+ * another of the same launch writes -- and copied back; the scratch is allocated by the first move that needs it and freed
+ * with the layers.  Asynchronous on the context's stream, in order with the launches before and after; a prefetch in flight
+ * is joined first.  A captured whole-map launch is dropped (as te_set_geometry with the shape held does) and captured anew.
+ *   TE_ERR_NOT_READY: no geometry.  TE_ERR_BAD_PARAM: a position that is not finite.  TE_ERR_UNSUPPORTED, before anything is
+ *   written or changed: the scratch does not fit in device memory, or the layers hold 2^31 cells or more (all maps) -- such
+ *   maps are REFUSED, not moved (the kernel's index arithmetic is 64-bit all the same).  `info` may be NULL. */
+typedef struct te_move_info {
+  int32_t shift_rows, shift_cols;   /* cells; old cell (i, j) is now (i + shift_rows, j + shift_cols) */
+  int32_t n_rects, results_kept, all_exposed, _pad0;
+  double pos_x, pos_y;              /* the position held after the move */
+  int32_t rects[4][4];              /* (row0, col0, h, w) */
+  int32_t rect_exposed[4];          /* 1: exposed cells (upload them), 0: a trailing line (re-filter only) */
+} te_move_info;
+/* Host only, no context: the plan of one move of a rows x cols map held at (pos_x, pos_y).  params = NULL: results_kept = 0.
+ * (TE_OPT_NORMALS_ALGORITHM is a context option: te_move_map clears results_kept under raster, this call cannot know.)
+ * TE_ERR_INVALID_ARG: NULL out, rows or cols below 1, a resolution that is not positive and finite, a held position that is
+ * not finite; TE_ERR_BAD_PARAM: a requested position that is not finite. */
+int te_move_geometry(int rows, int cols, double resolution, double pos_x, double pos_y, double new_x, double new_y,
+                     const te_params* params, te_move_info* out);
+int te_move_map(te_ctx* ctx, double new_x, double new_y, te_move_info* info);
+
 /* ---- gridMapFilters/MathExpressionFilter with ANY expression (robot_filter_parameter.yaml:29-33) ----
  * te_run_chain / TE_FILTER_COMBINE run the weighted sum of the three scores (te_params: w_scale, w_slope, w_step, w_rough) and
  * keep their fused path.  te_run_expression evaluates any expression of the language below over the resident layers into

@@ -56,6 +56,7 @@ SYMBOLS = ["te_params_default", "te_params_validate", "te_device_count", "te_cre
            "te_download_occupancy", "te_download_occupancy_msg", "te_occupancy_msg_write", "te_occupancy_parse",
            "te_download_cloud", "te_download_cloud_msg", "te_cloud_msg_write", "te_cloud_parse", "te_cloud_field", "te_cloud_spans",
            "te_submap_geometry", "te_download_submap", "te_download_submap_msg",
+           "te_move_geometry", "te_move_map",
            "te_expr_check", "te_run_expression", "te_time_expression_samples",
            "te_median_fill_params_default", "te_median_fill_params_validate", "te_run_median_fill", "te_run_median_fill_region", "te_download_fill_mask",
            "te_time_median_fill_samples",
@@ -142,6 +143,19 @@ class TeSubmapInfo(C.Structure):
     """te_submap_info: what GridMap::getSubmap makes of a request -- the rectangle in the map and the submap's own geometry."""
     _fields_ = [("ok", C.c_int32), ("row0", C.c_int32), ("col0", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
                 ("pos_x", C.c_double), ("pos_y", C.c_double), ("length_x", C.c_double), ("length_y", C.c_double)]
+
+
+class TeMoveInfo(C.Structure):
+    """te_move_info: the plan of one move -- the shift in cells, the position held afterwards, the rectangles to refresh
+    (row0, col0, h, w; rect_exposed 1: upload its cells first, 0: a trailing line, re-filter only) and whether the results
+    computed at the old position were kept."""
+    _fields_ = [("shift_rows", C.c_int32), ("shift_cols", C.c_int32), ("n_rects", C.c_int32), ("results_kept", C.c_int32),
+                ("all_exposed", C.c_int32), ("_pad0", C.c_int32), ("pos_x", C.c_double), ("pos_y", C.c_double),
+                ("rects", (C.c_int32 * 4) * 4), ("rect_exposed", C.c_int32 * 4)]
+
+    def rectangles(self):
+        """[((row0, col0, h, w), exposed)] in the plan's order."""
+        return [(tuple(int(v) for v in self.rects[k]), bool(self.rect_exposed[k])) for k in range(self.n_rects)]
 
 
 # encoding name -> (channels, bytes per channel): the encodings te_image_parse accepts
@@ -288,6 +302,9 @@ def load():
         L.te_submap_geometry.argtypes = [C.c_int, C.c_int] + [C.c_double] * 7 + [smp]
         L.te_download_submap.argtypes = [vp, C.c_int] + [C.c_double] * 4 + [C.c_int, ip, smp, vp, C.c_size_t]
         L.te_download_submap_msg.argtypes = [vp, C.POINTER(TeMsgInfo)] + [C.c_double] * 4 + [C.c_int, ip, cpp, C.c_int, cpp, smp, vp, C.c_size_t, szp]
+        if "TRAVGPU_LIB" not in os.environ or hasattr(L, "te_move_map"):  # (an A/B library of an earlier round lacks the pair)
+            L.te_move_geometry.argtypes = [C.c_int, C.c_int] + [C.c_double] * 5 + [pp, C.POINTER(TeMoveInfo)]
+            L.te_move_map.argtypes = [vp, C.c_double, C.c_double, C.POINTER(TeMoveInfo)]
         L.te_expr_check.argtypes = [C.c_char_p, C.POINTER(TeExprInfo)]
         L.te_run_expression.argtypes = [vp, C.c_char_p, C.c_int]
         L.te_time_expression_samples.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
@@ -504,6 +521,15 @@ def submap_geometry(rows, cols, res, pos, position, length):
     info = TeSubmapInfo()
     _check(load().te_submap_geometry(int(rows), int(cols), float(res), float(pos[0]), float(pos[1]), float(position[0]),
                                      float(position[1]), float(length[0]), float(length[1]), C.byref(info)))
+    return info
+
+
+def move_geometry(rows, cols, res, pos, new_pos, params=None):
+    """te_move_geometry: the plan of moving a rows x cols map held at `pos` to `new_pos` (host only, no context): a TeMoveInfo.
+    params=None: results_kept is 0."""
+    info = TeMoveInfo()
+    _check(load().te_move_geometry(int(rows), int(cols), float(res), float(pos[0]), float(pos[1]), float(new_pos[0]), float(new_pos[1]),
+                                   None if params is None else C.byref(params), C.byref(info)))
     return info
 
 
@@ -745,6 +771,33 @@ class Context:
 
     def run_footprint(self):
         _check(load().te_run_footprint(self._h))
+
+    def move_map(self, x, y):
+        """te_move_map: GridMap::move of every resident layer to the position (x, y), rounded to whole cells; asynchronous like
+        run_chain.  Returns the TeMoveInfo: hand it to refresh_moved."""
+        info = TeMoveInfo()
+        _check(load().te_move_map(self._h, float(x), float(y), C.byref(info)))
+        return info
+
+    def refresh_moved(self, info, flags=0, tiles=None, map_index=0):
+        """The loop a caller writes after move_map, for one map: for each rectangle of `info`, upload its tile if the rectangle
+        is exposed and a tile is given (tiles[k]: the array of shape (w, h) for rectangle k, or None), then run_chain_region on
+        it -- trailing lines included.  With results_kept == 0 (a tie radius, raster normals) the tiles are uploaded and the
+        whole chain runs instead.  A zero-shift move has nothing to refresh.
+        The footprint flags are served by ONE whole-map footprint pass behind the region runs, not by the region runs: the
+        footprint checks' own windows, circle(3 res) and circle(2.5 res), have cells on their circle at every resolution, so
+        the untraversable mask is decided anew at the new position (include/travgpu.h, caveat 3)."""
+        rects = info.rectangles()
+        fp = flags & (RUN_FOOTPRINT | RUN_FOOTPRINT_MEMO)
+        for k, ((row0, col0, h, w), exposed) in enumerate(rects):
+            if exposed and tiles is not None and tiles[k] is not None:
+                self.upload_tile(tiles[k], map_index, row0, col0)
+            if info.results_kept:
+                self.run_chain_region(map_index, row0, col0, h, w, flags & ~fp)
+        if rects and not info.results_kept:
+            self.run_chain(flags)
+        elif rects and fp:
+            self.run_footprint()
 
     def run_expression(self, text, out="traversability"):
         """te_run_expression: `out` = text over the resident layers (any MathExpressionFilter expression of the language in

@@ -98,6 +98,9 @@ struct te_ctx {
     te::DevBuf radius_copy;
     // te_run_window_expression (te_window_expr.hip): the copy of the input layer a call with in_layer == out_layer reads
     te::DevBuf window_copy;
+    // te_move_map (te_move.hip): one float layer of one map, the out-of-place target of a shift (te_slab.h: move_scratch_bytes);
+    // allocated by the first move that needs it
+    te::DevBuf move_scratch;
     // the circular footprint at any reach (te_footprint_any.hip): its tables and its prefix-sum scratch ([batch][cols][rows + 1]
     // doubles, then as many unsigned), allocated when the footprint tables are rebuilt for that route; c->fp.any_* point into them
     struct FpAny {
@@ -228,6 +231,8 @@ int region_filter_layers(const char* who, te_ctx* c, int in_layer, int out_layer
 void note_region_written(te_ctx* c, int out_layer);
 int rebuild_tables(te_ctx* c);
 void rebuild_footprint_tables(te_ctx* c);
+// destroys the captured whole-map launches: their kernel arguments (tables, grids, the geometry) are baked in
+void drop_graph(te_ctx* c);
 int sync_tiles(te_ctx* c);  // waits for the copy streams of the streaming-tile calls
 int run_whole_locked(te_ctx* c, unsigned flags);
 }  // namespace shim

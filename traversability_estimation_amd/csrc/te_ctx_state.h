@@ -49,6 +49,20 @@ struct CtxState {
   void layers_freed() { *this = CtxState(); }
   // te_set_geometry, also with the shape held: resolution or position may have changed under the results.
   void geometry_set() { drop_results(); }
+  // te_move_map has shifted every layer by whole cells and holds the new position (te_move_plan.h).  results_kept: no disc
+  // of the parameters has a tie cell, so what was computed at the old position stands wherever no cell left or entered a disc
+  // -- the region contract, as after elevation_tile_written: the caller hands the exposed rectangles and the trailing lines
+  // to te_run_chain_region.  The count and the face flags (built per 64 x 4 tile, which a shift misaligns) are unknown, and
+  // the untraversable mask counts as not built until a whole pass or a path check rebuilds it.  Without results_kept the
+  // elevation is still shifted and valid, and everything computed from it is dropped: as a whole upload.
+  void map_moved(bool results_kept) {
+    if (!results_kept) {
+      elevation_replaced();
+      return;
+    }
+    count_unknown();
+    mask_done_ = false;
+  }
 
   // ---- the elevation layer ---------------------------------------------------------------------------------------------
   // Every cell of one or more maps was replaced (whole uploads, an image, a median fill into the layer).  Called once the

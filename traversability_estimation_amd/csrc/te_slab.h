@@ -15,6 +15,11 @@ namespace te {
 constexpr int kSlabGuardRows = 48;
 constexpr int kSlabFloatLayers = 13;
 
+// Beside the slab: the scratch of te_move_map (te_move.hip), one float layer of ONE map whatever the batch.  It is a buffer of
+// its own (te_ctx::LayerMem::move_scratch), allocated by the first move and freed with the slab: no kernel marches over it, so
+// it needs no guard rows, and contexts that never move do not pay for it.
+inline size_t move_scratch_bytes(int rows, int cols) { return (size_t)rows * (size_t)cols * sizeof(float); }
+
 struct SlabPart {
   size_t off, bytes;
 };

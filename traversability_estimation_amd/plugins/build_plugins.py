@@ -18,6 +18,7 @@ MEDIAN_TEST = os.path.join(HERE, "plugin_median_test")
 RADIUS_FILTER_TEST = os.path.join(HERE, "plugin_radius_filter_test")
 WINDOW_EXPRESSION_TEST = os.path.join(HERE, "plugin_window_expression_test")
 RASTER_TEST = os.path.join(HERE, "plugin_raster_test")
+MOVE_TEST = os.path.join(HERE, "plugin_move_test")
 SRCS = ["src/DeviceMap.cpp", "src/SlopeFilter.cpp", "src/StepFilter.cpp", "src/RoughnessFilter.cpp",
         "src/FusedChainFilter.cpp", "src/SurfaceNormalsFilter.cpp", "src/MedianFillFilter.cpp", "src/MeanInRadiusFilter.cpp", "src/MinInRadiusFilter.cpp", "src/SlidingWindowMathExpressionFilter.cpp", "src/TraversabilityMap.cpp", "stubs/pluginlib/registry.cpp"]
 
@@ -95,6 +96,12 @@ def build(verbose=False):
     # SurfaceNormalsFilter and FusedChainFilter with `algorithm: raster` (tests/test_plugins_raster.py)
     cmd = cmd[:cmd.index("-o")] + ["-o", RASTER_TEST]
     cmd[cmd.index(os.path.join(HERE, "test", "plugin_window_expression_test.cpp"))] = os.path.join(HERE, "test", "plugin_raster_test.cpp")
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    # TraversabilityMap::moveMap (tests/test_plugins_move.py)
+    cmd = cmd[:cmd.index("-o")] + ["-o", MOVE_TEST]
+    cmd[cmd.index(os.path.join(HERE, "test", "plugin_raster_test.cpp"))] = os.path.join(HERE, "test", "plugin_move_test.cpp")
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

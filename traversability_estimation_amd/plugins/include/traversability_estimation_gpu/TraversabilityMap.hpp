@@ -51,6 +51,17 @@ class TraversabilityMap {
    *  not step * height.  An image carries no layer "robot_slope". */
   bool setElevationFromImage(const sensor_msgs::Image& image, double resolution, const grid_map::Position& position,
                              double minHeight, double maxHeight);
+  /*! GridMap::move on the device (te_move_map): the resident map follows the robot to `position`, rounded to whole cells,
+   *  without a new setElevationMap.  `info` receives the plan: the shift, the position held afterwards and up to four
+   *  rectangles (row0, col0, h, w).  exposedCells[k], for a rectangle k with info.rect_exposed[k] == 1, points to its h x w new
+   *  elevation cells, column-major like a GridMap block (nullptr, or no array at all: the cells stay NaN).  The loop of
+   *  INTEGRATION.md "Incremental updates of a resident map" then runs: each strip is uploaded and, if the traversability map
+   *  was computed, every rectangle -- the trailing border lines included -- is re-filtered (te_run_chain_region), or the
+   *  whole chain runs when info.results_kept == 0 (a tie radius, raster normals); a circular footprint layer that existed is
+   *  rebuilt by one whole-map footprint pass (include/travgpu.h, caveat 3); the polygon layers are dropped.  A zero shift
+   *  changes nothing.  false + error(), and nothing moved, without an elevation map or with setFillHoles / setSmoothElevation
+   *  in force (the strips would enter the elevation layer raw: use the region forms of the C API). */
+  bool moveMap(const grid_map::Position& position, te_move_info& info, const float* const* exposedCells = nullptr);
   /*! computeTraversability (:202-237): the filter chain; false if no elevation map has been set. */
   bool computeTraversability();
   /*! Hole filling in front of the chain (gridMapFilters/MedianFillFilter on the device, te_run_median_fill): with parameters

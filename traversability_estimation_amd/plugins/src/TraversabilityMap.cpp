@@ -144,6 +144,42 @@ bool TraversabilityMap::setElevationFromImage(const sensor_msgs::Image& image, d
   return true;
 }
 
+bool TraversabilityMap::moveMap(const grid_map::Position& position, te_move_info& info, const float* const* exposedCells) {
+  std::lock_guard<std::mutex> lock(mutex_);
+  info = te_move_info();
+  if (!ctx_ || !elevationMapInitialized_) {
+    error_ = "moveMap: no elevation map";
+    ROS_ERROR("Traversability Estimation: Elevation map is not initialized!");
+    return false;
+  }
+  if (fillHoles_ || smoothRadius_ > 0.0) {
+    error_ = "moveMap: not with setFillHoles / setSmoothElevation (the strips would enter the elevation layer raw)";
+    ROS_ERROR("TraversabilityMap (MI355X): %s", error_.c_str());
+    return false;
+  }
+  if (!check(te_move_map(ctx_, position.x(), position.y(), &info))) return false;
+  if (info.n_rects == 0) return true;  // a zero shift: nothing has changed
+  const grid_map::Position held = {{info.pos_x, info.pos_y}};
+  geometry_.setGeometry(geometry_.getLength(), geometry_.getResolution(), held);
+  polygonLayers_ = false;
+  const bool computed = traversabilityMapInitialized_, footprint = footprintLayer_;
+  // until the loop is through, the map is not one to answer from
+  traversabilityMapInitialized_ = footprintLayer_ = false;
+  for (int k = 0; k < info.n_rects; ++k) {
+    const int32_t* r = info.rects[k];
+    if (info.rect_exposed[k] && exposedCells && exposedCells[k] && !check(te_upload_tile(ctx_, exposedCells[k], 0, r[0], r[1], r[2], r[3])))
+      return false;
+    if (computed && info.results_kept && !check(te_run_chain_region(ctx_, 0, 0, r[0], r[1], r[2], r[3]))) return false;
+  }
+  if (computed && !info.results_kept && !check(te_run_chain(ctx_, 0))) return false;
+  traversabilityMapInitialized_ = computed;
+  if (computed && footprint) {
+    if (!check(te_run_footprint(ctx_))) return false;
+    footprintLayer_ = true;
+  }
+  return true;
+}
+
 bool TraversabilityMap::setFillHoles(const te_median_fill_params* params) {
   std::lock_guard<std::mutex> lock(mutex_);
   if (!params) {
