@@ -863,9 +863,35 @@ int te_expr_check(const char* text, te_expr_info* info);
  *     path, the chain's state and te_get_params are untouched.  te_run_footprint and the path checks then read the new values;
  *     the next te_run_chain writes the weighted sum again.
  *   A prefetch in flight that writes a layer the text reads (or the traversability layer) is joined first.
- *   Limit: te_run_chain_region still recombines its region with the weights.  With a general expression run the region without
- *     TE_RUN_FOOTPRINT, then te_run_expression, then te_run_footprint. */
+ *   On a dirty rectangle: te_run_expression_region evaluates a text without a reduction on a rectangle of one map, and
+ *     te_run_chain_region_expression is te_run_chain_region with the text in the place of the weighted sum -- the whole tick in
+ *     one call, the footprint half included (below). */
 int te_run_expression(te_ctx* ctx, const char* text, int out_layer);
+/* traversability = text on the cells of the rectangle (row0, col0) + (h, w) of map `map`; every other cell of every map is
+ * untouched.  The evaluator is the whole-map call's, cell by cell: the cells carry the bits te_run_expression would write now.
+ * The reach is 0: a cell's value is read from the same cell of the input layers.
+ *   out_layer must be TE_LAYER_TRAVERSABILITY (TE_ERR_INVALID_ARG otherwise, as te_run_expression).
+ *   TE_ERR_UNSUPPORTED + message: a text with a reduction -- a map-wide meanOfFinites changes with one cell and then changes
+ *     every cell: run te_run_expression --; a text that reads the traversability layer itself -- "what the whole-map call
+ *     would write now" is not defined for a rectangle recomputed in place.
+ *   TE_ERR_NOT_READY: no geometry, an input layer that does not exist yet (as te_run_expression).  TE_ERR_INVALID_ARG: a bad
+ *     map, a rectangle outside the map (as te_run_chain_region).  A failed call leaves every layer as it was.
+ *   Afterwards the context is what te_upload_layer_tile(TE_LAYER_TRAVERSABILITY, the rectangle, the same values) leaves: the
+ *     layer counts as written from outside, the done-flags stay.  Asynchronous on the context's stream; a prefetch in flight
+ *     that writes a layer the text reads (or the traversability layer) is joined first. */
+int te_run_expression_region(te_ctx* ctx, const char* text, int out_layer, int map, int row0, int col0, int h, int w);
+/* The whole tick in one locked call: exactly te_run_chain_region(flags, map, row0, col0, h, w), except that the combined layer
+ * on the rectangle the chain recombines -- the region grown by the chain's reach, clamped to the map -- is `text` by the
+ * rules of te_run_expression_region instead of the weighted sum.  The footprint half (TE_RUN_FOOTPRINT[_MEMO]) runs behind it
+ * on the same cells as in te_run_chain_region; its precondition (a complete footprint layer) is the same, and it plans without
+ * a bound of the combined layer (the route of any reach), the layer being an expression's.
+ *   text == NULL: te_run_chain_region.  The refusals of te_run_expression_region (a reduction, a text that reads the
+ *   traversability layer: TE_ERR_UNSUPPORTED; a missing input layer: TE_ERR_NOT_READY) are checked before anything is launched.
+ *   Refused under TE_OPT_NORMALS_ALGORITHM = 1 like te_run_chain_region; every other error as te_run_chain_region.
+ *   Afterwards: what te_run_chain_region(flags, ...) followed by te_upload_layer_tile(TE_LAYER_TRAVERSABILITY) leaves.
+ *   Precondition as for the region chain: the combined layer outside that rectangle holds te_run_expression(text) of scores
+ *   that have not changed since. */
+int te_run_chain_region_expression(te_ctx* ctx, unsigned flags, const char* text, int map, int row0, int col0, int h, int w);
 /* Measurement aid: `iters` te_run_expression launches of `text`, one HIP event pair each, ms[k] = device time of the k-th
  * (after `warmup` untimed ones), like te_time_chain_samples.  text = NULL times te_run_filter(TE_FILTER_COMBINE) the same way: the
  * weighted sum's own kernel, the yardstick of tools/expr_bench.py. */
@@ -1051,6 +1077,26 @@ int te_window_expr_check(const char* text, int in_layer, te_expr_info* info);
  *   joining of a prefetch: as te_run_radius_filter.  TE_ERR_BAD_PARAM: the parameters, the window, the expression.
  *   TE_ERR_UNSUPPORTED: valid EigenLab that is not built; the copy of the input layer does not fit in device memory. */
 int te_run_window_expression(te_ctx* ctx, const te_window_expr_params* p, const char* text, int in_layer, int out_layer, int map0, int nmaps);
+/* The window expression after in_layer changed inside the rectangle (row0, col0) + (h, w) of map `map` only
+ * (te_upload_layer_tile): the contract of te_run_median_fill_region with the expression in the place of the fill.
+ *   Precondition: out_layer holds te_run_window_expression(p, text, in_layer, out_layer) of the EARLIER contents of in_layer --
+ *     from the whole-map call or from region calls since.  Postcondition: out_layer of that map equals, bit for bit, what the
+ *     whole-map call would write now.  Only the cells of out_rect = {row0, col0, h, w} of the rectangle written are touched:
+ *     the input rectangle grown by the reach and clamped to the map; other maps are untouched.
+ *   Reach, a Chebyshev distance: m = (w - 1) / 2 cells under all four edge handlings.  A cell reads its window and nothing
+ *     else.  Under TE_EDGE_MEAN the padding of a clipped window is meanOfFinites(B), and B -- the window clipped to the map --
+ *     lies inside the window: the reach stays m.  Under TE_EDGE_INSIDE the unvisited frame inside out_rect gets its NaN again;
+ *     with compute_empty_cells == 0 a cell whose own input is not finite gets NaN.  The region border is no map border: every
+ *     read is checked against the map.  csrc/te_region_plan.h has the plan; the tiling starts at out_rect's corner.  Work and
+ *     traffic are those of the region: no copy of the input layer, nothing is sized by the map.
+ *   in_layer == out_layer: TE_ERR_INVALID_ARG -- in place the earlier input of the neighbouring cells is gone.  A rectangle
+ *     outside the map, a bad map: TE_ERR_INVALID_ARG as te_run_chain_region.  Every other error as te_run_window_expression.
+ *   Afterwards: out_layer == TE_LAYER_ELEVATION leaves exactly what te_upload_tile of out_rect leaves, and the next call is
+ *     te_run_chain_region on out_rect.  Any other out_layer: as te_upload_layer_tile.  Asynchronous on the context's stream; a
+ *     prefetch that writes either layer is joined first.  TE_OPT_WINDOW_EXPR_ROUTE steers it as it steers the whole-map call
+ *     (both routes, the same bits), and te_window_expression_stats then counts the region call's workgroups. */
+int te_run_window_expression_region(te_ctx* ctx, const te_window_expr_params* p, const char* text, int in_layer, int out_layer, int map, int row0,
+                                    int col0, int h, int w, int out_rect[4]);
 /* Which route the last te_run_window_expression took: counts[0] = workgroups the separable route settled, counts[1] =
  * workgroups that walked their windows directly.  Waits for the call.  TE_ERR_NOT_READY before any call. */
 int te_window_expression_stats(te_ctx* ctx, uint64_t counts[2]);

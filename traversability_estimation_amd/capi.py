@@ -57,11 +57,11 @@ SYMBOLS = ["te_params_default", "te_params_validate", "te_device_count", "te_cre
            "te_download_cloud", "te_download_cloud_msg", "te_cloud_msg_write", "te_cloud_parse", "te_cloud_field", "te_cloud_spans",
            "te_submap_geometry", "te_download_submap", "te_download_submap_msg",
            "te_move_geometry", "te_move_map",
-           "te_expr_check", "te_run_expression", "te_time_expression_samples",
+           "te_expr_check", "te_run_expression", "te_run_expression_region", "te_run_chain_region_expression", "te_time_expression_samples",
            "te_median_fill_params_default", "te_median_fill_params_validate", "te_run_median_fill", "te_run_median_fill_region", "te_download_fill_mask",
            "te_time_median_fill_samples",
            "te_run_radius_filter", "te_run_radius_filter_region", "te_radius_filter_stats", "te_time_radius_filter_samples",
-           "te_window_expr_params_default", "te_window_expr_params_validate", "te_window_expr_check", "te_run_window_expression",
+           "te_window_expr_params_default", "te_window_expr_params_validate", "te_window_expr_check", "te_run_window_expression", "te_run_window_expression_region",
            "te_window_expression_stats", "te_time_window_expression_samples"]
 MSG_MAX_NAME = 64
 OCCUPANCY_MAX_LAYERS = CLOUD_MAX_LAYERS = SUBMAP_MAX_LAYERS = 16
@@ -307,6 +307,8 @@ def load():
             L.te_move_map.argtypes = [vp, C.c_double, C.c_double, C.POINTER(TeMoveInfo)]
         L.te_expr_check.argtypes = [C.c_char_p, C.POINTER(TeExprInfo)]
         L.te_run_expression.argtypes = [vp, C.c_char_p, C.c_int]
+        L.te_run_expression_region.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.te_run_chain_region_expression.argtypes = [vp, C.c_uint, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         L.te_time_expression_samples.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
         mp = C.POINTER(TeMedianFillParams)
         L.te_median_fill_params_default.argtypes = [mp]
@@ -325,6 +327,7 @@ def load():
         L.te_window_expr_params_validate.argtypes = [wp]
         L.te_window_expr_check.argtypes = [C.c_char_p, C.c_int, C.POINTER(TeExprInfo)]
         L.te_run_window_expression.argtypes = [vp, wp, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.te_run_window_expression_region.argtypes = [vp, wp, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.te_window_expression_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.te_time_window_expression_samples.argtypes = [vp, wp, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.te_last_error.restype = C.c_char_p
@@ -779,23 +782,29 @@ class Context:
         _check(load().te_move_map(self._h, float(x), float(y), C.byref(info)))
         return info
 
-    def refresh_moved(self, info, flags=0, tiles=None, map_index=0):
+    def refresh_moved(self, info, flags=0, tiles=None, map_index=0, expression=None):
         """The loop a caller writes after move_map, for one map: for each rectangle of `info`, upload its tile if the rectangle
         is exposed and a tile is given (tiles[k]: the array of shape (w, h) for rectangle k, or None), then run_chain_region on
         it -- trailing lines included.  With results_kept == 0 (a tie radius, raster normals) the tiles are uploaded and the
         whole chain runs instead.  A zero-shift move has nothing to refresh.
         The footprint flags are served by ONE whole-map footprint pass behind the region runs, not by the region runs: the
         footprint checks' own windows, circle(3 res) and circle(2.5 res), have cells on their circle at every resolution, so
-        the untraversable mask is decided anew at the new position (include/travgpu.h, caveat 3)."""
+        the untraversable mask is decided anew at the new position (include/travgpu.h, caveat 3).
+        expression: the combined layer is this text (run_expression) instead of the weighted sum -- the region runs are
+        run_chain_region_expression, and a whole chain is followed by run_expression before the footprint pass."""
         rects = info.rectangles()
         fp = flags & (RUN_FOOTPRINT | RUN_FOOTPRINT_MEMO)
         for k, ((row0, col0, h, w), exposed) in enumerate(rects):
             if exposed and tiles is not None and tiles[k] is not None:
                 self.upload_tile(tiles[k], map_index, row0, col0)
             if info.results_kept:
-                self.run_chain_region(map_index, row0, col0, h, w, flags & ~fp)
+                self.run_chain_region_expression(expression, map_index, row0, col0, h, w, flags & ~fp)
         if rects and not info.results_kept:
-            self.run_chain(flags)
+            self.run_chain(flags if expression is None else flags & ~fp)
+            if expression is not None:
+                self.run_expression(expression)
+                if fp:
+                    self.run_footprint()
         elif rects and fp:
             self.run_footprint()
 
@@ -803,6 +812,19 @@ class Context:
         """te_run_expression: `out` = text over the resident layers (any MathExpressionFilter expression of the language in
         include/travgpu.h); asynchronous like run_chain.  The context is then what upload_layer(out, the same values) leaves."""
         _check(load().te_run_expression(self._h, str(text).encode(), LAYERS[out] if isinstance(out, str) else int(out)))
+
+    def run_expression_region(self, text, map_index, row0, col0, h, w, out="traversability"):
+        """te_run_expression_region: `out` = text on the cells of the rectangle of one map, the bits of run_expression; a text
+        with a reduction or one that reads `out` is refused (TE_ERR_UNSUPPORTED).  The context is then what
+        upload_layer_tile(out, the same values) leaves."""
+        _check(load().te_run_expression_region(self._h, str(text).encode(), LAYERS[out] if isinstance(out, str) else int(out), int(map_index), int(row0),
+                                               int(col0), int(h), int(w)))
+
+    def run_chain_region_expression(self, text, map_index, row0, col0, h, w, flags=0):
+        """te_run_chain_region_expression: run_chain_region with `text` in the place of the weighted sum on the rectangle the
+        chain recombines, the footprint half (flags) behind it: the whole tick in one call.  text=None: run_chain_region."""
+        _check(load().te_run_chain_region_expression(self._h, int(flags), None if text is None else str(text).encode(), int(map_index), int(row0),
+                                                     int(col0), int(h), int(w)))
 
     def run_median_fill(self, params=None, layer="elevation", out=None, map0=0, nmaps=None):
         """gridMapFilters/MedianFillFilter on the device (te_run_median_fill): `out` (default: `layer`, in place) = the filled `layer`."""
@@ -877,6 +899,16 @@ class Context:
         nmaps = self.batch - map0 if nmaps is None else nmaps
         _check(load().te_run_window_expression(self._h, C.byref(p), str(text).encode(), lid(in_layer),
                                                lid(in_layer if out_layer is None else out_layer), int(map0), int(nmaps)))
+
+    def run_window_expression_region(self, text, params, in_layer, out_layer, map_index, row0, col0, h, w):
+        """te_run_window_expression_region: `out_layer` = the window expression of `in_layer` after it changed inside the rectangle
+        only; `out_layer` held the expression of the earlier contents.  Returns (row0, col0, h, w) of the rectangle written."""
+        p = window_expr_params(**params) if isinstance(params, dict) else params
+        lid = lambda name: LAYERS[name] if isinstance(name, str) else int(name)
+        rect = (C.c_int * 4)()
+        _check(load().te_run_window_expression_region(self._h, C.byref(p), str(text).encode(), lid(in_layer), lid(out_layer), int(map_index), int(row0),
+                                                      int(col0), int(h), int(w), rect))
+        return tuple(int(v) for v in rect)
 
     def window_expression_stats(self):
         """(workgroups the separable route settled, workgroups that walked directly) of the last run_window_expression."""

@@ -199,6 +199,10 @@ struct te_ctx {
 };
 
 namespace te {
+namespace expr {
+struct Program;  // te_expr.h
+struct Args;     // te_expr_launch.h
+}  // namespace expr
 namespace shim {
 // joins a running prefetch (caller holds c->mu); its result stays in c->prefetch_rc until te_wait_prefetch reports it
 void finish_prefetch_locked(te_ctx* c);
@@ -229,6 +233,13 @@ int note_layer_written(te_ctx* c, int out_layer);
 // facts of te_upload_tile (the elevation) or te_upload_layer (any other layer) afterwards
 int region_filter_layers(const char* who, te_ctx* c, int in_layer, int out_layer, int map, int row0, int col0, int h, int w, const float** in, float** out);
 void note_region_written(te_ctx* c, int out_layer);
+// te_expr_api.hip, the rectangle form of te_run_expression, shared with te_run_chain_region_expression: compile and refuse
+// (a reduction, a text that reads the traversability layer: TE_ERR_UNSUPPORTED) without a context; bind the layers
+// (TE_ERR_NOT_READY: one is missing) without a launch; launch on a rectangle of one map and record the facts of
+// te_upload_layer_tile(TE_LAYER_TRAVERSABILITY).  The last two under the caller's lock.
+int region_expression_program(const char* who, const char* text, te::expr::Program* p);
+int region_expression_args(const char* who, te_ctx* c, const te::expr::Program& p, te::expr::Args* a);
+int region_expression_launch(const char* who, te_ctx* c, const te::expr::Program& p, const te::expr::Args& a, int map, int row0, int col0, int h, int w);
 int rebuild_tables(te_ctx* c);
 void rebuild_footprint_tables(te_ctx* c);
 // destroys the captured whole-map launches: their kernel arguments (tables, grids, the geometry) are baked in

@@ -118,6 +118,13 @@ struct CtxState {
     layer_touched(TE_LAYER_TRAVERSABILITY);
     layer_written(TE_LAYER_TRAVERSABILITY, kUploaded);
   }
+  // te_run_expression_region, and the expression of te_run_chain_region_expression: as te_upload_layer_tile of the
+  // traversability layer with the same values -- the layer counts as written from outside (no bound: the footprint pass
+  // behind it takes the route of any reach), and the done-flags stay as they are.
+  void expression_wrote_traversability_region() {
+    layer_touched(TE_LAYER_TRAVERSABILITY);
+    layer_written(TE_LAYER_TRAVERSABILITY, kUploaded);
+  }
   // A prefetch was joined: `mask` the layers it wrote, `ok` whether all of them arrived.  An elevation in it counts as
   // replaced, arrived or torn -- a torn one is no elevation: the next chain needs a complete upload; the caller counts an
   // arrived one next (elevation_counted / count_unknown).  What an arrived layer changes for later calls it changes only

@@ -4,6 +4,7 @@
 //                  wave-uniform and the dispatch is a scalar branch per instruction; the operand stack lives in LDS as
 //                  [slot][thread] (a runtime-indexed register array would go to scratch).  The top of the stack stays in
 //                  registers: the shipped weighted sum touches LDS three times per group.
+//   k_expr_rect    te_run_expression_region: the same evaluation on a rectangle of one map, no reductions.
 //   k_expr_reduce  only for a program with reductions: evaluates every reduction argument per cell, folds a workgroup's
 //                  kReduceSpan cells in a fixed order and writes one partial (double sum, float min / max, count) per block.
 //   k_expr_finish  folds the partials of one (map, reduction) in a fixed order and writes the float32 result, which k_expr_map
@@ -82,6 +83,30 @@ __global__ __launch_bounds__(kThreads) void k_expr_map(const Program p, const Ar
   }
 }
 
+// te_run_expression_region: the cells [i0, i0 + h) x [j0, j0 + w) of one map (a.in / a.out point at the layers' first map,
+// `base` is the map's offset in cells).  The rows of the rectangle run along the lanes, four consecutive rows of one column per
+// thread -- the same run<4> as k_expr_map, element by element the same operations: the whole-map call's bits.  A column of the
+// rectangle starts at any float boundary: 4-byte aligned loads and stores.  No reductions (the caller refuses them).
+__global__ __launch_bounds__(kThreads) void k_expr_rect(const Program p, const Args a, size_t base, int rows, int i0, int j0, int h, int w) {
+  __shared__ float4a stk[kMaxStack - 1][kThreads];
+  LdsStack st{stk, threadIdx.x};
+  const size_t per_col = ((size_t)h + 3) >> 2, ngroups = per_col * (size_t)w;
+  for (size_t q = (size_t)blockIdx.x * kThreads + threadIdx.x; q < ngroups; q += (size_t)gridDim.x * kThreads) {
+    const size_t col = q / per_col;
+    const int di = (int)(q - col * per_col) << 2;
+    const int n = h - di >= 4 ? 4 : h - di;
+    const size_t g = base + ((size_t)j0 + col) * (size_t)rows + (size_t)(i0 + di);
+    const Source<float4u> src{a, g, n, nullptr, {0, 0, 0, 0}};
+    const Vec<4> v = run<4>(p, 0, p.n_main, st, src);
+    if (n == 4) {
+      *(float4u*)(a.out + g) = float4u{v.v[0], v.v[1], v.v[2], v.v[3]};
+    } else {
+      for (int e = 0; e < 4; ++e)
+        if (e < n) a.out[g + e] = v.v[e];
+    }
+  }
+}
+
 // block (b, m): cells [b * kReduceSpan, ..) of map m, four per thread in order; parts[(m * n_red + r) * nblocks + b]
 __global__ __launch_bounds__(kThreads) void k_expr_reduce(const Program p, const Args a, Partial* parts) {
   __shared__ float4a stk[kMaxStack - 1][kThreads];
@@ -150,6 +175,18 @@ hipError_t launch(const Program& p, const Args& a, size_t batch, void* scratch, 
   size_t blocks = (ngroups + kThreads - 1) / kThreads;
   if (blocks > 8192) blocks = 8192;  // (grid-stride beyond: 32 blocks per CU)
   hipLaunchKernelGGL(k_expr_map, dim3((unsigned)blocks), dim3(kThreads), 0, stream, p, a, results);
+  return hipGetLastError();
+}
+
+hipError_t launch_rect(const Program& p, const Args& a, int rows, int cols, int map, int i0, int j0, int h, int w, hipStream_t stream) {
+  // a rectangle of the map and a program without reductions: anything else is a caller's error, never a launch
+  if (p.n_red > 0 || map < 0 || i0 < 0 || j0 < 0 || h <= 0 || w <= 0 || h > rows - i0 || w > cols - j0 || (size_t)rows * cols != a.cells ||
+      ((size_t)map + 1) * a.cells > a.total)
+    return hipErrorInvalidValue;
+  const size_t ngroups = (((size_t)h + 3) >> 2) * (size_t)w;
+  size_t blocks = (ngroups + kThreads - 1) / kThreads;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(k_expr_rect, dim3((unsigned)blocks), dim3(kThreads), 0, stream, p, a, (size_t)map * a.cells, rows, i0, j0, h, w);
   return hipGetLastError();
 }
 

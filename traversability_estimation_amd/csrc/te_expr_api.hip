@@ -1,7 +1,8 @@
-// te_expr_api.hip -- C-ABI of te_run_expression / te_expr_check (include/travgpu.h): a general MathExpressionFilter expression
+// te_expr_api.hip -- C-ABI of te_run_expression(_region) / te_expr_check (include/travgpu.h): a general MathExpressionFilter expression
 // over the resident layers.  The language and its compiler: te_expr.h; the kernels: te_expr.hip.  The context: te_ctx.h.
 #include "te_ctx.h"
 #include "te_expr_launch.h"
+#include "te_region_plan.h"
 
 using namespace te;
 using namespace te::shim;
@@ -50,6 +51,44 @@ int launch_locked(te_ctx* c, const expr::Program& p, const expr::Args& a) {
 
 }  // namespace
 
+// The rectangle form, shared with te_run_chain_region_expression (te_shim.hip; declared in te_ctx.h)
+namespace te {
+namespace shim {
+
+// compiles `text` and refuses what has no rectangle form; touches no context
+int region_expression_program(const char* who, const char* text, expr::Program* p) {
+  if (const int rc = compile(who, text, p)) return rc;
+  if (p->n_red > 0)
+    return fail(TE_ERR_UNSUPPORTED, "%s: the expression has a reduction over the whole map, which a changed cell carries to every cell: "
+                                    "run te_run_expression", who);
+  if (expr::layer_mask(*p) & bit(TE_LAYER_TRAVERSABILITY))
+    return fail(TE_ERR_UNSUPPORTED, "%s: the expression reads the traversability layer it writes: what the whole-map call would write now is "
+                                    "not defined for a rectangle recomputed in place; run te_run_expression", who);
+  return TE_OK;
+}
+
+// the layers the program reads (TE_ERR_NOT_READY: one is missing); caller holds the lock; launches and changes nothing
+int region_expression_args(const char* who, te_ctx* c, const expr::Program& p, expr::Args* a) {
+  if (!c->have_geo) return fail(TE_ERR_NOT_READY, "%s: geometry not set", who);
+  return make_args(who, c, p, *a);
+}
+
+// the kernel on the rectangle (checked by the caller), then the facts of te_upload_layer_tile(TE_LAYER_TRAVERSABILITY)
+int region_expression_launch(const char* who, te_ctx* c, const expr::Program& p, const expr::Args& a, int map, int row0, int col0, int h, int w) {
+  HIP_TRY(hipSetDevice(c->device));
+  const hipError_t e = expr::launch_rect(p, a, c->geo.rows, c->geo.cols, map, row0, col0, h, w, c->stream);
+  if (e == hipErrorInvalidValue) {
+    (void)hipGetLastError();
+    return fail(TE_ERR_INVALID_ARG, "%s: rectangle (%d,%d)+(%d,%d) of map %d outside %dx%d", who, row0, col0, h, w, map, c->geo.rows, c->geo.cols);
+  }
+  HIP_TRY(e);
+  c->st.expression_wrote_traversability_region();
+  return TE_OK;
+}
+
+}  // namespace shim
+}  // namespace te
+
 extern "C" {
 
 int te_expr_check(const char* text, te_expr_info* info) {
@@ -81,6 +120,24 @@ int te_run_expression(te_ctx* c, const char* text, int out_layer) {
   // as te_upload_layer(TE_LAYER_TRAVERSABILITY) leaves it: the values are not bounded by the weights
   c->st.expression_wrote_traversability();
   return TE_OK;
+}
+
+int te_run_expression_region(te_ctx* c, const char* text, int out_layer, int map, int row0, int col0, int h, int w) {
+  const char* const who = "te_run_expression_region";
+  if (!c || !text) return fail(TE_ERR_INVALID_ARG, "%s: NULL", who);
+  if (out_layer != TE_LAYER_TRAVERSABILITY)
+    return fail(TE_ERR_INVALID_ARG, "%s: the output layer must be traversability (TE_LAYER_TRAVERSABILITY), got %d", who, out_layer);
+  expr::Program p;
+  if (const int rc = region_expression_program(who, text, &p)) return rc;
+  TraceRange tr(who);
+  CtxLock lk(c, /*beside_prefetch*/ true, expr::layer_mask(p) | bit(TE_LAYER_TRAVERSABILITY));
+  if (!c->have_geo) return fail(TE_ERR_NOT_READY, "%s: geometry not set", who);
+  if (map < 0 || map >= c->geo.batch) return fail(TE_ERR_INVALID_ARG, "%s: map %d of batch %d", who, map, c->geo.batch);
+  if (!region::valid_rect(c->geo.rows, c->geo.cols, row0, col0, h, w))
+    return fail(TE_ERR_INVALID_ARG, "%s: rectangle (%d,%d)+(%d,%d) outside %dx%d", who, row0, col0, h, w, c->geo.rows, c->geo.cols);
+  expr::Args a;
+  if (const int rc = region_expression_args(who, c, p, &a)) return rc;
+  return region_expression_launch(who, c, p, a, map, row0, col0, h, w);
 }
 
 int te_time_expression_samples(te_ctx* c, const char* text, int warmup, int iters, float* ms) {

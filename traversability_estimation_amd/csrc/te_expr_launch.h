@@ -25,6 +25,9 @@ inline size_t scratch_bytes(const Program& p, size_t cells, size_t batch) {
 }
 // the launches of one evaluation, in order on `stream`; `scratch` (scratch_bytes, 8-byte aligned) only with reductions
 hipError_t launch(const Program& p, const Args& a, size_t batch, void* scratch, hipStream_t stream);
+// te_run_expression_region: the program on the cells [i0, i0 + h) x [j0, j0 + w) of map `map` (rows x cols cells, a.cells of
+// them); no reductions, no scratch.  hipErrorInvalidValue: the rectangle is not one of the map, or the program has a reduction.
+hipError_t launch_rect(const Program& p, const Args& a, int rows, int cols, int map, int i0, int j0, int h, int w, hipStream_t stream);
 
 }  // namespace expr
 }  // namespace te

@@ -1,6 +1,6 @@
-// te_region_plan.h -- te_run_median_fill_region and te_run_radius_filter_region as plans: plain C++, no HIP, shared with the
-// CPU test (tests/cpu/region_plan_check.cpp).  How far a changed cell of the input reaches into the output, the rectangle a
-// region call writes, the rectangle every mask stage of the fill computes and reads, and the launch geometry of every route
+// te_region_plan.h -- te_run_median_fill_region, te_run_radius_filter_region and te_run_window_expression_region as plans: plain
+// C++, no HIP, shared with the CPU tests (tests/cpu/region_plan_check.cpp, tests/cpu/window_region_check.cpp).  How far a
+// changed cell of the input reaches into the output, the rectangle a region call writes, the rectangle every mask stage of the fill computes and reads, and the launch geometry of every route
 // over that rectangle.  The launchers (te_median_api.hip, te_radius_api.hip) decide nothing of their own.
 //
 // A region call recomputes every cell of `out` from the input as it is now; it never reads the output layer.  `out` is the
@@ -27,6 +27,7 @@
 #pragma once
 #include "te_median_plan.h"
 #include "te_radius_plan.h"
+#include "te_window_plan.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define TE_REGION_HD __host__ __device__ inline
@@ -149,4 +150,49 @@ inline RegionPlan region_plan(int op, int rows, int cols, const Shape& s, int op
 }
 
 }  // namespace radius
+
+// te_run_window_expression_region.  Reach (Chebyshev): m = (w - 1) / 2 under every edge handling.  A cell reads its window W
+// (rule 3 of the contract), which lies within m of the cell.  `inside` and `crop` clip W to the map, `empty` pads it with NaN:
+// nothing else is read.  `mean` pads a clipped window with meanOfFinites(B), and B = W clipped to the map lies inside W: the
+// padding of a cell reads no cell farther than m either (tests/test_window_region_ref.py holds the reference to exactly
+// this).  The visit rule reads the cell's own input (compute_empty_cells) and the map's size.  So a cell farther than m from
+// every changed cell keeps its bits, and `out` = the dirty rectangle grown by m, clamped to the map.
+// Launch geometry: the kernel of the whole-map call, the tiling started at out's corner; a workgroup stages its tile with the
+// halo of m cells as before, every read checked against the MAP (the region border is no map border).  The route, the LDS
+// layout and the staging decision are the whole-map plan's.
+namespace wexpr {
+
+struct RegionPlan {
+  int reach;         // m
+  region::Rect out;  // the cells written
+  Plan k;            // the whole-map plan with the origin and the end of the owned cells; tiles over `out`
+};
+
+// `dirty` lies in the map (region::valid_rect).  option: TE_OPT_WINDOW_EXPR_ROUTE, as plan()
+inline RegionPlan region_plan(int rows, int cols, int w, int n_red, int n_outer, int option, const region::Rect& dirty) {
+  RegionPlan p;
+  p.k = plan(rows, cols, w, n_red, n_outer, option);
+  p.reach = p.k.m;
+  p.out = region::grown(dirty, p.reach, p.reach, rows, cols);
+  p.k.region = 1;
+  p.k.oi0 = p.out.i0;
+  p.k.oj0 = p.out.j0;
+  p.k.oi1 = p.out.i1;
+  p.k.oj1 = p.out.j1;
+  p.k.tiles_i = (unsigned)((region::height(p.out) + kTI - 1) / kTI);
+  p.k.tiles_j = (unsigned)((region::width(p.out) + kTJ - 1) / kTJ);
+  p.k.tiles = (unsigned long long)p.k.tiles_i * p.k.tiles_j;  // (<= the whole map's, which plan() held against 2^31)
+  return p;
+}
+
+// the cells of the map a workgroup stages (or, unstaged, may read through At): its tile with the halo, before the clamp
+inline region::Rect staged(const Plan& k, unsigned tile) {
+  int i0, j0;
+  cell_of(k, tile, 0, &i0, &j0);
+  return region::Rect{i0 - k.m, j0 - k.m, i0 - k.m + k.tile_rows, j0 - k.m + k.tile_cols};
+}
+// the cells of the input the call may read: out grown by m, clamped to the map
+inline region::Rect window_reads(const RegionPlan& p, int rows, int cols) { return region::grown(p.out, p.reach, p.reach, rows, cols); }
+
+}  // namespace wexpr
 }  // namespace te

@@ -3,6 +3,7 @@
 // Owns the device-resident elevation/output layers of a batch of maps and launches the HIP chain.
 // No CPU fallback of any kind: without a gfx950 device te_create() fails with TE_ERR_NO_DEVICE.
 #include "te_ctx.h"
+#include "te_expr_launch.h"
 #include "te_fp_table.h"
 #include "te_hole_routing.h"
 
@@ -1120,45 +1121,76 @@ int te_run_chain(te_ctx* c, unsigned flags) {
   return run_whole_locked(c, flags);
 }
 
-int te_run_chain_region(te_ctx* c, unsigned flags, int map, int row0, int col0, int h, int w) {
-  if (!c) return fail(TE_ERR_INVALID_ARG, "te_run_chain_region: NULL ctx");
-  TraceRange tr("te_run_chain_region");
-  CtxLock lk(c);
-  if (!c->have_geo) return fail(TE_ERR_NOT_READY, "te_run_chain_region: geometry not set");
+// te_run_chain_region and te_run_chain_region_expression under the caller's lock.  prog (nullptr: the weighted sum the chain
+// writes) is evaluated on the rectangle the chain recombines -- the region grown by the chain's reach -- behind the chain and
+// before the footprint half.
+static int chain_region_locked(const char* who, te_ctx* c, unsigned flags, const expr::Program* prog, int map, int row0, int col0, int h, int w) {
+  if (!c->have_geo) return fail(TE_ERR_NOT_READY, "%s: geometry not set", who);
   if (map < 0 || map >= c->geo.batch || row0 < 0 || col0 < 0 || h <= 0 || w <= 0 || row0 + h > c->geo.rows ||
       col0 + w > c->geo.cols)
-    return fail(TE_ERR_INVALID_ARG, "te_run_chain_region: rectangle outside the map");
+    return fail(TE_ERR_INVALID_ARG, "%s: rectangle outside the map", who);
   if (c->opt_normals_raster)
-    return fail(TE_ERR_UNSUPPORTED, "te_run_chain_region: not built under TE_OPT_NORMALS_ALGORITHM = 1 (raster): the roughness route on given "
-                                    "normals is whole-map only; run te_run_chain");
-  if (!c->st.chain_done()) return fail(TE_ERR_NOT_READY, "te_run_chain_region: run the full chain once first");
+    return fail(TE_ERR_UNSUPPORTED, "%s: not built under TE_OPT_NORMALS_ALGORITHM = 1 (raster): the roughness route on given "
+                                    "normals is whole-map only; run te_run_chain", who);
+  if (!c->st.chain_done()) return fail(TE_ERR_NOT_READY, "%s: run the full chain once first", who);
   const Region r = {map, row0, col0, row0 + h, col0 + w};
   const bool want_fp = (flags & (TE_RUN_FOOTPRINT | TE_RUN_FOOTPRINT_MEMO)) != 0;
   const bool fp_was_done = c->st.footprint_done(), mask_was_done = c->st.mask_done();
   if (want_fp && !fp_was_done)
-    return fail(TE_ERR_NOT_READY, "te_run_chain_region: the footprint flag refreshes a complete traversability_footprint layer; run the "
-                                  "whole-map footprint pass once first (te_run_chain with TE_RUN_FOOTPRINT, or te_run_footprint)");
+    return fail(TE_ERR_NOT_READY, "%s: the footprint flag refreshes a complete traversability_footprint layer; run the "
+                                  "whole-map footprint pass once first (te_run_chain with TE_RUN_FOOTPRINT, or te_run_footprint)", who);
+  expr::Args ea;
+  if (prog)  // (a missing layer is refused before the chain is launched)
+    if (const int rc = region_expression_args(who, c, *prog, &ea)) return rc;
   int rc = run_chain_locked(c, flags & ~(TE_RUN_FOOTPRINT | TE_RUN_FOOTPRINT_MEMO), r);
-  if (rc || !want_fp) return rc;
+  if (rc) return rc;
+  const int reach = chain_max_reach(c->cp);
+  auto grown = [&](int k) {
+    Region o = r;
+    o.i0 = r.i0 - k < 0 ? 0 : r.i0 - k;
+    o.j0 = r.j0 - k < 0 ? 0 : r.j0 - k;
+    o.i1 = r.i1 + k > c->geo.rows ? c->geo.rows : r.i1 + k;
+    o.j1 = r.j1 + k > c->geo.cols ? c->geo.cols : r.j1 + k;
+    return o;
+  };
+  if (prog && !(flags & TE_RUN_NORMALS_ONLY)) {
+    // the chain's weighted sum on r_combine (te_chain_route.h: plan_rects) is overwritten by the expression, cell for cell
+    const Region rc_ = grown(reach);
+    if (const int rc2 = region_expression_launch(who, c, *prog, ea, map, rc_.i0, rc_.j0, rc_.i1 - rc_.i0, rc_.j1 - rc_.j0)) return rc2;
+  }
+  if (!want_fp) return TE_OK;
   // The scores changed within the chain's reach of the rectangle (launch_chain re-filters and re-combines exactly that);
   // the footprint pass follows on the cells that can see them.
   // (checkForStep also follows a ray of up to max_gap_width and a Bresenham line along it through the ELEVATION, which
   // changed in the rectangle itself: the mask of a cell depends on elevations up to 2.5 + 1 + max_gap/res cells away; the
   // mask is recomputed within 3 cells of `changed`)
   const int gap_cells = (int)ceil(c->params.fp_max_gap / c->geo.res) + 5;
-  const int reach = chain_max_reach(c->cp);
-  const int grow = reach > gap_cells - 3 ? reach : gap_cells - 3;
-  Region changed = r;
-  changed.i0 = r.i0 - grow < 0 ? 0 : r.i0 - grow;
-  changed.j0 = r.j0 - grow < 0 ? 0 : r.j0 - grow;
-  changed.i1 = r.i1 + grow > c->geo.rows ? c->geo.rows : r.i1 + grow;
-  changed.j1 = r.j1 + grow > c->geo.cols ? c->geo.cols : r.j1 + grow;
+  const Region changed = grown(reach > gap_cells - 3 ? reach : gap_cells - 3);
+  // (behind an expression the layer counts as written from outside: no bound, the route of any reach)
   const double trav_cap = trav_cap_now(c, /*fresh*/ false);
   if (int rc2 = ensure_fp_any(c, trav_cap)) return rc2;
   HIP_TRY(launch_footprint(c->geo, c->fp, c->L, usable_face_flags(c), c->cmem.spiral.as<unsigned>(), c->cmem.fp_clip_table.as<int>(), (flags & TE_RUN_FOOTPRINT_MEMO) != 0, nullptr, trav_cap,
                            c->stream, &changed));
   c->st.region_footprint_refreshed(mask_was_done);
   return TE_OK;
+}
+
+int te_run_chain_region(te_ctx* c, unsigned flags, int map, int row0, int col0, int h, int w) {
+  if (!c) return fail(TE_ERR_INVALID_ARG, "te_run_chain_region: NULL ctx");
+  TraceRange tr("te_run_chain_region");
+  CtxLock lk(c);
+  return chain_region_locked("te_run_chain_region", c, flags, nullptr, map, row0, col0, h, w);
+}
+
+int te_run_chain_region_expression(te_ctx* c, unsigned flags, const char* text, int map, int row0, int col0, int h, int w) {
+  if (!text) return te_run_chain_region(c, flags, map, row0, col0, h, w);
+  const char* const who = "te_run_chain_region_expression";
+  if (!c) return fail(TE_ERR_INVALID_ARG, "%s: NULL ctx", who);
+  expr::Program prog;
+  if (const int rc = region_expression_program(who, text, &prog)) return rc;
+  TraceRange tr(who);
+  CtxLock lk(c);
+  return chain_region_locked(who, c, flags, &prog, map, row0, col0, h, w);
 }
 
 int te_run_footprint(te_ctx* c) {

@@ -14,6 +14,8 @@
 //              into LDS as arrays; pass B: each cell merges the columns of its window in ascending order.  The same
 //              functions in the same order as window_reduce: the same bits.  A workgroup that wg_separable() refuses
 //              (`mean` with a clipped window) walks directly; the branch is uniform over the workgroup.
+// A region call (te_run_window_expression_region, plan: te_region_plan.h) is the second instantiation of the kernel: the tiles
+// start at the plan's origin and a lane owns a cell below the plan's end; staging, At and both routes are the same code.
 // Built with -ffp-contract=off like every source of the library.
 #include "te_window_expr_launch.h"
 
@@ -69,6 +71,9 @@ __device__ float direct_cell(const Program& p, const Args& a, int m, LdsStack& s
   return expr::run<1>(p, 0, p.n_main, st, src).v[0];
 }
 
+// kRegion: a region call (te_region_plan.h) -- the tiles start at the plan's origin and own the cells below its end; a.in and
+// a.out point at the one map.  Every read still goes through At and the staging's own check against the MAP.
+template <bool kRegion>
 __global__ __launch_bounds__(kThreads) void k_window_expr(const Program p, const Args a, const Plan pl) {
   extern __shared__ double lds_d[];
   char* lds = (char*)lds_d;
@@ -83,6 +88,10 @@ __global__ __launch_bounds__(kThreads) void k_window_expr(const Program p, const
   const int m = pl.m;
   int i, j;
   cell_of(pl.tiles_i, blockIdx.x, (int)tid, &i, &j);
+  if (kRegion) {
+    i += pl.oi0;
+    j += pl.oj0;
+  }
   const int ii = (int)tid % kTI;
   const int i0 = i - ii, j0 = j - (int)tid / kTI;
   At at{in, T, a.rows, a.cols, i0 - m, j0 - m, pl.tile_rows, __builtin_nanf("")};
@@ -98,7 +107,7 @@ __global__ __launch_bounds__(kThreads) void k_window_expr(const Program p, const
   }
   const bool sep = pl.route == kRouteSeparable && wg_separable(a.edge, m, a.rows, a.cols, i0, j0);
   if (tid == 0) atomicAdd(&a.counts[sep ? 0 : 1], 1ull);
-  const bool mine = i < a.rows && j < a.cols;
+  const bool mine = kRegion ? i < pl.oi1 && j < pl.oj1 : i < a.rows && j < a.cols;
   if (!sep) {
     if (mine) out[(size_t)j * a.rows + i] = direct_cell(p, a, m, st, res, at, i, j);
     return;
@@ -161,7 +170,15 @@ __global__ __launch_bounds__(kThreads) void k_window_expr(const Program p, const
 hipError_t launch(const Program& prog, const Args& a, const Plan& p, hipStream_t stream) {
   if (a.nmaps <= 0) return hipSuccess;
   if (!p.fits || p.lds_bytes > kMaxLds) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_window_expr, dim3((unsigned)p.tiles, (unsigned)a.nmaps), dim3(kThreads), p.lds_bytes, stream, prog, a, p);
+  if (p.region) {
+    // the origin and the end lie in the map and the tiles cover exactly [oi0, oi1) x [oj0, oj1): anything else is no plan
+    if (a.nmaps != 1 || p.oi0 < 0 || p.oj0 < 0 || p.oi1 > a.rows || p.oj1 > a.cols || p.oi1 <= p.oi0 || p.oj1 <= p.oj0 ||
+        p.tiles_i != (unsigned)((p.oi1 - p.oi0 + kTI - 1) / kTI) || p.tiles != (unsigned long long)p.tiles_i * (unsigned)((p.oj1 - p.oj0 + kTJ - 1) / kTJ))
+      return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_window_expr<true>, dim3((unsigned)p.tiles, 1u), dim3(kThreads), p.lds_bytes, stream, prog, a, p);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(k_window_expr<false>, dim3((unsigned)p.tiles, (unsigned)a.nmaps), dim3(kThreads), p.lds_bytes, stream, prog, a, p);
   return hipGetLastError();
 }
 

@@ -2,6 +2,7 @@
 // (include/travgpu.h: gridMapFilters/SlidingWindowMathExpressionFilter on the device).  The language and its compiler:
 // te_expr.h (compile_window); the plan: te_window_plan.h; the kernel: te_window_expr.hip.  The context: te_ctx.h.
 #include "te_ctx.h"
+#include "te_region_plan.h"
 #include "te_window_expr_launch.h"
 
 using namespace te;
@@ -135,6 +136,51 @@ int te_run_window_expression(te_ctx* c, const te_window_expr_params* p, const ch
   HIP_TRY(wexpr::launch(call.prog, call.a, call.plan, c->stream));
   c->window_counts_valid = true;
   return note_layer_written(c, out_layer);
+}
+
+int te_run_window_expression_region(te_ctx* c, const te_window_expr_params* p, const char* text, int in_layer, int out_layer, int map, int row0, int col0, int h,
+                                    int w, int out_rect[4]) {
+  const char* const who = "te_run_window_expression_region";
+  if (!c || !p || !text || !out_rect) return fail(TE_ERR_INVALID_ARG, "%s: NULL", who);
+  if (const int rc = te_window_expr_params_validate(p)) return rc;
+  if (in_layer < 0 || in_layer >= TE_LAYER_COUNT) return fail(TE_ERR_INVALID_ARG, "%s: bad input layer %d", who, in_layer);
+  Call call;
+  if (const int rc = compile(who, text, in_layer, &call.prog)) return rc;
+  TraceRange tr(who);
+  CtxLock lk(c, /*beside_prefetch*/ true, bit(in_layer) | bit(out_layer));
+  if (c->have_geo) HIP_TRY(hipSetDevice(c->device));
+  // (the window before the layers: region_filter_layers marks out_layer as touched once its own checks have passed)
+  int win = 0;
+  if (c->have_geo)
+    if (const char* why = wexpr::window_from_params(p->window_size, p->use_window_length, p->window_length, c->geo.res, &win))
+      return fail(TE_ERR_BAD_PARAM, "%s: %s", who, why);
+  if (c->have_geo && !wexpr::plan(c->geo.rows, c->geo.cols, win, call.prog.n_red, call.prog.n_outer, c->opt_window_expr_route).fits)
+    return fail(TE_ERR_UNSUPPORTED, "%s: a map of %d x %d cells with a window of %d is more than the kernel indexes", who, c->geo.rows, c->geo.cols, win);
+  const float* in = nullptr;
+  float* out = nullptr;
+  if (const int rc = region_filter_layers(who, c, in_layer, out_layer, map, row0, col0, h, w, &in, &out)) return rc;
+  const region::Rect dirty = {row0, col0, row0 + h, col0 + w};
+  const wexpr::RegionPlan plan = wexpr::region_plan(c->geo.rows, c->geo.cols, win, call.prog.n_red, call.prog.n_outer, c->opt_window_expr_route, dirty);
+  HIP_TRY(c->cmem.window_counts.once(2 * sizeof(unsigned long long)));
+  call.plan = plan.k;
+  call.a.in = in;
+  call.a.out = out;
+  call.a.counts = c->cmem.window_counts.as<unsigned long long>();
+  call.a.rows = c->geo.rows;
+  call.a.cols = c->geo.cols;
+  call.a.nmaps = 1;
+  call.a.edge = p->edge_handling;
+  call.a.compute_empty_cells = p->compute_empty_cells != 0;
+  c->window_counts_valid = false;
+  HIP_TRY(hipMemsetAsync(call.a.counts, 0, 2 * sizeof(unsigned long long), c->stream));
+  HIP_TRY(wexpr::launch(call.prog, call.a, call.plan, c->stream));
+  c->window_counts_valid = true;
+  out_rect[0] = plan.out.i0;
+  out_rect[1] = plan.out.j0;
+  out_rect[2] = region::height(plan.out);
+  out_rect[3] = region::width(plan.out);
+  note_region_written(c, out_layer);
+  return TE_OK;
 }
 
 int te_window_expression_stats(te_ctx* c, uint64_t counts[2]) {

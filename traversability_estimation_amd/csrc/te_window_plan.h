@@ -93,6 +93,11 @@ struct Plan {
   unsigned tiles_i, tiles_j;
   unsigned long long tiles;   // per map: tiles_i * tiles_j, the grid's x
   int fits;           // rows, cols, m and the tile count are within what the kernels index
+  // A region call (te_region_plan.h: wexpr::region_plan): the tiles start at (oi0, oj0) instead of the map's corner and own
+  // the cells below (oi1, oj1); tiles_i, tiles_j and tiles count the tiles over that rectangle.  The whole-map plan: region 0,
+  // the rectangle the map.
+  int region;
+  int oi0, oj0, oi1, oj1;
 };
 
 // option: TE_OPT_WINDOW_EXPR_ROUTE -- 0 by plan, 1 the separable route wherever allowed, 2 the direct route always
@@ -118,6 +123,8 @@ inline Plan plan(int rows, int cols, int w, int n_red, int n_outer, int option) 
   if (option == 0 && w < kSepMinWindow) sep = false;
   p.route = sep ? kRouteSeparable : kRouteDirect;
   p.lds_bytes = sep ? p.off_part + (size_t)part_bytes : p.off_part;
+  p.oi1 = rows;
+  p.oj1 = cols;
   return p;
 }
 
@@ -146,12 +153,22 @@ TE_WIN_HD void owner_of(unsigned tiles_i, int i, int j, unsigned* tile, int* lan
   *lane = (j % kTJ) * kTI + i % kTI;
 }
 
+// ... of a plan with an origin (a region call): the same numbering over the tiles of [oi0, oi1) x [oj0, oj1); a cell at or
+// beyond (oi1, oj1) has no owner.  The whole-map plan has the origin (0, 0): cell_of / owner_of above.
+TE_WIN_HD bool cell_of(const Plan& p, unsigned tile, int lane, int* i, int* j) {
+  cell_of(p.tiles_i, tile, lane, i, j);
+  *i += p.oi0;
+  *j += p.oj0;
+  return *i < p.oi1 && *j < p.oj1;
+}
+TE_WIN_HD void owner_of(const Plan& p, int i, int j, unsigned* tile, int* lane) { owner_of(p.tiles_i, i - p.oi0, j - p.oj0, tile, lane); }
+
 // workgroups a call leaves in counts[0] (separable) and counts[1] (direct), per map
 inline void expected_counts(const Plan& p, int edge, int rows, int cols, unsigned long long counts[2]) {
   counts[0] = counts[1] = 0;
   for (unsigned t = 0; t < p.tiles; ++t) {
     int i0, j0;
-    cell_of(p.tiles_i, t, 0, &i0, &j0);
+    cell_of(p, t, 0, &i0, &j0);
     ++counts[p.route == kRouteSeparable && wg_separable(edge, p.m, rows, cols, i0, j0) ? 0 : 1];
   }
 }
