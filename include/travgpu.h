@@ -117,6 +117,10 @@ typedef enum te_layer {
                                   from its first upload on (te_upload_layer / _circular / te_upload_msg / te_device_ptr) */
   TE_LAYER_COUNT = 15
 } te_layer;
+/* Beside the 15 layers above a context holds up to TE_MAX_USER_LAYERS float layers under names of the caller's choice
+ * (te_add_layer, below): ids TE_LAYER_COUNT .. TE_LAYER_COUNT + TE_MAX_USER_LAYERS - 1, so that every id fits a 32-bit layer
+ * mask (te_expr_info).  An id that was never added is refused wherever an out-of-range id is. */
+#define TE_MAX_USER_LAYERS 16
 
 /* te_run_chain flags */
 #define TE_RUN_KEEP_NORMALS 0x1u /* also write surface_normal_{x,y,z} (i.e. no DeletionFilter) */
@@ -896,6 +900,83 @@ int te_run_chain_region_expression(te_ctx* ctx, unsigned flags, const char* text
  * (after `warmup` untimed ones), like te_time_chain_samples.  text = NULL times te_run_filter(TE_FILTER_COMBINE) the same way: the
  * weighted sum's own kernel, the yardstick of tools/expr_bench.py. */
 int te_time_expression_samples(te_ctx* ctx, const char* text, int warmup, int iters, float* ms);
+
+/* ---- user layers: a grid_map filter chain under its own layer names ----
+ * A chain file is written around layers of its own (elevation_filled, elevation_smooth, slope, edges, ...).  A context holds up
+ * to TE_MAX_USER_LAYERS of them beside the reference's 15; none is part of the slab (each is an allocation of its own).
+ *   name      matches [A-Za-z_][A-Za-z0-9_]{0,62}, is none of the 15 reference names and no function, reduction or refused
+ *             EigenLab function name of the expression language (TE_ERR_BAD_PARAM otherwise).
+ *   ids       handed out lowest free first; adding a name that exists returns its id with TE_OK; with all 16 in use
+ *             TE_ERR_UNSUPPORTED.
+ *   memory    a user layer gets its memory from its first write, as robot_slope does (every cell NaN until written; handing
+ *             out te_device_ptr counts as that write), and is present from then on.  Reading an absent one -- a download, an
+ *             input of a filter or an operand of an expression -- is TE_ERR_NOT_READY.  te_set_layer_present(layer, 0 / 1)
+ *             declares it absent / present again (1 needs memory).  te_set_geometry with another shape drops the contents and
+ *             keeps the names; a pointer from te_device_ptr is valid until then or until te_remove_layer.
+ *   where     a user id is taken wherever any float layer is: te_upload_layer / _tile / _circular, te_download_layer /
+ *             _circular / te_download_tile, te_device_ptr, te_prefetch_layers, te_run_median_fill, te_run_radius_filter,
+ *             te_run_window_expression and their region forms, te_download_occupancy / _cloud / _submap, te_upload_msg /
+ *             te_download_msg, te_run_layer_expression, te_run_threshold, te_copy_layer.  te_move_map shifts the present ones
+ *             with the other layers (exposed cells NaN).
+ *   state     writing a user layer changes none of the chain's cached results (te_ctx_state.h: user_layer_written).
+ * te_remove_layer is gridMapFilters/DeletionFilter: the memory and the name are freed (a prefetch in flight is joined
+ * first); TE_ERR_INVALID_ARG for a reference layer or an id that was never added.
+ * te_layer_id knows the reference names too (TE_ERR_INVALID_ARG: no such layer); te_layer_name writes the name with its
+ * terminator (TE_ERR_INVALID_ARG: no such layer, or cap too small). */
+int te_add_layer(te_ctx* ctx, const char* name, int* layer);
+int te_remove_layer(te_ctx* ctx, int layer);
+int te_layer_id(te_ctx* ctx, const char* name, int* layer);
+int te_layer_name(te_ctx* ctx, int layer, char* out, size_t cap);
+
+/* ---- expressions over any layer ----
+ * te_expr_check_ctx is te_expr_check with the context's user names as operands beside the reference's.
+ * te_run_layer_expression is te_run_expression into any layer that has memory or gets it from its first write (robot_slope,
+ * a user layer); the operands are reference and user names.  The evaluator, its limits and its bits are te_run_expression's.
+ *   out_layer == TE_LAYER_TRAVERSABILITY: te_run_expression(_region), bit for bit and state for state.
+ *   any other reference layer: afterwards the context is what te_upload_layer(out_layer, the same values) leaves (the region
+ *     form: te_upload_layer_tile) -- TE_LAYER_ELEVATION counts as replaced and is counted again.
+ *   a user layer: nothing else changes.
+ *   In place (out_layer in the text) works on whole maps; the region form refuses it, and a text with a reduction, with
+ *     TE_ERR_UNSUPPORTED as te_run_expression_region does.
+ *   TE_ERR_INVALID_ARG: out_layer is no layer, or one without memory that a write does not give any (traversability_x / _rot
+ *     before te_run_polygon_footprint).  TE_ERR_NOT_READY: no geometry, an operand that does not exist yet. */
+int te_expr_check_ctx(te_ctx* ctx, const char* text, te_expr_info* info);
+int te_run_layer_expression(te_ctx* ctx, const char* text, int out_layer);
+int te_run_layer_expression_region(te_ctx* ctx, const char* text, int out_layer, int map, int row0, int col0, int h, int w);
+
+/* ---- gridMapFilters/ThresholdFilter and DuplicationFilter on the device ----
+ * grid_map_filters is not in the reference tree: like the other restated filters this contract is RESTATED from memory, not
+ * pinned by a vector the reference holds.  The yardstick of the tests is the same contract in numpy
+ * (tests/ref_py/pointwise_ref.py).
+ *   te_run_threshold   in place on maps [map0, map0 + nmaps) of `layer`:
+ *                        TE_THRESHOLD_LOWER  v < (float)threshold ? (float)set_to : v
+ *                        TE_THRESHOLD_UPPER  v > (float)threshold ? (float)set_to : v
+ *                      A NaN cell stays NaN (both comparisons are false).  The layer must exist (TE_ERR_NOT_READY otherwise, as an
+ *                      input of te_run_median_fill); TE_ERR_INVALID_ARG: a bad layer, mode or map range, a NaN threshold.
+ *   te_copy_layer      dst = src on those maps, a copy on the device; dst gets memory if a write gives it any.  src == dst
+ *                      is TE_OK and does nothing.
+ * Afterwards the context is what te_upload_layer (the region form: te_upload_layer_tile) of the same values into the written
+ * layer leaves.  Asynchronous on the context's stream. */
+#define TE_THRESHOLD_LOWER 1
+#define TE_THRESHOLD_UPPER 2
+int te_run_threshold(te_ctx* ctx, int layer, int mode, double threshold, double set_to, int map0, int nmaps);
+int te_run_threshold_region(te_ctx* ctx, int layer, int mode, double threshold, double set_to, int map, int row0, int col0, int h, int w);
+int te_copy_layer(te_ctx* ctx, int src, int dst, int map0, int nmaps);
+/* A chain file typically ends MathExpressionFilter -> ThresholdFilter(lower) -> ThresholdFilter(upper) on one layer: three
+ * passes for what one cell decides alone.  This is te_run_layer_expression followed by the n te_run_threshold calls on
+ * out_layer (all maps), in ONE launch and with exactly their bits: the thresholds ride behind the expression's code as two
+ * internal opcodes (not part of the language) and count against its 64 instructions.
+ *   n in 0 .. TE_MAX_FUSED_THRESHOLDS.  TE_ERR_BAD_PARAM: the text with its thresholds no longer fits -- the caller then issues
+ *   the calls separately.  Every other refusal and the state afterwards: te_run_layer_expression(_region). */
+#define TE_MAX_FUSED_THRESHOLDS 4
+typedef struct te_threshold {
+  int32_t mode; /* TE_THRESHOLD_LOWER / TE_THRESHOLD_UPPER */
+  int32_t _pad;
+  double threshold, set_to;
+} te_threshold;
+int te_run_layer_expression_thresholds(te_ctx* ctx, const char* text, int out_layer, int n, const te_threshold* t);
+int te_run_layer_expression_thresholds_region(te_ctx* ctx, const char* text, int out_layer, int n, const te_threshold* t, int map, int row0,
+                                              int col0, int h, int w);
 
 /* ---- gridMapFilters/MedianFillFilter on the device: hole filling in front of the chain ----
  * grid_map_filters is neither in the reference tree nor vendored: like the image, occupancy and submap routes this contract is

@@ -166,9 +166,9 @@ int make_spec(const char* who, te_ctx* c, int map, int n_layers, const int* laye
     const int m = pass ? n_basic : n_layers;
     const int* ids = pass ? basic_layers : layers;
     for (int k = 0; k < m; ++k) {
-      if (ids[k] < 0 || ids[k] >= TE_LAYER_COUNT) return fail(TE_ERR_INVALID_ARG, "%s: bad layer %d", who, ids[k]);
+      if (!layer_known(c, ids[k])) return fail(TE_ERR_INVALID_ARG, "%s: bad layer %d", who, ids[k]);
       const float* p = layer_ptr(c, ids[k]);
-      if (!p) return fail(TE_ERR_NOT_READY, "%s: layer %d does not exist yet", who, ids[k]);
+      if (!p || (c->user.added(ids[k]) && !(c->st.layers_written() & bit(ids[k])))) return fail(TE_ERR_NOT_READY, "%s: layer %d does not exist yet", who, ids[k]);
       if (pass) {
         s.basic[k] = p + at;
       } else if (ids[k] == point_layer) {

@@ -35,6 +35,7 @@
 #include "te_disc_table.h"
 #include "te_internal.h"
 #include "te_msg.h"
+#include "te_user_layers.h"
 
 struct te_ctx;
 
@@ -101,6 +102,9 @@ struct te_ctx {
     // te_move_map (te_move.hip): one float layer of one map, the out-of-place target of a shift (te_slab.h: move_scratch_bytes);
     // allocated by the first move that needs it
     te::DevBuf move_scratch;
+    // the user layers (te_add_layer; te_user_layers.h holds their names, which outlive this memory): one float layer each,
+    // allocated and filled with NaN by the first write (ensure_input_layer), released one by one by te_remove_layer
+    te::DevBuf user[TE_MAX_USER_LAYERS];
     // the circular footprint at any reach (te_footprint_any.hip): its tables and its prefix-sum scratch ([batch][cols][rows + 1]
     // doubles, then as many unsigned), allocated when the footprint tables are rebuilt for that route; c->fp.any_* point into them
     struct FpAny {
@@ -126,6 +130,7 @@ struct te_ctx {
   float* poly_rot = nullptr;  // (derived: lmem.poly)
   bool check_inclination = false;  // footprint/check_robot_inclination (:114)
   std::vector<unsigned> poly_stream_host;  // stays alive until the asynchronous upload has been consumed
+  te::user::Table user;  // names of the user layers (their memory: lmem.user)
   te::Geo geo;
   te::ChainParams cp;
   te::FootprintParams fp;
@@ -224,6 +229,24 @@ int count_invalid_elevation(te_ctx* c);
 const uint8_t* usable_face_flags(const te_ctx* c);
 float* layer_ptr(te_ctx* c, int layer);
 int ensure_input_layer(te_ctx* c, int layer);
+// a reference layer, or a user layer that was added: the ids an entry point takes at all
+inline bool layer_known(const te_ctx* c, int layer) { return (layer >= 0 && layer < TE_LAYER_COUNT) || c->user.added(layer); }
+// the layers whose memory comes from their first write (ensure_input_layer): robot_slope and the user layers
+inline bool layer_on_demand(const te_ctx* c, int layer) { return layer == TE_LAYER_ROBOT_SLOPE || c->user.added(layer); }
+// the layer as a download reads it: TE_ERR_INVALID_ARG for an id that is no layer or a reference layer without memory (as ever),
+// TE_ERR_NOT_READY for a user layer that is absent
+int readable_layer(const char* who, te_ctx* c, int layer, float** out);
+// The user names as operands of an expression, copied under the context's mutex (taken and dropped here): an entry point
+// compiles its text before it takes its CtxLock.  A layer removed in between is then simply absent.
+struct UserNames {
+  te::expr::LayerName v[TE_MAX_USER_LAYERS];
+  te::user::Table copy;
+  int n = 0;
+  bool has(int layer) const { return copy.added(layer); }
+};
+void snapshot_user_names(te_ctx* c, UserNames* out);
+// the name of a layer the context knows, for messages
+const char* layer_name_of(const te_ctx* c, int layer);
 // te_median_api.hip, shared by the device filters: the layer a filter may read (TE_ERR_NOT_READY: it does not exist yet);
 // b.reserve with TE_ERR_UNSUPPORTED and a message; the facts of an upload of the same values into out_layer
 int filter_input_layer(const char* who, te_ctx* c, int id, const float** out);
@@ -237,9 +260,11 @@ void note_region_written(te_ctx* c, int out_layer);
 // (a reduction, a text that reads the traversability layer: TE_ERR_UNSUPPORTED) without a context; bind the layers
 // (TE_ERR_NOT_READY: one is missing) without a launch; launch on a rectangle of one map and record the facts of
 // te_upload_layer_tile(TE_LAYER_TRAVERSABILITY).  The last two under the caller's lock.
-int region_expression_program(const char* who, const char* text, te::expr::Program* p);
+// (un: user names that are operands too, or NULL; out_layer: the layer the text writes and therefore must not read)
+int region_expression_program(const char* who, const char* text, te::expr::Program* p, const UserNames* un = nullptr, int out_layer = TE_LAYER_TRAVERSABILITY);
 int region_expression_args(const char* who, te_ctx* c, const te::expr::Program& p, te::expr::Args* a);
-int region_expression_launch(const char* who, te_ctx* c, const te::expr::Program& p, const te::expr::Args& a, int map, int row0, int col0, int h, int w);
+int region_expression_launch(const char* who, te_ctx* c, const te::expr::Program& p, const te::expr::Args& a, int map, int row0, int col0, int h, int w,
+                             int out_layer = TE_LAYER_TRAVERSABILITY);
 int rebuild_tables(te_ctx* c);
 void rebuild_footprint_tables(te_ctx* c);
 // destroys the captured whole-map launches: their kernel arguments (tables, grids, the geometry) are baked in

@@ -104,15 +104,29 @@ struct CtxState {
   // ---- the other layers ------------------------------------------------------------------------------------------------
   // A layer is about to be written from outside (ensure_input_layer: every upload route and te_device_ptr pass there
   // before they write).  Stays set if the call then fails.
-  void layer_touched(int layer) { layers_written_ |= layer_bit(layer); }
+  void layer_touched(int layer) {
+    if (layer < TE_LAYER_COUNT) layers_written_ |= layer_bit(layer);  // (a user layer is present once a write has happened: user_layer_written)
+  }
   // A layer other than the elevation was written from outside.  A pointer hand-out does not make robot_slope present: the
   // buffer is all NaN until the caller has filled it and says so (te_set_layer_present).
   void layer_written(int layer, Written how) {
+    if (layer >= TE_LAYER_COUNT) return user_layer_written(layer);
     if (layer == TE_LAYER_ROBOT_SLOPE && how == kUploaded) have_robot_slope_ = true;
     if (layer == TE_LAYER_TRAVERSABILITY) trav_external_ = trav_ptr_out_ = true;
     if (layer_bit(layer) & kScoreLayers) mask_done_ = false;  // (the mask reads them; footprint_done stays as it was)
   }
   void robot_slope_present(bool present) { have_robot_slope_ = present; }
+  // A user layer (ids TE_LAYER_COUNT and above: te_user_layers.h) was written -- an upload, a filter, an expression, a copy,
+  // its pointer handed out.  It is present from now on, and NO cached result of the chain changes: no pass of the chain, the
+  // footprint or the mask reads a user layer.
+  void user_layer_written(int layer) {
+    if (layer >= TE_LAYER_COUNT) layers_written_ |= layer_bit(layer);
+  }
+  // te_set_layer_present on a user layer, and te_remove_layer / te_add_layer (absent: a new layer under a reused id starts so)
+  void user_layer_present(int layer, bool present) {
+    if (layer < TE_LAYER_COUNT) return;
+    layers_written_ = present ? layers_written_ | layer_bit(layer) : layers_written_ & ~layer_bit(layer);
+  }
   // te_run_expression: as an upload of the traversability layer; the expression never passes ensure_input_layer.
   void expression_wrote_traversability() {
     layer_touched(TE_LAYER_TRAVERSABILITY);
@@ -134,7 +148,9 @@ struct CtxState {
       elevation_replaced();
       have_elev_ = ok;
     }
+    if (!ok) layers_written_ &= ~(mask & ~(layer_bit(TE_LAYER_COUNT) - 1u));  // (a torn user layer is absent again)
     if (ok) {
+      layers_written_ |= mask & ~(layer_bit(TE_LAYER_COUNT) - 1u);  // (an arrived user layer is present)
       if (mask & layer_bit(TE_LAYER_ROBOT_SLOPE)) have_robot_slope_ = true;
       if (mask & layer_bit(TE_LAYER_TRAVERSABILITY)) trav_external_ = trav_ptr_out_ = true;
     }

@@ -50,6 +50,10 @@ enum Op : uint8_t {
   kPushRed,        // arg: reduction
   kAdd, kSub, kMul, kDiv, kPow, kMin, kMax,  // binary: a = below the top, b = top
   kNeg, kAbs, kSqrt, kSquare, kExp, kLog, kLog10, kSin, kCos, kTan, kAsin, kAcos,
+  // Not part of the language, never emitted by the compiler: append_thresholds() puts them behind the main code (ThresholdFilter
+  // fused into the expression's pass).  arg: index into consts of the threshold, the replacement behind it.
+  kThreshLower,  // top = top < consts[arg] ? consts[arg + 1] : top   (a NaN stays)
+  kThreshUpper,  // top = top > consts[arg] ? consts[arg + 1] : top
   kOpCount
 };
 
@@ -94,6 +98,10 @@ TE_EXPR_HD float unary(int op, float x) {
     default: return acosf(x);
   }
 }
+
+// ThresholdFilter on one value (te_run_threshold and the two opcodes): the comparison is false for a NaN, which stays
+TE_EXPR_HD float threshold_lower(float v, float t, float set_to) { return v < t ? set_to : v; }
+TE_EXPR_HD float threshold_upper(float v, float t, float set_to) { return v > t ? set_to : v; }
 
 TE_EXPR_HD float binary(int op, float a, float b) {
   switch (op) {
@@ -153,6 +161,14 @@ TE_EXPR_HD Vec<N> run(const Program& p, int begin, int end, Stack& st, const Sou
         case kCos: for (int k = 0; k < N; ++k) top.v[k] = unary(kCos, top.v[k]); break;
         case kTan: for (int k = 0; k < N; ++k) top.v[k] = unary(kTan, top.v[k]); break;
         case kAsin: for (int k = 0; k < N; ++k) top.v[k] = unary(kAsin, top.v[k]); break;
+        case kThreshLower: {
+          const float t = p.consts[arg], s = p.consts[arg + 1];
+          for (int k = 0; k < N; ++k) top.v[k] = threshold_lower(top.v[k], t, s);
+        } break;
+        case kThreshUpper: {
+          const float t = p.consts[arg], s = p.consts[arg + 1];
+          for (int k = 0; k < N; ++k) top.v[k] = threshold_upper(top.v[k], t, s);
+        } break;
         default: for (int k = 0; k < N; ++k) top.v[k] = unary(kAcos, top.v[k]); break;
       }
     }
@@ -274,8 +290,12 @@ class Compiler {
  public:
   // kOk, kBadParam or kUnsupported; on failure `err` (may be NULL) holds the message with the column
   // window_layer >= 0: window mode with that te_layer as the one variable
-  static int compile(const char* text, Program* out, char* err, size_t err_len, int window_layer = -1) {
+  // user / n_user: further operand names with their te_layer ids (a context's user layers, te_user_layers.h)
+  static int compile(const char* text, Program* out, char* err, size_t err_len, int window_layer = -1, const LayerName* user = nullptr,
+                     int n_user = 0) {
     Compiler c(text, err, err_len);
+    c.user_ = user;
+    c.n_user_ = user ? n_user : 0;
     c.window_ = window_layer >= 0;
     c.win_layer_ = window_layer;
     memset(out, 0, sizeof(*out));
@@ -329,6 +349,9 @@ class Compiler {
     return kOk;
   }
 
+  // a name the language gives a meaning: a function, a reduction, or an EigenLab function it refuses by name
+  static bool is_function_name(const char* s, size_t n) { return find_fn(s, n) != nullptr; }
+
  private:
   struct Ins {
     uint8_t op, arg;
@@ -352,6 +375,8 @@ class Compiler {
   int rc_ = kOk;
   Ins main_[kMaxCode + 1], argc_[kMaxCode + 1], arg2_[kMaxCode + 1];
   int n_main_ = 0, n_arg_ = 0, n_arg2_ = 0;
+  const LayerName* user_ = nullptr;  // operand names beside the reference's
+  int n_user_ = 0;
   bool window_ = false;  // window mode
   int win_layer_ = -1;
   int red_depth_ = 0;  // reductions around the code being emitted: 0 the main code, 1 a reduction's argument, 2 a nested one's
@@ -590,6 +615,17 @@ class Compiler {
     return nullptr;
   }
 
+  // a layer by its name: the reference's 15, then the user names handed to compile()
+  const LayerName* find_layer(const char* s, size_t n) const {
+    int n_ref = 0;
+    const LayerName* const ref = layer_names(&n_ref);
+    for (int k = 0; k < n_ref + n_user_; ++k) {
+      const LayerName* const name = k < n_ref ? &ref[k] : &user_[k - n_ref];
+      if (strlen(name->name) == n && memcmp(name->name, s, n) == 0) return name;
+    }
+    return nullptr;
+  }
+
   // primary := number | '(' expr ')' | layer | function '(' args ')'
   bool parse_primary(int nest, Node* out) {
     if (nest > kMaxNesting) return failb(kBadParam, pos_, "nested deeper than 64 levels");
@@ -613,23 +649,20 @@ class Compiler {
     const size_t n = pos_ - start;
     skip();
     const bool call = !at_end() && s_[pos_] == '(';
-    int n_names = 0;
-    const LayerName* names = layer_names(&n_names);
-    for (int k = 0; k < n_names; ++k)
-      if (strlen(names[k].name) == n && memcmp(names[k].name, s_ + start, n) == 0) {
-        if (call) return failb(kUnsupported, pos_, "indexing into a layer is not built");
-        if (window_ && names[k].id != win_layer_)
-          return failb(kBadParam, start, "a window expression has one variable: the input layer, written by its name");
-        int slot = 0;
-        while (slot < n_layers_ && layer_id_[slot] != names[k].id) ++slot;
-        if (slot == n_layers_) {
-          if (n_layers_ >= kMaxLayers) return failb(kBadParam, start, "more than 8 distinct layers");
-          layer_id_[n_layers_++] = names[k].id;
-        }
-        out->map = true;
-        out->konst = false;
-        return emit(kPushLayer, (uint8_t)slot, start);
+    if (const LayerName* const name = find_layer(s_ + start, n)) {
+      if (call) return failb(kUnsupported, pos_, "indexing into a layer is not built");
+      if (window_ && name->id != win_layer_)
+        return failb(kBadParam, start, "a window expression has one variable: the input layer, written by its name");
+      int slot = 0;
+      while (slot < n_layers_ && layer_id_[slot] != name->id) ++slot;
+      if (slot == n_layers_) {
+        if (n_layers_ >= kMaxLayers) return failb(kBadParam, start, "more than 8 distinct layers");
+        layer_id_[n_layers_++] = name->id;
       }
+      out->map = true;
+      out->konst = false;
+      return emit(kPushLayer, (uint8_t)slot, start);
+    }
     const Fn* f = find_fn(s_ + start, n);
     if (!f) return failb(kBadParam, start, "unknown name (neither a layer of the map nor a function)");
     if (f->kind == 3) return failb(kUnsupported, start, "this EigenLab function is not built (matrix algebra, and min / max whose NaN behaviour depends on Eigen's version: use minOfFinites / maxOfFinites)");
@@ -683,19 +716,64 @@ class Compiler {
   }
 };
 
-inline int compile(const char* text, Program* out, char* err, size_t err_len) { return Compiler::compile(text, out, err, err_len); }
+inline int compile(const char* text, Program* out, char* err, size_t err_len, const LayerName* user = nullptr, int n_user = 0) {
+  return Compiler::compile(text, out, err, err_len, -1, user, n_user);
+}
+
+// One ThresholdFilter behind an expression: `lower` -- v < threshold ? set_to : v, otherwise v > threshold ? set_to : v.
+struct Threshold {
+  bool lower;
+  float threshold, set_to;
+};
+constexpr int kMaxThresholds = 4;
+
+// Appends the n thresholds, in order, to the main code of a compiled program: one instruction and two constants each.  kOk, or
+// kBadParam where the program then exceeds the 64 instructions (or its table of constants) -- the caller runs the thresholds as
+// passes of their own.  The arguments of the reductions move up behind the longer main code.
+inline int append_thresholds(Program* p, int n, const Threshold* t, char* err, size_t err_len) {
+  if (err && err_len) err[0] = 0;
+  if (n < 0 || n > kMaxThresholds || (n > 0 && !t)) {
+    if (err && err_len) snprintf(err, err_len, "expression: %d thresholds (0 .. %d)", n, kMaxThresholds);
+    return kBadParam;
+  }
+  if (p->n_code + n > kMaxCode || p->n_consts + 2 * n > kMaxCode) {
+    if (err && err_len) snprintf(err, err_len, "expression: more than 64 instructions with its %d thresholds", n);
+    return kBadParam;
+  }
+  for (int k = p->n_code - 1; k >= p->n_main; --k) {
+    p->op[k + n] = p->op[k];
+    p->arg[k + n] = p->arg[k];
+  }
+  for (int k = 0; k < p->n_red; ++k) {
+    p->red_begin[k] = (uint8_t)(p->red_begin[k] + n);
+    p->red_end[k] = (uint8_t)(p->red_end[k] + n);
+  }
+  for (int k = 0; k < n; ++k) {
+    p->op[p->n_main + k] = t[k].lower ? kThreshLower : kThreshUpper;
+    p->arg[p->n_main + k] = (uint8_t)p->n_consts;
+    p->consts[p->n_consts++] = t[k].threshold;
+    p->consts[p->n_consts++] = t[k].set_to;
+  }
+  p->n_main += n;
+  p->n_code += n;
+  return kOk;
+}
 
 // window mode: `in_layer` (a te_layer id) is the one variable and denotes the window; the result must be a scalar;
 // reductions nest one level
-inline int compile_window(const char* text, int in_layer, Program* out, char* err, size_t err_len) {
+// user / n_user: the context's user layers; `in_layer` may be one of them
+inline int compile_window(const char* text, int in_layer, Program* out, char* err, size_t err_len, const LayerName* user = nullptr,
+                          int n_user = 0) {
   int n = 0;
   layer_names(&n);
-  if (in_layer < 0 || in_layer >= n) {
+  bool known = in_layer >= 0 && in_layer < n;
+  for (int k = 0; user && k < n_user; ++k) known = known || user[k].id == in_layer;
+  if (!known) {
     memset(out, 0, sizeof(*out));
     if (err && err_len) snprintf(err, err_len, "expression: bad input layer %d", in_layer);
     return kBadParam;
   }
-  return Compiler::compile(text, out, err, err_len, in_layer);
+  return Compiler::compile(text, out, err, err_len, in_layer, user, n_user);
 }
 
 inline uint32_t layer_mask(const Program& p) {

@@ -15,11 +15,11 @@ int filter_input_layer(const char* who, te_ctx* c, int id, const float** out) {
   constexpr unsigned optional = bit(TE_LAYER_NORMAL_X) | bit(TE_LAYER_NORMAL_Y) | bit(TE_LAYER_NORMAL_Z) | bit(TE_LAYER_SLOPE_FOOTPRINT) |
                                 bit(TE_LAYER_STEP_FOOTPRINT) | bit(TE_LAYER_ROUGHNESS_FOOTPRINT) | bit(TE_LAYER_TRAVERSABILITY_X) |
                                 bit(TE_LAYER_TRAVERSABILITY_ROT);
-  if (id < 0 || id >= TE_LAYER_COUNT) return fail(TE_ERR_INVALID_ARG, "%s: bad input layer %d", who, id);
+  if (!layer_known(c, id)) return fail(TE_ERR_INVALID_ARG, "%s: bad input layer %d", who, id);
   const float* ptr = layer_ptr(c, id);
   const bool written = id == TE_LAYER_TRAVERSABILITY_X || id == TE_LAYER_TRAVERSABILITY_ROT || (c->st.layers_written() & bit(id));
   const bool absent = !ptr || ((bit(id) & optional) && !written) || (id == TE_LAYER_ROBOT_SLOPE && !c->st.have_robot_slope()) ||
-                      (id == TE_LAYER_ELEVATION && !c->st.have_elev());
+                      (id == TE_LAYER_ELEVATION && !c->st.have_elev()) || (c->user.added(id) && !(c->st.layers_written() & bit(id)));
   if (absent) return fail(TE_ERR_NOT_READY, "%s: the input layer %d does not exist yet", who, id);
   *out = ptr;
   return TE_OK;
@@ -48,11 +48,11 @@ int note_layer_written(te_ctx* c, int out_layer) {
 // On success *in / *out point at the cells of `map`.  Nothing is touched before every check has passed.
 int region_filter_layers(const char* who, te_ctx* c, int in_layer, int out_layer, int map, int row0, int col0, int h, int w, const float** in, float** out) {
   if (!c->have_geo) return fail(TE_ERR_NOT_READY, "%s: geometry not set", who);
-  if (out_layer < 0 || out_layer >= TE_LAYER_COUNT) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
+  if (!layer_known(c, out_layer)) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
   if (map < 0 || map >= c->geo.batch) return fail(TE_ERR_INVALID_ARG, "%s: map %d of batch %d", who, map, c->geo.batch);
   const float* src = nullptr;
   if (const int rc = filter_input_layer(who, c, in_layer, &src)) return rc;
-  if (out_layer != TE_LAYER_ROBOT_SLOPE && !layer_ptr(c, out_layer))
+  if (!layer_on_demand(c, out_layer) && !layer_ptr(c, out_layer))
     return fail(TE_ERR_INVALID_ARG, "%s: the output layer %d has no memory yet", who, out_layer);
   if (in_layer == out_layer)
     return fail(TE_ERR_INVALID_ARG, "%s: in_layer == out_layer (%d): a region call reads the neighbours of the rectangle as they were before "
@@ -89,11 +89,11 @@ struct Call {
 // the kernels read a copy of the input, queued here.
 int prepare(const char* who, te_ctx* c, const te_median_fill_params* p, int in_layer, int out_layer, int map0, int nmaps, Call* call) {
   if (!c->have_geo) return fail(TE_ERR_NOT_READY, "%s: geometry not set", who);
-  if (out_layer < 0 || out_layer >= TE_LAYER_COUNT) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
+  if (!layer_known(c, out_layer)) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
   if (map0 < 0 || nmaps <= 0 || map0 > c->geo.batch - nmaps) return fail(TE_ERR_INVALID_ARG, "%s: maps [%d,%d) of batch %d", who, map0, map0 + nmaps, c->geo.batch);
   const float* in = nullptr;
   if (const int rc = filter_input_layer(who, c, in_layer, &in)) return rc;
-  if (out_layer != TE_LAYER_ROBOT_SLOPE && !layer_ptr(c, out_layer))
+  if (!layer_on_demand(c, out_layer) && !layer_ptr(c, out_layer))
     return fail(TE_ERR_INVALID_ARG, "%s: the output layer %d has no memory yet", who, out_layer);
   if (in_layer != out_layer)
     if (const int rc = ensure_input_layer(c, out_layer)) return rc;  // (robot_slope exists from its first write on)

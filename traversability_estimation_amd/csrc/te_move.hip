@@ -126,10 +126,10 @@ int te_move_map(te_ctx* c, double new_x, double new_y, te_move_info* info) {
     if (const int rc = reserve_scratch("te_move_map", c->lmem.move_scratch, p.scratch_bytes, c->stream, "the scratch of one layer of one map")) return rc;
   }
   if (info) *info = p.info;  // (behind the last refusal: a refused move hands out no rectangles)
-  // the 15 public layers and the step filter's height layer, wherever they have memory; the two byte masks
-  float* layers[TE_LAYER_COUNT + 1];
+  // the 15 public layers, the user layers and the step filter's height layer, wherever they have memory; the two byte masks
+  float* layers[TE_LAYER_COUNT + TE_MAX_USER_LAYERS + 1];
   int n_layers = 0;
-  for (int k = 0; k < TE_LAYER_COUNT; ++k)
+  for (int k = 0; k < TE_LAYER_COUNT + TE_MAX_USER_LAYERS; ++k)
     if (float* l = layer_ptr(c, k)) layers[n_layers++] = l;
   if (c->L.step_height) layers[n_layers++] = c->L.step_height;
   uint8_t* const masks[2] = {c->L.untrav, c->lmem.median_mask.as<uint8_t>()};

@@ -75,11 +75,11 @@ int make_job(const char* who, te_ctx* c, int map, int n_layers, const int* layer
   const size_t n = (size_t)c->geo.rows * c->geo.cols;
   memset(&job, 0, sizeof(job));
   for (int k = 0; k < n_layers; ++k) {
-    if (layers[k] < 0 || layers[k] >= TE_LAYER_COUNT) return fail(TE_ERR_INVALID_ARG, "%s: bad layer %d", who, layers[k]);
+    if (!layer_known(c, layers[k])) return fail(TE_ERR_INVALID_ARG, "%s: bad layer %d", who, layers[k]);
     if (!isfinite(data_min[k]) || !isfinite(data_max[k]))
       return fail(TE_ERR_INVALID_ARG, "%s: data_min = %g, data_max = %g", who, (double)data_min[k], (double)data_max[k]);
     const float* p = layer_ptr(c, layers[k]);
-    if (!p) return fail(TE_ERR_NOT_READY, "%s: layer %d does not exist yet", who, layers[k]);
+    if (!p || (c->user.added(layers[k]) && !(c->st.layers_written() & bit(layers[k])))) return fail(TE_ERR_NOT_READY, "%s: layer %d does not exist yet", who, layers[k]);
     job.l[k].src = p + n * (size_t)map;
     job.l[k].mn = data_min[k];
     job.l[k].range = data_max[k] - data_min[k];

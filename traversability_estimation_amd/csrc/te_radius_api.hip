@@ -56,12 +56,12 @@ int window_table(const char* who, te_ctx* c, double rad, radius::Window* w, radi
 // the kernels read a copy of the input, queued here.
 int prepare(const char* who, te_ctx* c, int op, double rad, int in_layer, int out_layer, int map0, int nmaps, Call* call) {
   if (!c->have_geo) return fail(TE_ERR_NOT_READY, "%s: geometry not set", who);
-  if (out_layer < 0 || out_layer >= TE_LAYER_COUNT) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
+  if (!layer_known(c, out_layer)) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
   if (map0 < 0 || nmaps <= 0 || map0 > c->geo.batch - nmaps) return fail(TE_ERR_INVALID_ARG, "%s: maps [%d,%d) of batch %d", who, map0, map0 + nmaps, c->geo.batch);
   if (nmaps > 65535) return fail(TE_ERR_INVALID_ARG, "%s: %d maps in one call (at most 65535)", who, nmaps);
   const float* in = nullptr;
   if (const int rc = filter_input_layer(who, c, in_layer, &in)) return rc;
-  if (out_layer != TE_LAYER_ROBOT_SLOPE && !layer_ptr(c, out_layer))
+  if (!layer_on_demand(c, out_layer) && !layer_ptr(c, out_layer))
     return fail(TE_ERR_INVALID_ARG, "%s: the output layer %d has no memory yet", who, out_layer);
   if (in_layer != out_layer)
     if (const int rc = ensure_input_layer(c, out_layer)) return rc;  // (robot_slope exists from its first write on)

@@ -588,21 +588,45 @@ float* layer_ptr(te_ctx* c, int layer) {
     case TE_LAYER_TRAVERSABILITY_X: return c->lmem.poly.as<float>();
     case TE_LAYER_TRAVERSABILITY_ROT: return c->poly_rot;
     case TE_LAYER_ROBOT_SLOPE: return c->lmem.robot_slope.as<float>();
-    default: return nullptr;
+    default: return c->user.added(layer) ? c->lmem.user[layer - TE_LAYER_COUNT].as<float>() : nullptr;  // (a user layer, or no layer)
   }
 }
 
-// the optional input layer robot_slope exists from its first upload on (every cell NaN = not valid until written)
+int readable_layer(const char* who, te_ctx* c, int layer, float** out) {
+  float* const p = layer_ptr(c, layer);
+  if (c->user.added(layer) && (!p || !(c->st.layers_written() & bit(layer))))
+    return fail(TE_ERR_NOT_READY, "%s: the layer %s does not exist yet (nothing has written it)", who, layer_name_of(c, layer));
+  if (!p) return fail(TE_ERR_INVALID_ARG, "%s: bad layer %d", who, layer);
+  *out = p;
+  return TE_OK;
+}
+
+void snapshot_user_names(te_ctx* c, UserNames* out) {
+  std::lock_guard<std::mutex> lk(c->mu);
+  out->copy = c->user;
+  out->n = out->copy.operands(out->v);
+}
+
+const char* layer_name_of(const te_ctx* c, int layer) {
+  int n = 0;
+  const expr::LayerName* names = expr::layer_names(&n);
+  if (layer >= 0 && layer < n) return names[layer].name;
+  return c->user.added(layer) ? c->user.name[layer - TE_LAYER_COUNT] : "(no layer)";
+}
+
+// the optional input layer robot_slope exists from its first upload on (every cell NaN = not valid until written), and so
+// does every user layer
 int ensure_input_layer(te_ctx* c, int layer) {
   c->st.layer_touched(layer);
-  DevBuf& rs = c->lmem.robot_slope;
-  if (layer != TE_LAYER_ROBOT_SLOPE || rs.p) return TE_OK;
+  if (!layer_on_demand(c, layer)) return TE_OK;
+  DevBuf& rs = layer == TE_LAYER_ROBOT_SLOPE ? c->lmem.robot_slope : c->lmem.user[layer - TE_LAYER_COUNT];
+  if (rs.p) return TE_OK;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(rs.once(c->layer_elems * sizeof(float)));
   const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)rs.p, 0x7fc00000, c->layer_elems, c->stream);
   if (e != hipSuccess) {
     rs.release();
-    return fail(TE_ERR_HIP, "robot_slope layer: %s", hipGetErrorString(e));
+    return fail(TE_ERR_HIP, "layer %s: %s", layer_name_of(c, layer), hipGetErrorString(e));
   }
   return TE_OK;
 }

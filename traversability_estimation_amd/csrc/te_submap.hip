@@ -82,8 +82,8 @@ int make_job(const char* who, te_ctx* c, int map, double req_x, double req_y, do
   const size_t n = (size_t)c->geo.rows * c->geo.cols;
   memset(&job, 0, sizeof(job));
   for (int k = 0; k < n_layers; ++k) {
-    const float* p = layer_ptr(c, layers[k]);  // (as te_download_msg: no such id, or a layer that does not exist yet)
-    if (!p) return fail(TE_ERR_INVALID_ARG, "%s: bad layer %d", who, layers[k]);
+    float* p = nullptr;  // (as te_download_msg: no such id, or a layer that does not exist yet)
+    if (const int rc = readable_layer(who, c, layers[k], &p)) return rc;
     job.src[k] = p + n * (size_t)map;
   }
   if (!si.ok) return TE_OK;

@@ -1,6 +1,7 @@
 // te_transfer.hip -- C-ABI of libtravgpu.so, the transfers (include/travgpu.h): whole layers, tiles (synchronous and on the
 // copy streams), GridMap's circular-buffer order, grid_map_msgs/GridMap messages and bags, whole-layer prefetches beside
-// the caller's own work, page-locking, sensor_msgs/Image (parser and kernel: te_image.hip).  The context and the helpers
+// the caller's own work, page-locking, sensor_msgs/Image (parser and kernel: te_image.hip), and the user layers' own calls
+// (te_add_layer, te_remove_layer, te_layer_id, te_layer_name).  The context and the helpers
 // shared with the other parts: te_ctx.h.
 #include "te_ctx.h"
 #include "te_image.h"
@@ -76,7 +77,7 @@ int te_upload_layer_tile(te_ctx* c, int layer, const float* host_tile, int map, 
   if (!c || !host_tile) return fail(TE_ERR_INVALID_ARG, "te_upload_layer_tile: NULL");
   CtxLock lk(c);
   if (const int rc = check_tile(c, "te_upload_layer_tile", map, row0, col0, h, w)) return rc;
-  if (layer < 0 || layer >= TE_LAYER_COUNT || (layer != TE_LAYER_ROBOT_SLOPE && !layer_ptr(c, layer)))
+  if (!layer_known(c, layer) || (!layer_on_demand(c, layer) && !layer_ptr(c, layer)))
     return fail(TE_ERR_INVALID_ARG, "te_upload_layer_tile: bad layer %d", layer);
   if (const int rc = ensure_input_layer(c, layer)) return rc;
   HIP_TRY(hipSetDevice(c->device));
@@ -92,8 +93,8 @@ int te_download_tile(te_ctx* c, int layer, int map, int row0, int col0, int h, i
   if (!c || !host_tile) return fail(TE_ERR_INVALID_ARG, "te_download_tile: NULL");
   CtxLock lk(c);
   if (const int rc = check_tile(c, "te_download_tile", map, row0, col0, h, w)) return rc;
-  const float* p = layer_ptr(c, layer);
-  if (!p) return fail(TE_ERR_INVALID_ARG, "te_download_tile: bad layer %d", layer);
+  float* p = nullptr;
+  if (const int rc = readable_layer("te_download_tile", c, layer, &p)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const float* src = p + (size_t)map * c->geo.rows * c->geo.cols + (size_t)col0 * c->geo.rows + row0;
   HIP_TRY(hipMemcpy2DAsync(host_tile, (size_t)h * sizeof(float), src, (size_t)c->geo.rows * sizeof(float), (size_t)h * sizeof(float),
@@ -133,8 +134,8 @@ int te_download_tile_async(te_ctx* c, int layer, int map, int row0, int col0, in
   if (!c || !host_tile) return fail(TE_ERR_INVALID_ARG, "te_download_tile_async: NULL");
   CtxLock lk(c);
   if (const int rc = check_tile(c, "te_download_tile_async", map, row0, col0, h, w)) return rc;
-  const float* p = layer_ptr(c, layer);
-  if (!p) return fail(TE_ERR_INVALID_ARG, "te_download_tile_async: bad layer %d", layer);
+  float* p = nullptr;
+  if (const int rc = readable_layer("te_download_tile_async", c, layer, &p)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   if (const int rc = tile_streams(c)) return rc;
   te_ctx::TileSlot& sl = c->out_slot[c->out_next];
@@ -176,6 +177,11 @@ int te_device_ptr(te_ctx* c, int layer, void** dptr, size_t* bytes) {
 int te_set_layer_present(te_ctx* c, int layer, int present) {
   if (!c) return fail(TE_ERR_INVALID_ARG, "te_set_layer_present: NULL ctx");
   CtxLock lk(c);
+  if (c->user.added(layer)) {  // a user layer: present needs memory, as robot_slope
+    if (present && !layer_ptr(c, layer)) return fail(TE_ERR_NOT_READY, "te_set_layer_present: the layer %s was never written nor handed out (te_device_ptr)", layer_name_of(c, layer));
+    c->st.user_layer_present(layer, present != 0);
+    return TE_OK;
+  }
   if (layer != TE_LAYER_ROBOT_SLOPE) return fail(TE_ERR_INVALID_ARG, "te_set_layer_present: only the optional input layer robot_slope can be declared present / absent");
   if (present && !c->lmem.robot_slope.p) return fail(TE_ERR_NOT_READY, "te_set_layer_present: robot_slope was never uploaded nor handed out (te_device_ptr)");
   c->st.robot_slope_present(present != 0);
@@ -272,8 +278,8 @@ static int download_layer_circular_checked(te_ctx* c, int layer, float* host, in
   if (expect_rows > 0 && (c->geo.rows != expect_rows || c->geo.cols != expect_cols))
     return fail(TE_ERR_NOT_READY, "the geometry changed to %dx%d under a %dx%d message transfer (another thread)", c->geo.rows,
                 c->geo.cols, expect_rows, expect_cols);
-  float* p = layer_ptr(c, layer);
-  if (!p) return fail(TE_ERR_INVALID_ARG, "te_download_layer_circular: bad layer %d", layer);
+  float* p = nullptr;
+  if (const int rc = readable_layer("te_download_layer_circular", c, layer, &p)) return rc;
   if (map < 0 || map >= c->geo.batch || start_row < 0 || start_row >= c->geo.rows || start_col < 0 || start_col >= c->geo.cols)
     return fail(TE_ERR_INVALID_ARG, "te_download_layer_circular: map %d, start index (%d,%d) of a %dx%d map", map, start_row,
                 start_col, c->geo.rows, c->geo.cols);
@@ -475,8 +481,8 @@ int te_download_layer(te_ctx* c, int layer, float* host, int map0, int nmaps) {
   if (!c || !host) return fail(TE_ERR_INVALID_ARG, "te_download_layer: NULL");
   CtxLock lk(c, /*beside_prefetch*/ true, bit(layer));
   if (!c->have_geo) return fail(TE_ERR_NOT_READY, "te_download_layer: geometry not set");
-  float* p = layer_ptr(c, layer);
-  if (!p) return fail(TE_ERR_INVALID_ARG, "te_download_layer: bad layer %d", layer);
+  float* p = nullptr;
+  if (const int rc = readable_layer("te_download_layer", c, layer, &p)) return rc;
   if (map0 < 0 || nmaps <= 0 || map0 + nmaps > c->geo.batch)
     return fail(TE_ERR_INVALID_ARG, "te_download_layer: maps [%d,%d) of batch %d", map0, map0 + nmaps, c->geo.batch);
   HIP_TRY(hipSetDevice(c->device));
@@ -569,6 +575,54 @@ int te_wait_prefetch(te_ctx* c) {
   CtxLock lk(c);  // (joins the prefetch)
   const int rc = c->prefetch_rc.exchange(TE_OK);
   if (rc != TE_OK) return fail(rc, "te_prefetch_layers: a transfer failed");
+  return TE_OK;
+}
+
+// ---- the user layers (travgpu.h; names: te_user_layers.h, memory: te_ctx::LayerMem::user, allocated by ensure_input_layer) ----
+int te_add_layer(te_ctx* c, const char* name, int* layer) {
+  if (!c || !name || !layer) return fail(TE_ERR_INVALID_ARG, "te_add_layer: NULL");
+  CtxLock lk(c, /*beside_prefetch*/ true);  // (a new name touches no layer)
+  const char* why = "";
+  const bool existed = c->user.find(name) >= TE_LAYER_COUNT;
+  const int rc = c->user.add(name, layer, &why);
+  if (rc != TE_OK) return fail(rc, "te_add_layer: '%.80s': %s", name, why);
+  if (!existed) c->st.user_layer_present(*layer, false);  // (an id that is used again starts absent)
+  return TE_OK;
+}
+
+int te_remove_layer(te_ctx* c, int layer) {
+  if (!c) return fail(TE_ERR_INVALID_ARG, "te_remove_layer: NULL ctx");
+  CtxLock lk(c, /*beside_prefetch*/ true, bit(layer));  // (a prefetch that writes the layer is joined first)
+  if (!c->user.added(layer))
+    return fail(TE_ERR_INVALID_ARG, layer >= 0 && layer < TE_LAYER_COUNT ? "te_remove_layer: %d is a layer of the reference; only user layers are removed"
+                                                                         : "te_remove_layer: bad layer %d", layer);
+  te::DevBuf& b = c->lmem.user[layer - TE_LAYER_COUNT];
+  if (b.p) {
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (launches in flight may still read or write it)
+    b.release();
+  }
+  c->user.remove(layer);
+  c->st.user_layer_present(layer, false);
+  return TE_OK;
+}
+
+int te_layer_id(te_ctx* c, const char* name, int* layer) {
+  if (!c || !name || !layer) return fail(TE_ERR_INVALID_ARG, "te_layer_id: NULL");
+  CtxLock lk(c, /*beside_prefetch*/ true);
+  const int id = c->user.find(name);
+  if (id < 0) return fail(TE_ERR_INVALID_ARG, "te_layer_id: no layer '%.80s'", name);
+  *layer = id;
+  return TE_OK;
+}
+
+int te_layer_name(te_ctx* c, int layer, char* out, size_t cap) {
+  if (!c || !out) return fail(TE_ERR_INVALID_ARG, "te_layer_name: NULL");
+  CtxLock lk(c, /*beside_prefetch*/ true);
+  if (!layer_known(c, layer)) return fail(TE_ERR_INVALID_ARG, "te_layer_name: bad layer %d", layer);
+  const char* const name = layer_name_of(c, layer);
+  if (strlen(name) + 1 > cap) return fail(TE_ERR_INVALID_ARG, "te_layer_name: %zu bytes for '%s'", cap, name);
+  strcpy(out, name);
   return TE_OK;
 }
 

@@ -21,9 +21,13 @@ struct Call {
   wexpr::Plan plan;
 };
 
-int compile(const char* who, const char* text, int in_layer, expr::Program* p) {
+// c: the context whose user layers are names too (a user in_layer is the window's variable), or NULL
+int compile(const char* who, const char* text, int in_layer, expr::Program* p, te_ctx* c = nullptr) {
   char err[200];
-  const int rc = expr::compile_window(text, in_layer, p, err, sizeof(err));
+  UserNames un;
+  if (c) snapshot_user_names(c, &un);
+  if (c && in_layer >= TE_LAYER_COUNT && !un.has(in_layer)) return fail(TE_ERR_INVALID_ARG, "%s: bad input layer %d", who, in_layer);
+  const int rc = expr::compile_window(text, in_layer, p, err, sizeof(err), un.v, un.n);
   return rc == TE_OK ? TE_OK : fail(rc, "%s: %s", who, err);
 }
 
@@ -31,12 +35,12 @@ int compile(const char* who, const char* text, int in_layer, expr::Program* p) {
 // the kernel reads a copy of the input, queued here.
 int prepare(const char* who, te_ctx* c, const te_window_expr_params* p, int in_layer, int out_layer, int map0, int nmaps, Call* call) {
   if (!c->have_geo) return fail(TE_ERR_NOT_READY, "%s: geometry not set", who);
-  if (out_layer < 0 || out_layer >= TE_LAYER_COUNT) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
+  if (!layer_known(c, out_layer)) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
   if (map0 < 0 || nmaps <= 0 || map0 > c->geo.batch - nmaps) return fail(TE_ERR_INVALID_ARG, "%s: maps [%d,%d) of batch %d", who, map0, map0 + nmaps, c->geo.batch);
   if (nmaps > 65535) return fail(TE_ERR_INVALID_ARG, "%s: %d maps in one call (at most 65535)", who, nmaps);
   const float* in = nullptr;
   if (const int rc = filter_input_layer(who, c, in_layer, &in)) return rc;
-  if (out_layer != TE_LAYER_ROBOT_SLOPE && !layer_ptr(c, out_layer))
+  if (!layer_on_demand(c, out_layer) && !layer_ptr(c, out_layer))
     return fail(TE_ERR_INVALID_ARG, "%s: the output layer %d has no memory yet", who, out_layer);
   if (in_layer != out_layer)
     if (const int rc = ensure_input_layer(c, out_layer)) return rc;  // (robot_slope exists from its first write on)
@@ -124,9 +128,9 @@ int te_window_expr_check(const char* text, int in_layer, te_expr_info* info) {
 int te_run_window_expression(te_ctx* c, const te_window_expr_params* p, const char* text, int in_layer, int out_layer, int map0, int nmaps) {
   if (!c || !p || !text) return fail(TE_ERR_INVALID_ARG, "te_run_window_expression: NULL");
   if (const int rc = te_window_expr_params_validate(p)) return rc;
-  if (in_layer < 0 || in_layer >= TE_LAYER_COUNT) return fail(TE_ERR_INVALID_ARG, "te_run_window_expression: bad input layer %d", in_layer);
+  if (in_layer < 0) return fail(TE_ERR_INVALID_ARG, "te_run_window_expression: bad input layer %d", in_layer);
   Call call;
-  if (const int rc = compile("te_run_window_expression", text, in_layer, &call.prog)) return rc;
+  if (const int rc = compile("te_run_window_expression", text, in_layer, &call.prog, c)) return rc;
   TraceRange tr("te_run_window_expression");
   CtxLock lk(c, /*beside_prefetch*/ true, bit(in_layer) | bit(out_layer));
   if (c->have_geo) HIP_TRY(hipSetDevice(c->device));
@@ -143,9 +147,9 @@ int te_run_window_expression_region(te_ctx* c, const te_window_expr_params* p, c
   const char* const who = "te_run_window_expression_region";
   if (!c || !p || !text || !out_rect) return fail(TE_ERR_INVALID_ARG, "%s: NULL", who);
   if (const int rc = te_window_expr_params_validate(p)) return rc;
-  if (in_layer < 0 || in_layer >= TE_LAYER_COUNT) return fail(TE_ERR_INVALID_ARG, "%s: bad input layer %d", who, in_layer);
+  if (in_layer < 0) return fail(TE_ERR_INVALID_ARG, "%s: bad input layer %d", who, in_layer);
   Call call;
-  if (const int rc = compile(who, text, in_layer, &call.prog)) return rc;
+  if (const int rc = compile(who, text, in_layer, &call.prog, c)) return rc;
   TraceRange tr(who);
   CtxLock lk(c, /*beside_prefetch*/ true, bit(in_layer) | bit(out_layer));
   if (c->have_geo) HIP_TRY(hipSetDevice(c->device));

@@ -368,3 +368,181 @@ def radius_filter_from_yaml(path_or_dict):
         out.append({"op": RADIUS_FILTER_TYPES[str(f["type"])], "radius": radius, "input_layer": str(prm["input_layer"]),
                     "output_layer": str(prm["output_layer"])})
     return out
+
+
+# ---- a grid_map_filters chain file as a list of steps (Context.run_filter_chain runs them) -------------------------------------
+REFERENCE_LAYERS = ("elevation", "traversability_slope", "traversability_step", "traversability_roughness", "traversability",
+                    "traversability_footprint", "surface_normal_x", "surface_normal_y", "surface_normal_z", "slope_footprint",
+                    "step_footprint", "roughness_footprint", "traversability_x", "traversability_rot", "robot_slope")
+_NORMAL_LAYERS = ("surface_normal_x", "surface_normal_y", "surface_normal_z")
+_LAYER_NAME = re.compile(r"[A-Za-z_][A-Za-z0-9_]{0,62}\Z")
+MAX_FUSED_THRESHOLDS = 4
+_CHAIN_KEYS = {
+    "NormalVectorsFilter": {"input_layer", "output_layers_prefix", "radius", "normal_vector_positive_axis", "algorithm", "parallelization_enabled",
+                            "thread_number"},
+    "SlopeFilter": {"map_type", "critical_value"},
+    "StepFilter": {"map_type", "critical_value", "first_window_radius", "second_window_radius", "critical_cell_number"},
+    "RoughnessFilter": {"map_type", "critical_value", "estimation_radius"},
+    "MathExpressionFilter": {"output_layer", "expression"},
+    "ThresholdFilter": {"layer", "condition_layer", "output_layer", "lower_threshold", "upper_threshold", "set_to"},
+    "DuplicationFilter": {"input_layer", "output_layer"},
+    "DeletionFilter": {"layers"},
+}
+_PLUGIN_MAP_TYPE = {"SlopeFilter": "traversability_slope", "StepFilter": "traversability_step", "RoughnessFilter": "traversability_roughness"}
+_CHAIN_TYPES = ("MedianFillFilter", "MeanInRadiusFilter", "MinInRadiusFilter", "NormalVectorsFilter", "SlopeFilter", "StepFilter", "RoughnessFilter",
+                "MathExpressionFilter", "SlidingWindowMathExpressionFilter", "ThresholdFilter", "DuplicationFilter", "DeletionFilter")
+
+
+def _chain_step(entry, k):
+    """One entry of a chain list as a step; every refusal names the entry."""
+    name = str(entry.get("name", "entry %d" % k)) if isinstance(entry, dict) else "entry %d" % k
+
+    def refuse(msg):
+        raise ParamsYamlError(f"filter '{name}': {msg}")
+
+    if not isinstance(entry, dict) or "type" not in entry:
+        refuse("no type")
+    ns, _, kind = str(entry["type"]).partition("/")
+    if ns not in ("gridMapFilters", "traversabilityFilters") or kind not in _CHAIN_TYPES:
+        refuse(f"type '{entry['type']}' is not built (built: {', '.join(_CHAIN_TYPES)})")
+    prm = entry.get("params") or {}
+    if not isinstance(prm, dict):
+        refuse("params is not a map")
+    one = [{"type": "gridMapFilters/" + kind, "params": prm}]
+    try:  # the three readers this module already has: their checks, their words
+        if kind == "MedianFillFilter":
+            f = median_fill_from_yaml(one)
+            return {"name": name, "filter": "median_fill", "input_layer": f.pop("input_layer"), "output_layer": f.pop("output_layer"), "params": f}
+        if kind in ("MeanInRadiusFilter", "MinInRadiusFilter"):
+            return dict(radius_filter_from_yaml(one)[0], name=name, filter="radius")
+        if kind == "SlidingWindowMathExpressionFilter":
+            return dict(window_expression_from_yaml(one)[0], name=name, filter="window_expression")
+    except ParamsYamlError as e:
+        refuse(str(e))
+    unknown = set(prm) - _CHAIN_KEYS[kind]
+    if unknown:
+        refuse(f"{kind}: unknown parameter(s) {sorted(unknown)}")
+
+    def need(key):
+        if key not in prm:
+            refuse(f"{kind} did not find param {key}")
+        return prm[key]
+
+    def number(key):
+        try:
+            v = float(need(key))
+        except (TypeError, ValueError):
+            refuse(f"{kind}: {key} must be a number (got {prm[key]!r})")
+        if not np.isfinite(v):
+            refuse(f"{kind}: {key} must be finite (got {v})")
+        return v
+
+    def layer(key):
+        v = str(need(key))
+        if not _LAYER_NAME.match(v):
+            refuse(f"{kind}: {key} '{v}' is no layer name ([A-Za-z_][A-Za-z0-9_]*, at most 63 characters)")
+        return v
+
+    if kind == "NormalVectorsFilter":
+        if str(prm.get("input_layer", "elevation")) != "elevation":
+            refuse("NormalVectorsFilter: input_layer must be 'elevation' (the plugin reads the elevation layer)")
+        if str(prm.get("output_layers_prefix", "surface_normal_")) != "surface_normal_":
+            refuse("NormalVectorsFilter: output_layers_prefix must be 'surface_normal_' (SlopeFilter.cpp:71 hard-codes it)")
+        algorithm = str(prm.get("algorithm", "area"))
+        if algorithm not in ("area", "raster"):
+            refuse(f"NormalVectorsFilter: algorithm must be area or raster (got '{algorithm}')")
+        fields = {}
+        if algorithm == "area" or "radius" in prm:
+            fields["normals_radius"] = number("radius")
+        try:
+            fields["normals_axis"] = _axis(prm.get("normal_vector_positive_axis", "z"))
+        except ParamsYamlError as e:
+            refuse(str(e))
+        return {"name": name, "filter": "normals", "fields": fields, "algorithm": algorithm}
+    if kind in _PLUGIN_MAP_TYPE:
+        want = _PLUGIN_MAP_TYPE[kind]
+        if str(prm.get("map_type", want)) != want:
+            refuse(f"{kind}: map_type must stay '{want}': the plugin writes the layer of that name")
+        if kind == "SlopeFilter":
+            fields = {"slope_critical": number("critical_value")}
+        elif kind == "StepFilter":
+            n = need("critical_cell_number")
+            if isinstance(n, bool) or not isinstance(n, int):
+                refuse(f"StepFilter: critical_cell_number must be an integer (got {n!r})")
+            fields = {"step_critical": number("critical_value"), "step_radius1": number("first_window_radius"),
+                      "step_radius2": number("second_window_radius"), "step_ncrit": n}
+            fields["fp_critical_step"] = fields["step_critical"]
+        else:
+            fields = {"rough_critical": number("critical_value"), "rough_radius": number("estimation_radius")}
+        return {"name": name, "filter": kind[:-len("Filter")].lower(), "fields": fields}
+    if kind == "MathExpressionFilter":
+        text = str(need("expression"))
+        if not text.strip():
+            refuse("MathExpressionFilter: the expression is empty")
+        return {"name": name, "filter": "expression", "expression": text, "output_layer": layer("output_layer")}
+    if kind == "ThresholdFilter":
+        lower, upper = "lower_threshold" in prm, "upper_threshold" in prm
+        if lower == upper:
+            refuse("ThresholdFilter: exactly one of lower_threshold and upper_threshold (got %s)" % ("both" if lower else "neither"))
+        names = {str(prm[k]) for k in ("layer", "condition_layer", "output_layer") if k in prm}
+        if not names:
+            refuse("ThresholdFilter did not find param layer")
+        if len(names) > 1:
+            refuse(f"ThresholdFilter: the filter runs in place: layer, condition_layer and output_layer must name one layer (got {sorted(names)})")
+        key = "layer" if "layer" in prm else "condition_layer" if "condition_layer" in prm else "output_layer"
+        return {"name": name, "filter": "threshold", "layer": layer(key), "mode": "lower" if lower else "upper",
+                "threshold": number("lower_threshold" if lower else "upper_threshold"), "set_to": float(need("set_to"))}
+    if kind == "DuplicationFilter":
+        return {"name": name, "filter": "duplication", "input_layer": layer("input_layer"), "output_layer": layer("output_layer")}
+    layers = need("layers")
+    if not isinstance(layers, list) or not layers:
+        refuse("DeletionFilter: layers must be a list of layer names")
+    layers = [str(v) for v in layers]
+    kept = [v for v in layers if v in REFERENCE_LAYERS and v not in _NORMAL_LAYERS]
+    if kept:
+        refuse(f"DeletionFilter: {kept} are layers of the context itself and cannot be deleted (the normal layers are dropped, user layers removed)")
+    return {"name": name, "filter": "deletion", "layers": layers}
+
+
+def filter_chain_from_yaml(path_or_text, key=None):
+    """A grid_map_filters chain file as the list of steps Context.run_filter_chain runs, in file order.  `key`: the name of the
+    list in the document (default: `traversability_map_filters` if it is there, otherwise the document's only list; a document
+    that IS a list needs none).  Types, as gridMapFilters/... or traversabilityFilters/...: MedianFillFilter, MeanInRadiusFilter,
+    MinInRadiusFilter, NormalVectorsFilter (area or raster), SlopeFilter, StepFilter, RoughnessFilter, MathExpressionFilter,
+    SlidingWindowMathExpressionFilter, ThresholdFilter, DuplicationFilter, DeletionFilter.  Every key each filter reads is
+    checked; any other type, an unknown key and a ThresholdFilter with both or neither threshold raise ParamsYamlError with the
+    entry's name.  A step is a dict with "name", "filter" and that filter's arguments; the three plugins and NormalVectorsFilter
+    carry the te_params fields their entry sets ("fields"): they run as te_run_filter on the reference's layer names."""
+    doc = _load(path_or_text)
+    if isinstance(doc, list):
+        chain = doc
+    else:
+        lists = {k: v for k, v in (doc or {}).items() if isinstance(v, list)} if isinstance(doc, dict) else {}
+        if key is None:
+            key = CHAIN_KEY if CHAIN_KEY in lists else next(iter(lists)) if len(lists) == 1 else None
+        if key is None or key not in lists:
+            raise ParamsYamlError(f"no filter list {'named ' + repr(key) if key else 'to choose'} in the chain file (lists: {sorted(lists)})")
+        chain = lists[key]
+    if not chain:
+        raise ParamsYamlError("the filter list is empty")
+    return [_chain_step(e, k) for k, e in enumerate(chain)]
+
+
+def plan_filter_chain(steps, fuse=True):
+    """The steps grouped into the calls the runner issues: a list of (call, step, extra).  With `fuse` a MathExpressionFilter
+    takes the ThresholdFilters that DIRECTLY follow it on its output layer into its own launch
+    (te_run_layer_expression_thresholds), at most MAX_FUSED_THRESHOLDS of them: a threshold on another layer, or behind any
+    other filter, is a call of its own, and so is the fifth threshold and every one behind it."""
+    out, k = [], 0
+    while k < len(steps):
+        s = steps[k]
+        k += 1
+        if s["filter"] != "expression":
+            out.append((s["filter"], s, None))
+            continue
+        fused = []
+        while fuse and k < len(steps) and len(fused) < MAX_FUSED_THRESHOLDS and steps[k]["filter"] == "threshold" and steps[k]["layer"] == s["output_layer"]:
+            fused.append(steps[k])
+            k += 1
+        out.append(("expression", s, fused))
+    return out
