@@ -134,3 +134,45 @@ def test_a_refused_call_changes_nothing(capi, name):
         refused(capi, capi.TE_ERR_INVALID_ARG, f.run, ctx, dst=12)
         assert np.array_equal(bits(ctx, OUT), layer)
         assert f.state(ctx) == state
+
+
+def pointwise_call(name):
+    """te_copy_layer, te_run_threshold or te_run_layer_expression reading `src`, writing `dst`; `maps` where the call takes them."""
+    def call(ctx, src="elevation", dst=OUT, **maps):
+        if name == "copy":
+            ctx.copy_layer(src, dst, **maps)
+        elif name == "threshold":
+            ctx.run_threshold(dst, "lower", 0.0, 1.0, **maps)
+        else:
+            assert not maps
+            ctx.run_layer_expression(f"2 * {src}" if isinstance(src, str) else "2 * elevation", dst)
+    return call
+
+
+@pytest.mark.parametrize("shape", [(ROWS, COLS), (16, 9)])
+@pytest.mark.parametrize("name", ("copy", "threshold", "layer_expression"))
+def test_a_refused_pointwise_call_changes_nothing(capi, name, shape):
+    """A bad map range and a user id that was never added: the layers of the call, the block counts of the radius filter before
+    it and the user layers' absence are afterwards what they were."""
+    rows, cols = shape
+    call = pointwise_call(name)
+    unadded = len(capi.LAYERS) + 3
+    elevation = np.ascontiguousarray(np.stack([m.T for m in K.holey_maps(rows, cols, BATCH, 43, ["speckle_5"])]), np.float32).reshape(-1)
+    with context(capi, rows, cols, elevation) as ctx:
+        Filter(capi, "radius").run(ctx)
+        call(ctx)
+        layers = {k: bits(ctx, k) for k in ("elevation", OUT)}
+        state = ctx.radius_filter_stats()
+        if name == "layer_expression":  # (the whole-map call takes no maps: its region form names one)
+            refused(capi, capi.TE_ERR_INVALID_ARG, ctx.run_layer_expression_region, "2 * elevation", OUT, BATCH, 0, 0, 4, 4)
+            refused(capi, capi.TE_ERR_INVALID_ARG, ctx.run_layer_expression_region, "2 * elevation", OUT, -1, 0, 0, 4, 4)
+        else:
+            refused(capi, capi.TE_ERR_INVALID_ARG, call, ctx, map0=1, nmaps=2)
+            refused(capi, capi.TE_ERR_INVALID_ARG, call, ctx, map0=BATCH, nmaps=1)
+        refused(capi, capi.TE_ERR_INVALID_ARG, call, ctx, dst=unadded)
+        if name == "copy":
+            refused(capi, capi.TE_ERR_INVALID_ARG, call, ctx, src=unadded)
+        for k, v in layers.items():
+            assert np.array_equal(bits(ctx, k), v), k
+        assert ctx.radius_filter_stats() == state
+        refused(capi, capi.TE_ERR_INVALID_ARG, ctx.download, unadded)

@@ -26,6 +26,7 @@
 #include <chrono>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <thread>
 #include <vector>
 
@@ -34,6 +35,7 @@
 #include "te_devbuf.h"
 #include "te_disc_table.h"
 #include "te_internal.h"
+#include "te_layer_call.h"
 #include "te_msg.h"
 #include "te_user_layers.h"
 
@@ -229,10 +231,28 @@ int count_invalid_elevation(te_ctx* c);
 const uint8_t* usable_face_flags(const te_ctx* c);
 float* layer_ptr(te_ctx* c, int layer);
 int ensure_input_layer(te_ctx* c, int layer);
+// The call contract of the layer filters (te_layer_call.h) on a context: its facts, and a refusal as the entry point's status
+// and message -- the one home of each wording.  Caller holds the lock.
+te::layer_call::Facts facts_of(const te_ctx* c);
+// where a call points, for the messages: maps [map0, map0 + nmaps) (a region form: the map `map0`) and the rectangle
+struct CallWhere {
+  int map0 = 0, nmaps = 1, max_maps = 0;
+  int row0 = 0, col0 = 0, h = 0, w = 0;
+};
+// TE_OK for an accepted verdict, else fail(v.code, ...)
+int refused(const char* who, const te_ctx* c, const te::layer_call::Verdict& v, const CallWhere& at = CallWhere());
 // a reference layer, or a user layer that was added: the ids an entry point takes at all
-inline bool layer_known(const te_ctx* c, int layer) { return (layer >= 0 && layer < TE_LAYER_COUNT) || c->user.added(layer); }
+inline bool layer_known(const te_ctx* c, int layer) {
+  te::layer_call::Facts f;
+  f.user_added = c->user.mask();
+  return te::layer_call::known(f, layer);
+}
 // the layers whose memory comes from their first write (ensure_input_layer): robot_slope and the user layers
-inline bool layer_on_demand(const te_ctx* c, int layer) { return layer == TE_LAYER_ROBOT_SLOPE || c->user.added(layer); }
+inline bool layer_on_demand(const te_ctx* c, int layer) {
+  te::layer_call::Facts f;
+  f.user_added = c->user.mask();
+  return te::layer_call::on_demand(f, layer);
+}
 // the layer as a download reads it: TE_ERR_INVALID_ARG for an id that is no layer or a reference layer without memory (as ever),
 // TE_ERR_NOT_READY for a user layer that is absent
 int readable_layer(const char* who, te_ctx* c, int layer, float** out);
@@ -247,15 +267,25 @@ struct UserNames {
 void snapshot_user_names(te_ctx* c, UserNames* out);
 // the name of a layer the context knows, for messages
 const char* layer_name_of(const te_ctx* c, int layer);
-// te_median_api.hip, shared by the device filters: the layer a filter may read (TE_ERR_NOT_READY: it does not exist yet);
-// b.reserve with TE_ERR_UNSUPPORTED and a message; the facts of an upload of the same values into out_layer
-int filter_input_layer(const char* who, te_ctx* c, int id, const float** out);
+// te_median_api.hip, shared by the device filters: b.reserve with TE_ERR_UNSUPPORTED and a message; the facts of an upload of
+// the same values into out_layer
 int reserve_scratch(const char* who, te::DevBuf& b, size_t bytes, hipStream_t stream, const char* what);
 int note_layer_written(te_ctx* c, int out_layer);
 // ... and of the region filters: their checks for one map and one rectangle (the cells of the map behind *in / *out), and the
 // facts of te_upload_tile (the elevation) or te_upload_layer (any other layer) afterwards
 int region_filter_layers(const char* who, te_ctx* c, int in_layer, int out_layer, int map, int row0, int col0, int h, int w, const float** in, float** out);
 void note_region_written(te_ctx* c, int out_layer);
+// the rectangle a region call wrote, as its out_rect: row0, col0, height, width
+inline void write_rect(const te::region::Rect& r, int out_rect[4]) {
+  out_rect[0] = r.i0;
+  out_rect[1] = r.j0;
+  out_rect[2] = te::region::height(r);
+  out_rect[3] = te::region::width(r);
+}
+// the two block counts a filter left in `counts`, read back (waits for the stream); caller holds the lock
+int read_block_counts(te_ctx* c, const te::DevBuf& counts, uint64_t out[2]);
+// what te_expr_check and its kin report of a compiled program (te_expr_api.hip)
+void fill_expr_info(const te::expr::Program& p, te_expr_info* info);
 // te_expr_api.hip, the rectangle form of te_run_expression, shared with te_run_chain_region_expression: compile and refuse
 // (a reduction, a text that reads the traversability layer: TE_ERR_UNSUPPORTED) without a context; bind the layers
 // (TE_ERR_NOT_READY: one is missing) without a launch; launch on a rectangle of one map and record the facts of
@@ -271,5 +301,33 @@ void rebuild_footprint_tables(te_ctx* c);
 void drop_graph(te_ctx* c);
 int sync_tiles(te_ctx* c);  // waits for the copy streams of the streaming-tile calls
 int run_whole_locked(te_ctx* c, unsigned flags);
+
+// The event-timed loop of the te_time_*_samples: warmup + iters times `before()` (outside the timed span), ev0, `body()`, ev1,
+// and the elapsed time of the last `iters` into ms.  Both return a status; the first that is not TE_OK ends the loop.
+// locked: the caller holds the context's lock over the whole loop and has made the device current.  Otherwise `body` is an
+// entry point that takes the lock itself, and the loop takes it around its events.
+template <class Before, class Body>
+int time_samples(te_ctx* c, bool locked, int warmup, int iters, float* ms, Before before, Body body) {
+  for (int k = -warmup; k < iters; ++k) {
+    {
+      std::optional<CtxLock> lk;
+      if (!locked) {
+        lk.emplace(c);
+        HIP_TRY(hipSetDevice(c->device));
+      }
+      if (const int rc = before()) return rc;
+      HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    }
+    if (const int rc = body()) return rc;
+    std::optional<CtxLock> lk;
+    if (!locked) lk.emplace(c);
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(hipEventSynchronize(c->ev1));
+    float t = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&t, c->ev0, c->ev1));
+    if (k >= 0) ms[k] = t;
+  }
+  return TE_OK;
+}
 }  // namespace shim
 }  // namespace te

@@ -35,16 +35,12 @@ int append_thresholds(const char* who, expr::Program* p, int n, const te_thresho
 
 // the layers the program reads, as the launch takes them; caller holds the lock.  Every refusal comes before the first launch.
 int make_args(const char* who, te_ctx* c, const expr::Program& p, expr::Args& a) {
-  constexpr unsigned optional = bit(TE_LAYER_NORMAL_X) | bit(TE_LAYER_NORMAL_Y) | bit(TE_LAYER_NORMAL_Z) | bit(TE_LAYER_SLOPE_FOOTPRINT) |
-                                bit(TE_LAYER_STEP_FOOTPRINT) | bit(TE_LAYER_ROUGHNESS_FOOTPRINT);
   memset(&a, 0, sizeof(a));
+  const layer_call::Facts f = facts_of(c);
   for (int k = 0; k < p.n_layers; ++k) {
     const int id = p.layer_id[k];
-    const float* ptr = layer_ptr(c, id);
-    const bool absent = !ptr || (bit(id) & optional & ~c->st.layers_written()) || (id == TE_LAYER_ROBOT_SLOPE && !c->st.have_robot_slope()) ||
-                        (id >= TE_LAYER_COUNT && !(bit(id) & c->st.layers_written()));
-    if (absent) return fail(TE_ERR_NOT_READY, "%s: the layer %s does not exist yet", who, layer_name_of(c, id));
-    a.in[k] = ptr;
+    if (const int rc = refused(who, c, layer_call::check_expression_operand(f, id))) return rc;
+    a.in[k] = layer_ptr(c, id);
   }
   a.out = c->L.trav;
   a.cells = (size_t)c->geo.rows * c->geo.cols;
@@ -67,6 +63,13 @@ int launch_locked(te_ctx* c, const expr::Program& p, const expr::Args& a) {
 // The rectangle form, shared with te_run_chain_region_expression (te_shim.hip; declared in te_ctx.h)
 namespace te {
 namespace shim {
+
+void fill_expr_info(const expr::Program& p, te_expr_info* info) {
+  info->n_instructions = p.n_code;
+  info->layer_mask = expr::layer_mask(p);
+  info->n_reductions = p.n_red;
+  info->stack_depth = p.stack_depth;
+}
 
 // compiles `text` and refuses what has no rectangle form; touches no context
 int region_expression_program(const char* who, const char* text, expr::Program* p, const UserNames* un, int out_layer) {
@@ -114,12 +117,7 @@ int te_expr_check(const char* text, te_expr_info* info) {
   if (!text) return fail(TE_ERR_INVALID_ARG, "te_expr_check: NULL");
   expr::Program p;
   if (const int rc = compile("te_expr_check", text, &p)) return rc;
-  if (info) {
-    info->n_instructions = p.n_code;
-    info->layer_mask = expr::layer_mask(p);
-    info->n_reductions = p.n_red;
-    info->stack_depth = p.stack_depth;
-  }
+  if (info) fill_expr_info(p, info);
   return TE_OK;
 }
 
@@ -165,28 +163,21 @@ int te_expr_check_ctx(te_ctx* c, const char* text, te_expr_info* info) {
   snapshot_user_names(c, &un);
   expr::Program p;
   if (const int rc = compile("te_expr_check_ctx", text, &p, &un)) return rc;
-  if (info) {
-    info->n_instructions = p.n_code;
-    info->layer_mask = expr::layer_mask(p);
-    info->n_reductions = p.n_red;
-    info->stack_depth = p.stack_depth;
-  }
+  if (info) fill_expr_info(p, info);
   return TE_OK;
 }
 
 namespace {
 
-// out_layer as the output of an expression: a layer the context knows that has memory or gets it from this write.  Caller
-// holds the lock; allocates nothing.
-int check_out_layer(const char* who, te_ctx* c, int out_layer) {
-  if (!layer_known(c, out_layer)) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
-  if (!layer_on_demand(c, out_layer) && !layer_ptr(c, out_layer)) return fail(TE_ERR_INVALID_ARG, "%s: the output layer %d has no memory yet", who, out_layer);
-  return TE_OK;
+// out_layer before the context is looked at: an id that can be a layer at all
+int possible_out_layer(const char* who, int out_layer) {
+  if (out_layer >= 0 && out_layer < TE_LAYER_COUNT + TE_MAX_USER_LAYERS) return TE_OK;
+  return refused(who, nullptr, {TE_ERR_INVALID_ARG, layer_call::kBadOutput, out_layer, false});
 }
 
 int run_layer_expression(const char* who, te_ctx* c, const char* text, int out_layer, int n, const te_threshold* t) {
   if (!c || !text) return fail(TE_ERR_INVALID_ARG, "%s: NULL", who);
-  if (out_layer < 0 || out_layer >= TE_LAYER_COUNT + TE_MAX_USER_LAYERS) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
+  if (const int rc = possible_out_layer(who, out_layer)) return rc;
   UserNames un;
   snapshot_user_names(c, &un);
   expr::Program p;
@@ -195,7 +186,7 @@ int run_layer_expression(const char* who, te_ctx* c, const char* text, int out_l
   TraceRange tr(who);
   CtxLock lk(c, /*beside_prefetch*/ true, expr::layer_mask(p) | bit(out_layer));
   if (!c->have_geo) return fail(TE_ERR_NOT_READY, "%s: geometry not set", who);
-  if (const int rc = check_out_layer(who, c, out_layer)) return rc;
+  if (const int rc = refused(who, c, layer_call::check_expression_output(facts_of(c), out_layer))) return rc;  // (allocates nothing)
   expr::Args a;
   if (const int rc = make_args(who, c, p, a)) return rc;
   HIP_TRY(hipSetDevice(c->device));
@@ -213,7 +204,7 @@ int run_layer_expression(const char* who, te_ctx* c, const char* text, int out_l
 int run_layer_expression_region(const char* who, te_ctx* c, const char* text, int out_layer, int n, const te_threshold* t, int map, int row0, int col0, int h,
                                 int w) {
   if (!c || !text) return fail(TE_ERR_INVALID_ARG, "%s: NULL", who);
-  if (out_layer < 0 || out_layer >= TE_LAYER_COUNT + TE_MAX_USER_LAYERS) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
+  if (const int rc = possible_out_layer(who, out_layer)) return rc;
   UserNames un;
   snapshot_user_names(c, &un);
   expr::Program p;
@@ -222,7 +213,7 @@ int run_layer_expression_region(const char* who, te_ctx* c, const char* text, in
   TraceRange tr(who);
   CtxLock lk(c, /*beside_prefetch*/ true, expr::layer_mask(p) | bit(out_layer));
   if (!c->have_geo) return fail(TE_ERR_NOT_READY, "%s: geometry not set", who);
-  if (const int rc = check_out_layer(who, c, out_layer)) return rc;
+  if (const int rc = refused(who, c, layer_call::check_expression_output(facts_of(c), out_layer))) return rc;  // (allocates nothing)
   if (map < 0 || map >= c->geo.batch) return fail(TE_ERR_INVALID_ARG, "%s: map %d of batch %d", who, map, c->geo.batch);
   if (!region::valid_rect(c->geo.rows, c->geo.cols, row0, col0, h, w))
     return fail(TE_ERR_INVALID_ARG, "%s: rectangle (%d,%d)+(%d,%d) outside %dx%d", who, row0, col0, h, w, c->geo.rows, c->geo.cols);
@@ -254,21 +245,8 @@ int te_run_layer_expression_thresholds_region(te_ctx* c, const char* text, int o
 
 int te_time_expression_samples(te_ctx* c, const char* text, int warmup, int iters, float* ms) {
   if (!c || !ms || iters <= 0 || warmup < 0) return fail(TE_ERR_INVALID_ARG, "te_time_expression_samples: bad argument");
-  for (int k = -warmup; k < iters; ++k) {
-    {
-      CtxLock lk(c);
-      HIP_TRY(hipSetDevice(c->device));
-      HIP_TRY(hipEventRecord(c->ev0, c->stream));
-    }
-    if (const int rc = text ? te_run_expression(c, text, TE_LAYER_TRAVERSABILITY) : te_run_filter(c, TE_FILTER_COMBINE, 0)) return rc;
-    CtxLock lk(c);
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(hipEventSynchronize(c->ev1));
-    float t = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&t, c->ev0, c->ev1));
-    if (k >= 0) ms[k] = t;
-  }
-  return TE_OK;
+  const auto body = [&]() -> int { return text ? te_run_expression(c, text, TE_LAYER_TRAVERSABILITY) : te_run_filter(c, TE_FILTER_COMBINE, 0); };
+  return time_samples(c, /*locked*/ false, warmup, iters, ms, [] { return TE_OK; }, body);
 }
 
 }  // extern "C"

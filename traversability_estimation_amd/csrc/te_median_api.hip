@@ -10,21 +10,6 @@ using namespace te::shim;
 namespace te {
 namespace shim {
 
-// the layers a call may read: as te_run_expression sees them, and an elevation that was uploaded
-int filter_input_layer(const char* who, te_ctx* c, int id, const float** out) {
-  constexpr unsigned optional = bit(TE_LAYER_NORMAL_X) | bit(TE_LAYER_NORMAL_Y) | bit(TE_LAYER_NORMAL_Z) | bit(TE_LAYER_SLOPE_FOOTPRINT) |
-                                bit(TE_LAYER_STEP_FOOTPRINT) | bit(TE_LAYER_ROUGHNESS_FOOTPRINT) | bit(TE_LAYER_TRAVERSABILITY_X) |
-                                bit(TE_LAYER_TRAVERSABILITY_ROT);
-  if (!layer_known(c, id)) return fail(TE_ERR_INVALID_ARG, "%s: bad input layer %d", who, id);
-  const float* ptr = layer_ptr(c, id);
-  const bool written = id == TE_LAYER_TRAVERSABILITY_X || id == TE_LAYER_TRAVERSABILITY_ROT || (c->st.layers_written() & bit(id));
-  const bool absent = !ptr || ((bit(id) & optional) && !written) || (id == TE_LAYER_ROBOT_SLOPE && !c->st.have_robot_slope()) ||
-                      (id == TE_LAYER_ELEVATION && !c->st.have_elev()) || (c->user.added(id) && !(c->st.layers_written() & bit(id)));
-  if (absent) return fail(TE_ERR_NOT_READY, "%s: the input layer %d does not exist yet", who, id);
-  *out = ptr;
-  return TE_OK;
-}
-
 int reserve_scratch(const char* who, DevBuf& b, size_t bytes, hipStream_t stream, const char* what) {
   const hipError_t e = b.reserve(bytes, stream);
   if (e != hipSuccess) return fail(TE_ERR_UNSUPPORTED, "%s: %s (%zu bytes) does not fit in device memory: %s", who, what, bytes, hipGetErrorString(e));
@@ -43,25 +28,16 @@ int note_layer_written(te_ctx* c, int out_layer) {
   return TE_OK;
 }
 
-// The checks of a region filter (te_run_median_fill_region, te_run_radius_filter_region) in the order of the whole-map
-// calls (te_layer_call.h) for the one map, then the two of their own: the layers differ, the rectangle lies in the map.
-// On success *in / *out point at the cells of `map`.  Nothing is touched before every check has passed.
+// The checks of a region filter (te_run_median_fill_region, te_run_radius_filter_region, te_run_window_expression_region):
+// te_layer_call.h, check_region.  On success *in / *out point at the cells of `map`.  Nothing is touched before every check
+// has passed.
 int region_filter_layers(const char* who, te_ctx* c, int in_layer, int out_layer, int map, int row0, int col0, int h, int w, const float** in, float** out) {
-  if (!c->have_geo) return fail(TE_ERR_NOT_READY, "%s: geometry not set", who);
-  if (!layer_known(c, out_layer)) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
-  if (map < 0 || map >= c->geo.batch) return fail(TE_ERR_INVALID_ARG, "%s: map %d of batch %d", who, map, c->geo.batch);
-  const float* src = nullptr;
-  if (const int rc = filter_input_layer(who, c, in_layer, &src)) return rc;
-  if (!layer_on_demand(c, out_layer) && !layer_ptr(c, out_layer))
-    return fail(TE_ERR_INVALID_ARG, "%s: the output layer %d has no memory yet", who, out_layer);
-  if (in_layer == out_layer)
-    return fail(TE_ERR_INVALID_ARG, "%s: in_layer == out_layer (%d): a region call reads the neighbours of the rectangle as they were before "
-                                    "the filter, and in place their earlier input is gone; keep the unfiltered values in a layer of their own", who, in_layer);
-  if (!region::valid_rect(c->geo.rows, c->geo.cols, row0, col0, h, w))
-    return fail(TE_ERR_INVALID_ARG, "%s: rectangle (%d,%d)+(%d,%d) outside %dx%d", who, row0, col0, h, w, c->geo.rows, c->geo.cols);
+  CallWhere at;
+  at.map0 = map, at.row0 = row0, at.col0 = col0, at.h = h, at.w = w;
+  if (const int rc = refused(who, c, layer_call::check_region(facts_of(c), in_layer, out_layer, map, row0, col0, h, w), at)) return rc;
   if (const int rc = ensure_input_layer(c, out_layer)) return rc;  // (robot_slope exists from its first write on)
   const size_t cells = (size_t)c->geo.rows * c->geo.cols;
-  *in = src + cells * (size_t)map;
+  *in = layer_ptr(c, in_layer) + cells * (size_t)map;
   *out = layer_ptr(c, out_layer) + cells * (size_t)map;
   return TE_OK;
 }
@@ -85,28 +61,32 @@ struct Call {
   median::Plan plan;
 };
 
+// the radii of the two windows in cells; r_exist -1: finite cells keep their value
+void window_radii(const te_ctx* c, const te_median_fill_params* p, int* r_fill, int* r_exist) {
+  const int rows = c->geo.rows, cols = c->geo.cols;
+  *r_fill = median::radius_cells(p->fill_hole_radius, c->geo.res, rows, cols);
+  *r_exist = -1;
+  if (p->filter_existing_values) {
+    *r_exist = median::radius_cells(p->existing_value_radius, c->geo.res, rows, cols);
+    if (*r_exist == 0) *r_exist = -1;  // the median of a finite cell's window of one cell is the cell
+  }
+}
+
 // checks, scratch and plan of one call; caller holds the lock and has made the device current.  With in_layer == out_layer
 // the kernels read a copy of the input, queued here.
 int prepare(const char* who, te_ctx* c, const te_median_fill_params* p, int in_layer, int out_layer, int map0, int nmaps, Call* call) {
-  if (!c->have_geo) return fail(TE_ERR_NOT_READY, "%s: geometry not set", who);
-  if (!layer_known(c, out_layer)) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
-  if (map0 < 0 || nmaps <= 0 || map0 > c->geo.batch - nmaps) return fail(TE_ERR_INVALID_ARG, "%s: maps [%d,%d) of batch %d", who, map0, map0 + nmaps, c->geo.batch);
-  const float* in = nullptr;
-  if (const int rc = filter_input_layer(who, c, in_layer, &in)) return rc;
-  if (!layer_on_demand(c, out_layer) && !layer_ptr(c, out_layer))
-    return fail(TE_ERR_INVALID_ARG, "%s: the output layer %d has no memory yet", who, out_layer);
+  CallWhere at;
+  at.map0 = map0, at.nmaps = nmaps;
+  if (const int rc = refused(who, c, layer_call::check(facts_of(c), in_layer, out_layer, map0, nmaps, 0), at)) return rc;
   if (in_layer != out_layer)
     if (const int rc = ensure_input_layer(c, out_layer)) return rc;  // (robot_slope exists from its first write on)
+  const float* const in = layer_ptr(c, in_layer);
   float* const out = layer_ptr(c, out_layer);
 
   const int rows = c->geo.rows, cols = c->geo.cols;
   const size_t cells = (size_t)rows * cols, total = cells * (size_t)nmaps;
-  const int r_fill = median::radius_cells(p->fill_hole_radius, c->geo.res, rows, cols);
-  int r_exist = -1;
-  if (p->filter_existing_values) {
-    r_exist = median::radius_cells(p->existing_value_radius, c->geo.res, rows, cols);
-    if (r_exist == 0) r_exist = -1;  // the median of a finite cell's window of one cell is the cell
-  }
+  int r_fill = 0, r_exist = -1;
+  window_radii(c, p, &r_fill, &r_exist);
   const median::Plan plan = median::plan(rows, cols, nmaps, std::max(r_fill, r_exist), c->opt_median_route);
   if (plan.route == median::kRouteAny && cells >= ((size_t)1 << 32))
     return fail(TE_ERR_UNSUPPORTED, "%s: a window radius of %d cells takes the general kernel, which lists cells in 32 bits: %zu cells per map are too many", who, plan.r, cells);
@@ -175,7 +155,7 @@ int te_run_median_fill(te_ctx* c, const te_median_fill_params* p, int in_layer, 
   if (const int rc = te_median_fill_params_validate(p)) return rc;
   TraceRange tr("te_run_median_fill");
   CtxLock lk(c, /*beside_prefetch*/ true, bit(in_layer) | bit(out_layer));
-  Call call;
+  Call call{};
   if (c->have_geo) HIP_TRY(hipSetDevice(c->device));
   if (const int rc = prepare("te_run_median_fill", c, p, in_layer, out_layer, map0, nmaps, &call)) return rc;
   HIP_TRY(median::launch(call.a, call.plan, c->stream));
@@ -196,12 +176,8 @@ int te_run_median_fill_region(te_ctx* c, const te_median_fill_params* p, int in_
   if (const int rc = region_filter_layers(who, c, in_layer, out_layer, map, row0, col0, h, w, &in, &out)) return rc;
   const int rows = c->geo.rows, cols = c->geo.cols;
   const size_t cells = (size_t)rows * cols, batch_cells = cells * (size_t)c->geo.batch;
-  const int r_fill = median::radius_cells(p->fill_hole_radius, c->geo.res, rows, cols);
-  int r_exist = -1;
-  if (p->filter_existing_values) {
-    r_exist = median::radius_cells(p->existing_value_radius, c->geo.res, rows, cols);
-    if (r_exist == 0) r_exist = -1;
-  }
+  int r_fill = 0, r_exist = -1;
+  window_radii(c, p, &r_fill, &r_exist);
   const region::Rect dirty = {row0, col0, row0 + h, col0 + w};
   const median::RegionPlan plan = median::region_plan(rows, cols, r_fill, r_exist, p->num_erode_dilation_iterations, c->opt_median_route, dirty);
   if (plan.k.route == median::kRouteAny && cells >= ((size_t)1 << 32))
@@ -213,8 +189,7 @@ int te_run_median_fill_region(te_ctx* c, const te_median_fill_params* p, int in_
   if (const int rc = reserve_scratch(who, m.median_tmp, 2 * batch_cells, c->stream, "the scratch masks")) return rc;
   if (plan.k.route == median::kRouteAny)
     if (const int rc = reserve_scratch(who, m.median_any, (plan.any_blocks + 1 + region::cells(plan.out)) * sizeof(unsigned), c->stream, "the list of cells")) return rc;
-  median::Args a;
-  memset(&a, 0, sizeof(a));
+  median::Args a{};
   a.in = in;
   a.out = out;
   a.mask = m.median_mask.as<uint8_t>() + cells * (size_t)map;
@@ -229,10 +204,7 @@ int te_run_median_fill_region(te_ctx* c, const te_median_fill_params* p, int in_
   a.r_exist = r_exist;
   a.iterations = p->num_erode_dilation_iterations;
   HIP_TRY(median::launch_region(a, plan, c->stream));
-  out_rect[0] = plan.out.i0;
-  out_rect[1] = plan.out.j0;
-  out_rect[2] = region::height(plan.out);
-  out_rect[3] = region::width(plan.out);
+  write_rect(plan.out, out_rect);
   note_region_written(c, out_layer);
   return TE_OK;
 }
@@ -263,21 +235,17 @@ int te_time_median_fill_samples(te_ctx* c, const te_median_fill_params* p, int i
   }
   CtxLock lk(c);
   if (c->have_geo) HIP_TRY(hipSetDevice(c->device));
-  Call call;
+  Call call{};
   if (const int rc = prepare("te_time_median_fill_samples", c, &q, in_layer, out_layer, 0, c->have_geo ? c->geo.batch : 1, &call)) return rc;
   const size_t bytes = (size_t)c->geo.rows * c->geo.cols * (size_t)c->geo.batch * sizeof(float);
-  for (int k = -warmup; k < iters; ++k) {
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+  const auto body = [&]() -> int {
     if (p)
       HIP_TRY(median::launch(call.a, call.plan, c->stream));
     else
       HIP_TRY(hipMemcpyAsync(call.a.out, call.a.in, bytes, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(hipEventSynchronize(c->ev1));
-    float t = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&t, c->ev0, c->ev1));
-    if (k >= 0) ms[k] = t;
-  }
+    return TE_OK;
+  };
+  if (const int rc = time_samples(c, /*locked*/ true, warmup, iters, ms, [] { return TE_OK; }, body)) return rc;
   // out_layer now holds the fill (or the copy): the facts of an upload of those values
   if (p) {
     c->fill_mask_valid.assign((size_t)c->geo.batch, 1);

@@ -55,16 +55,12 @@ int window_table(const char* who, te_ctx* c, double rad, radius::Window* w, radi
 // checks, scratch and plan of one call; caller holds the lock and has made the device current.  With in_layer == out_layer
 // the kernels read a copy of the input, queued here.
 int prepare(const char* who, te_ctx* c, int op, double rad, int in_layer, int out_layer, int map0, int nmaps, Call* call) {
-  if (!c->have_geo) return fail(TE_ERR_NOT_READY, "%s: geometry not set", who);
-  if (!layer_known(c, out_layer)) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
-  if (map0 < 0 || nmaps <= 0 || map0 > c->geo.batch - nmaps) return fail(TE_ERR_INVALID_ARG, "%s: maps [%d,%d) of batch %d", who, map0, map0 + nmaps, c->geo.batch);
-  if (nmaps > 65535) return fail(TE_ERR_INVALID_ARG, "%s: %d maps in one call (at most 65535)", who, nmaps);
-  const float* in = nullptr;
-  if (const int rc = filter_input_layer(who, c, in_layer, &in)) return rc;
-  if (!layer_on_demand(c, out_layer) && !layer_ptr(c, out_layer))
-    return fail(TE_ERR_INVALID_ARG, "%s: the output layer %d has no memory yet", who, out_layer);
+  CallWhere at;
+  at.map0 = map0, at.nmaps = nmaps, at.max_maps = 65535;
+  if (const int rc = refused(who, c, layer_call::check(facts_of(c), in_layer, out_layer, map0, nmaps, at.max_maps), at)) return rc;
   if (in_layer != out_layer)
     if (const int rc = ensure_input_layer(c, out_layer)) return rc;  // (robot_slope exists from its first write on)
+  const float* const in = layer_ptr(c, in_layer);
   float* const out = layer_ptr(c, out_layer);
 
   const int rows = c->geo.rows, cols = c->geo.cols;
@@ -105,7 +101,7 @@ int te_run_radius_filter(te_ctx* c, int op, double rad, int in_layer, int out_la
   TraceRange tr("te_run_radius_filter");
   // (bit() of an id out of range is 0: te_ctx_state.h, layer_bit; prepare refuses the id under the lock)
   CtxLock lk(c, /*beside_prefetch*/ true, bit(in_layer) | bit(out_layer));
-  Call call;
+  Call call{};
   if (c->have_geo) HIP_TRY(hipSetDevice(c->device));
   if (const int rc = prepare("te_run_radius_filter", c, op, rad, in_layer, out_layer, map0, nmaps, &call)) return rc;
   c->radius_counts_valid = false;
@@ -127,7 +123,7 @@ int te_run_radius_filter_region(te_ctx* c, int op, double rad, int in_layer, int
   if (const int rc = region_filter_layers(who, c, in_layer, out_layer, map, row0, col0, h, w, &in, &out)) return rc;
   const int rows = c->geo.rows, cols = c->geo.cols;
   // (the table of the last call with this radius and resolution is kept: nothing is rebuilt from tick to tick)
-  Call call;
+  Call call{};
   radius::Shape shape;
   if (const int rc = window_table(who, c, radius::bounded_radius(rad, c->geo.res, rows, cols), &call.w, &shape)) return rc;
   const region::Rect dirty = {row0, col0, row0 + h, col0 + w};
@@ -142,10 +138,7 @@ int te_run_radius_filter_region(te_ctx* c, int op, double rad, int in_layer, int
   HIP_TRY(hipMemsetAsync(call.a.counts, 0, 2 * sizeof(unsigned long long), c->stream));
   HIP_TRY(radius::launch_region(c->geo, call.w, call.a, plan, c->stream));
   c->radius_counts_valid = true;
-  out_rect[0] = plan.out.i0;
-  out_rect[1] = plan.out.j0;
-  out_rect[2] = region::height(plan.out);
-  out_rect[3] = region::width(plan.out);
+  write_rect(plan.out, out_rect);
   note_region_written(c, out_layer);
   return TE_OK;
 }
@@ -154,13 +147,7 @@ int te_radius_filter_stats(te_ctx* c, uint64_t counts[2]) {
   if (!c || !counts) return fail(TE_ERR_INVALID_ARG, "te_radius_filter_stats: NULL");
   CtxLock lk(c);
   if (!c->radius_counts_valid || !c->cmem.radius_counts.p) return fail(TE_ERR_NOT_READY, "te_radius_filter_stats: no te_run_radius_filter has run on this context");
-  HIP_TRY(hipSetDevice(c->device));
-  unsigned long long h[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(h, c->cmem.radius_counts.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  counts[0] = h[0];
-  counts[1] = h[1];
-  return TE_OK;
+  return read_block_counts(c, c->cmem.radius_counts, counts);
 }
 
 int te_time_radius_filter_samples(te_ctx* c, int op, double rad, int in_layer, int out_layer, int warmup, int iters, float* ms) {
@@ -169,23 +156,22 @@ int te_time_radius_filter_samples(te_ctx* c, int op, double rad, int in_layer, i
   if (const int rc = check_args("te_time_radius_filter_samples", op, rad, true)) return rc;
   CtxLock lk(c);
   if (c->have_geo) HIP_TRY(hipSetDevice(c->device));
-  Call call;
+  Call call{};
   if (const int rc = prepare("te_time_radius_filter_samples", c, op ? op : TE_RADIUS_MIN, rad, in_layer, out_layer, 0, c->have_geo ? c->geo.batch : 1, &call)) return rc;
   const size_t bytes = (size_t)c->geo.rows * c->geo.cols * (size_t)c->geo.batch * sizeof(float);
   c->radius_counts_valid = false;
-  for (int k = -warmup; k < iters; ++k) {
+  const auto clear = [&]() -> int {
     HIP_TRY(hipMemsetAsync(call.a.counts, 0, 2 * sizeof(unsigned long long), c->stream));
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    return TE_OK;
+  };
+  const auto body = [&]() -> int {
     if (op)
       HIP_TRY(radius::launch(c->geo, call.w, call.a, call.plan, c->stream));
     else
       HIP_TRY(hipMemcpyAsync(call.a.out, call.a.in, bytes, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(hipEventSynchronize(c->ev1));
-    float t = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&t, c->ev0, c->ev1));
-    if (k >= 0) ms[k] = t;
-  }
+    return TE_OK;
+  };
+  if (const int rc = time_samples(c, /*locked*/ true, warmup, iters, ms, clear, body)) return rc;
   c->radius_counts_valid = op != 0;
   // out_layer now holds the result (or the copy): the facts of an upload of those values
   return note_layer_written(c, out_layer);

@@ -592,6 +592,52 @@ float* layer_ptr(te_ctx* c, int layer) {
   }
 }
 
+layer_call::Facts facts_of(const te_ctx* c) {
+  layer_call::Facts f;
+  f.have_geo = c->have_geo;
+  f.batch = c->geo.batch;
+  f.rows = c->geo.rows;
+  f.cols = c->geo.cols;
+  for (int id = 0; id < TE_LAYER_COUNT + TE_MAX_USER_LAYERS; ++id)
+    if (layer_ptr(const_cast<te_ctx*>(c), id)) f.has_memory |= bit(id);  // (layer_ptr only reads)
+  f.layers_written = c->st.layers_written();
+  f.have_robot_slope = c->st.have_robot_slope();
+  f.have_elev = c->st.have_elev();
+  f.user_added = c->user.mask();
+  return f;
+}
+
+int refused(const char* who, const te_ctx* c, const layer_call::Verdict& v, const CallWhere& at) {
+  switch (v.rule) {
+    case layer_call::kAccepted: return TE_OK;
+    case layer_call::kNoGeometry: return fail(v.code, "%s: geometry not set", who);
+    case layer_call::kBadOutput: return fail(v.code, "%s: bad output layer %d", who, v.id);
+    case layer_call::kBadMaps: return fail(v.code, "%s: maps [%d,%d) of batch %d", who, at.map0, at.map0 + at.nmaps, c->geo.batch);
+    case layer_call::kTooManyMaps: return fail(v.code, "%s: %d maps in one call (at most %d)", who, at.nmaps, at.max_maps);
+    case layer_call::kBadInput: return fail(v.code, "%s: bad input layer %d", who, v.id);
+    case layer_call::kInputAbsent: return fail(v.code, "%s: the input layer %d does not exist yet", who, v.id);
+    case layer_call::kOutputNoMemory: return fail(v.code, "%s: the output layer %d has no memory yet", who, v.id);
+    case layer_call::kBadMap: return fail(v.code, "%s: map %d of batch %d", who, at.map0, c->geo.batch);
+    case layer_call::kRegionInPlace:
+      return fail(v.code, "%s: in_layer == out_layer (%d): a region call reads the neighbours of the rectangle as they were before "
+                          "the filter, and in place their earlier input is gone; keep the unfiltered values in a layer of their own", who, v.id);
+    case layer_call::kBadRect:
+      return fail(v.code, "%s: rectangle (%d,%d)+(%d,%d) outside %dx%d", who, at.row0, at.col0, at.h, at.w, c->geo.rows, c->geo.cols);
+    case layer_call::kOperandAbsent: return fail(v.code, "%s: the layer %s does not exist yet", who, layer_name_of(c, v.id));
+  }
+  return fail(TE_ERR_INVALID_ARG, "%s: refused", who);  // (never: every rule has its case)
+}
+
+int read_block_counts(te_ctx* c, const DevBuf& counts, uint64_t out[2]) {
+  HIP_TRY(hipSetDevice(c->device));
+  unsigned long long h[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(h, counts.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  out[0] = h[0];
+  out[1] = h[1];
+  return TE_OK;
+}
+
 int readable_layer(const char* who, te_ctx* c, int layer, float** out) {
   float* const p = layer_ptr(c, layer);
   if (c->user.added(layer) && (!p || !(c->st.layers_written() & bit(layer))))

@@ -21,29 +21,42 @@ struct Call {
   wexpr::Plan plan;
 };
 
-// c: the context whose user layers are names too (a user in_layer is the window's variable), or NULL
+// c: the context whose user layers are names too (a user in_layer is the window's variable; an id that is no layer is
+// refused here, before the text), or NULL
 int compile(const char* who, const char* text, int in_layer, expr::Program* p, te_ctx* c = nullptr) {
   char err[200];
   UserNames un;
-  if (c) snapshot_user_names(c, &un);
-  if (c && in_layer >= TE_LAYER_COUNT && !un.has(in_layer)) return fail(TE_ERR_INVALID_ARG, "%s: bad input layer %d", who, in_layer);
+  if (c) {
+    snapshot_user_names(c, &un);
+    layer_call::Facts ids;  // (the ids alone: the layers are judged under the lock)
+    ids.user_added = un.copy.mask();
+    if (!layer_call::known(ids, in_layer)) return refused(who, c, {TE_ERR_INVALID_ARG, layer_call::kBadInput, in_layer, false});
+  }
   const int rc = expr::compile_window(text, in_layer, p, err, sizeof(err), un.v, un.n);
   return rc == TE_OK ? TE_OK : fail(rc, "%s: %s", who, err);
+}
+
+// the kernel's arguments: `in` / `out` at the first map of `nmaps`; after cmem.window_counts.once
+void fill_args(te_ctx* c, const te_window_expr_params* p, const float* in, float* out, int nmaps, wexpr::Args* a) {
+  a->in = in;
+  a->out = out;
+  a->counts = c->cmem.window_counts.as<unsigned long long>();
+  a->rows = c->geo.rows;
+  a->cols = c->geo.cols;
+  a->nmaps = nmaps;
+  a->edge = p->edge_handling;
+  a->compute_empty_cells = p->compute_empty_cells != 0;
 }
 
 // checks, scratch and plan of one call; caller holds the lock and has made the device current.  With in_layer == out_layer
 // the kernel reads a copy of the input, queued here.
 int prepare(const char* who, te_ctx* c, const te_window_expr_params* p, int in_layer, int out_layer, int map0, int nmaps, Call* call) {
-  if (!c->have_geo) return fail(TE_ERR_NOT_READY, "%s: geometry not set", who);
-  if (!layer_known(c, out_layer)) return fail(TE_ERR_INVALID_ARG, "%s: bad output layer %d", who, out_layer);
-  if (map0 < 0 || nmaps <= 0 || map0 > c->geo.batch - nmaps) return fail(TE_ERR_INVALID_ARG, "%s: maps [%d,%d) of batch %d", who, map0, map0 + nmaps, c->geo.batch);
-  if (nmaps > 65535) return fail(TE_ERR_INVALID_ARG, "%s: %d maps in one call (at most 65535)", who, nmaps);
-  const float* in = nullptr;
-  if (const int rc = filter_input_layer(who, c, in_layer, &in)) return rc;
-  if (!layer_on_demand(c, out_layer) && !layer_ptr(c, out_layer))
-    return fail(TE_ERR_INVALID_ARG, "%s: the output layer %d has no memory yet", who, out_layer);
+  CallWhere at;
+  at.map0 = map0, at.nmaps = nmaps, at.max_maps = 65535;
+  if (const int rc = refused(who, c, layer_call::check(facts_of(c), in_layer, out_layer, map0, nmaps, at.max_maps), at)) return rc;
   if (in_layer != out_layer)
     if (const int rc = ensure_input_layer(c, out_layer)) return rc;  // (robot_slope exists from its first write on)
+  const float* const in = layer_ptr(c, in_layer);
   float* const out = layer_ptr(c, out_layer);
 
   const int rows = c->geo.rows, cols = c->geo.cols;
@@ -62,14 +75,7 @@ int prepare(const char* who, te_ctx* c, const te_window_expr_params* p, int in_l
     HIP_TRY(hipMemcpyAsync(copy.p, in_first, total * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     in_first = copy.as<float>();
   }
-  call->a.in = in_first;
-  call->a.out = out + cells * map0;
-  call->a.counts = c->cmem.window_counts.as<unsigned long long>();
-  call->a.rows = rows;
-  call->a.cols = cols;
-  call->a.nmaps = nmaps;
-  call->a.edge = p->edge_handling;
-  call->a.compute_empty_cells = p->compute_empty_cells != 0;
+  fill_args(c, p, in_first, out + cells * map0, nmaps, &call->a);
   return TE_OK;
 }
 
@@ -116,20 +122,14 @@ int te_window_expr_check(const char* text, int in_layer, te_expr_info* info) {
   if (!text) return fail(TE_ERR_INVALID_ARG, "te_window_expr_check: NULL");
   expr::Program p;
   if (const int rc = compile("te_window_expr_check", text, in_layer, &p)) return rc;
-  if (info) {
-    info->n_instructions = p.n_code;
-    info->layer_mask = expr::layer_mask(p);
-    info->n_reductions = p.n_red;
-    info->stack_depth = p.stack_depth;
-  }
+  if (info) fill_expr_info(p, info);
   return TE_OK;
 }
 
 int te_run_window_expression(te_ctx* c, const te_window_expr_params* p, const char* text, int in_layer, int out_layer, int map0, int nmaps) {
   if (!c || !p || !text) return fail(TE_ERR_INVALID_ARG, "te_run_window_expression: NULL");
   if (const int rc = te_window_expr_params_validate(p)) return rc;
-  if (in_layer < 0) return fail(TE_ERR_INVALID_ARG, "te_run_window_expression: bad input layer %d", in_layer);
-  Call call;
+  Call call{};
   if (const int rc = compile("te_run_window_expression", text, in_layer, &call.prog, c)) return rc;
   TraceRange tr("te_run_window_expression");
   CtxLock lk(c, /*beside_prefetch*/ true, bit(in_layer) | bit(out_layer));
@@ -147,8 +147,7 @@ int te_run_window_expression_region(te_ctx* c, const te_window_expr_params* p, c
   const char* const who = "te_run_window_expression_region";
   if (!c || !p || !text || !out_rect) return fail(TE_ERR_INVALID_ARG, "%s: NULL", who);
   if (const int rc = te_window_expr_params_validate(p)) return rc;
-  if (in_layer < 0) return fail(TE_ERR_INVALID_ARG, "%s: bad input layer %d", who, in_layer);
-  Call call;
+  Call call{};
   if (const int rc = compile(who, text, in_layer, &call.prog, c)) return rc;
   TraceRange tr(who);
   CtxLock lk(c, /*beside_prefetch*/ true, bit(in_layer) | bit(out_layer));
@@ -167,22 +166,12 @@ int te_run_window_expression_region(te_ctx* c, const te_window_expr_params* p, c
   const wexpr::RegionPlan plan = wexpr::region_plan(c->geo.rows, c->geo.cols, win, call.prog.n_red, call.prog.n_outer, c->opt_window_expr_route, dirty);
   HIP_TRY(c->cmem.window_counts.once(2 * sizeof(unsigned long long)));
   call.plan = plan.k;
-  call.a.in = in;
-  call.a.out = out;
-  call.a.counts = c->cmem.window_counts.as<unsigned long long>();
-  call.a.rows = c->geo.rows;
-  call.a.cols = c->geo.cols;
-  call.a.nmaps = 1;
-  call.a.edge = p->edge_handling;
-  call.a.compute_empty_cells = p->compute_empty_cells != 0;
+  fill_args(c, p, in, out, 1, &call.a);
   c->window_counts_valid = false;
   HIP_TRY(hipMemsetAsync(call.a.counts, 0, 2 * sizeof(unsigned long long), c->stream));
   HIP_TRY(wexpr::launch(call.prog, call.a, call.plan, c->stream));
   c->window_counts_valid = true;
-  out_rect[0] = plan.out.i0;
-  out_rect[1] = plan.out.j0;
-  out_rect[2] = region::height(plan.out);
-  out_rect[3] = region::width(plan.out);
+  write_rect(plan.out, out_rect);
   note_region_written(c, out_layer);
   return TE_OK;
 }
@@ -192,23 +181,18 @@ int te_window_expression_stats(te_ctx* c, uint64_t counts[2]) {
   CtxLock lk(c);
   if (!c->window_counts_valid || !c->cmem.window_counts.p)
     return fail(TE_ERR_NOT_READY, "te_window_expression_stats: no te_run_window_expression has run on this context");
-  HIP_TRY(hipSetDevice(c->device));
-  unsigned long long h[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(h, c->cmem.window_counts.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  counts[0] = h[0];
-  counts[1] = h[1];
-  return TE_OK;
+  return read_block_counts(c, c->cmem.window_counts, counts);
 }
 
 int te_time_window_expression_samples(te_ctx* c, const te_window_expr_params* p, const char* text, int in_layer, int out_layer, int warmup, int iters, float* ms) {
   if (!c || !ms || iters <= 0 || warmup < 0) return fail(TE_ERR_INVALID_ARG, "te_time_window_expression_samples: bad argument");
   if (in_layer == out_layer) return fail(TE_ERR_INVALID_ARG, "te_time_window_expression_samples: the input layer must survive the repeats (in_layer == out_layer)");
-  if (in_layer < 0 || in_layer >= TE_LAYER_COUNT) return fail(TE_ERR_INVALID_ARG, "te_time_window_expression_samples: bad input layer %d", in_layer);
+  if (!layer_call::known(layer_call::Facts(), in_layer))  // (a reference layer: the text is compiled without the user names)
+    return refused("te_time_window_expression_samples", c, {TE_ERR_INVALID_ARG, layer_call::kBadInput, in_layer, false});
   const bool copy = !p || !text;  // the floor: a device copy of the layer
   te_window_expr_params q;
   te_window_expr_params_default(&q);
-  Call call;
+  Call call{};
   if (!copy) {
     if (const int rc = te_window_expr_params_validate(p)) return rc;
     q = *p;
@@ -219,19 +203,18 @@ int te_time_window_expression_samples(te_ctx* c, const te_window_expr_params* p,
   if (const int rc = prepare("te_time_window_expression_samples", c, &q, in_layer, out_layer, 0, c->have_geo ? c->geo.batch : 1, &call)) return rc;
   const size_t bytes = (size_t)c->geo.rows * c->geo.cols * (size_t)c->geo.batch * sizeof(float);
   c->window_counts_valid = false;
-  for (int k = -warmup; k < iters; ++k) {
+  const auto clear = [&]() -> int {
     HIP_TRY(hipMemsetAsync(call.a.counts, 0, 2 * sizeof(unsigned long long), c->stream));
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    return TE_OK;
+  };
+  const auto body = [&]() -> int {
     if (!copy)
       HIP_TRY(wexpr::launch(call.prog, call.a, call.plan, c->stream));
     else
       HIP_TRY(hipMemcpyAsync(call.a.out, call.a.in, bytes, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(hipEventSynchronize(c->ev1));
-    float t = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&t, c->ev0, c->ev1));
-    if (k >= 0) ms[k] = t;
-  }
+    return TE_OK;
+  };
+  if (const int rc = time_samples(c, /*locked*/ true, warmup, iters, ms, clear, body)) return rc;
   c->window_counts_valid = !copy;
   // out_layer now holds the result (or the copy): the facts of an upload of those values
   return note_layer_written(c, out_layer);
