@@ -63,6 +63,9 @@
  *   te_run_window_expression / te_window_expr_check / te_window_expression_stats
  *                        <- gridMapFilters/SlidingWindowMathExpressionFilter (grid_map_filters; restated, see below): an
  *                           EigenLab expression over a square window around every cell (local deviation, box mean, relief)
+ *   te_run_distance / te_run_distance_region / te_distance_stats
+ *                        <- no filter of grid_map: the clearance layer a planner asks a traversability map for, the exact
+ *                           distance of every cell to the nearest untraversable one (defined below, not restated)
  *
  * Data contract (identical to grid_map::Matrix = Eigen::MatrixXf): float32, COLUMN-major,
  * element (row i, col j) of map m at ptr[m*rows*cols + j*rows + i]; invalid cell = non-finite.
@@ -259,6 +262,9 @@ int te_get_params(te_ctx* ctx, te_params* p);
  *   te_run_chain_region returns TE_ERR_UNSUPPORTED: the roughness route on given normals is whole-map only, and a region form of
  *     it is not built. */
 #define TE_OPT_NORMALS_ALGORITHM 13
+/* te_run_distance: 0 (default) the route of pass 2 the plan names (csrc/te_distance_plan.h), 1 the tiled route wherever its
+ * tile fits in LDS, 2 the route of any reach always.  The layers are identical under every value, bit for bit. */
+#define TE_OPT_DISTANCE_ROUTE 14
 int te_set_option(te_ctx* ctx, int option, int value);
 /* The face flags a footprint run would be given now (tests, diagnostics): batch x ceil(cols / 4) x ceil(rows / 64) bytes, the
  * flag of 64 cells along the rows fastest; `bytes` must be exactly that.  TE_ERR_NOT_READY while they are unknown or
@@ -1099,6 +1105,47 @@ int te_radius_filter_stats(te_ctx* ctx, uint64_t counts[2]);
 /* Measurement aid (tools/radius_filter_bench.py), like te_time_median_fill_samples: `iters` launches over the whole batch, one
  * HIP event pair each, after `warmup` untimed ones; in_layer != out_layer is required.  op = 0: a device copy of the layer. */
 int te_time_radius_filter_samples(te_ctx* ctx, int op, double radius, int in_layer, int out_layer, int warmup, int iters, float* ms);
+
+/* ---- The clearance layer: the exact Euclidean distance of every cell to the nearest seed of its map ----
+ * Unlike the filters above this one is DEFINED here, not restated: it is arithmetic, and a brute-force loop over all pairs
+ * (tests/ref_py/distance_ref.py) pins every bit.  Unsigned, one threshold, 2-D.
+ *   1. seeds           a cell v of in_layer is a seed iff v < (float)threshold (TE_DISTANCE_BELOW) or v > (float)threshold
+ *      (TE_DISTANCE_ABOVE): ThresholdFilter's comparisons, so v == threshold is a seed in neither mode.  A NaN cell is a seed
+ *      iff TE_DISTANCE_NAN_IS_SEED is or-ed in; without it a NaN cell is an ordinary cell and gets its distance;
+ *   2. d2              for every cell the smallest di * di + dj * dj (an integer, in cells) over the seeds of the same map;
+ *   3. cap             res = the map's resolution (double); cap2 = the largest integer k with
+ *      (double)k * (res * res) <= max_distance * max_distance; the reach R = floor(sqrt(cap2)) cells;
+ *   4. output          a seed gets 0.0f; a cell with d2 <= cap2 gets (float)(sqrt((double)d2) * res); every other cell -- a map
+ *      without a seed included -- gets (float)max_distance.  The output never holds a NaN.  With cell-centred discs, "the disc
+ *      of radius r <= max_distance around this cell holds a seed" is output <= r;
+ *   5. parameters      max_distance must be finite and positive with R <= 32767, the threshold finite (TE_ERR_BAD_PARAM + message).
+ * Two separable passes, both exact in integers; nothing is decided in floating point before the final sqrt. */
+#define TE_DISTANCE_BELOW 1      /* seed iff v < (float)threshold   (ThresholdFilter's comparisons) */
+#define TE_DISTANCE_ABOVE 2      /* seed iff v > (float)threshold */
+#define TE_DISTANCE_NAN_IS_SEED 4 /* or-ed in: a NaN cell is a seed too; without it a NaN cell is never one */
+/* out_layer = the distance layer of in_layer for maps [map0, map0 + nmaps) of the batch; the other maps are untouched.  Any two
+ * float layers of the context, user layers included; in_layer == out_layer needs no copy.  Identical run after run and between
+ * the routes (TE_OPT_DISTANCE_ROUTE).  Asynchronous on the context's stream unless out_layer is the elevation.
+ *   TE_ERR_INVALID_ARG (also: a mode that is neither comparison), TE_ERR_NOT_READY, the context afterwards and the joining of a
+ *   prefetch: as te_run_radius_filter.  TE_ERR_BAD_PARAM: 5.  TE_ERR_UNSUPPORTED: the scratch of the first pass (2 bytes per
+ *   cell of the call) does not fit in device memory. */
+int te_run_distance(te_ctx* ctx, int mode, double threshold, double max_distance, int in_layer, int out_layer, int map0, int nmaps);
+/* The distance layer after in_layer changed inside the rectangle of map `map` only: the contract of te_run_radius_filter_region
+ * with the reach R of 3.  out_rect = the rectangle grown by R and clamped to the map; what the call writes there is bit for bit
+ * what the whole-map call would write, and no other cell is touched.  It reads no cell of in_layer farther than 2 R from the
+ * rectangle, and no launch and no scratch is sized by the map.  in_layer == out_layer: TE_ERR_INVALID_ARG. */
+int te_run_distance_region(te_ctx* ctx, int mode, double threshold, double max_distance, int in_layer, int out_layer, int map, int row0, int col0, int h,
+                           int w, int out_rect[4]);
+/* Which route the second pass of the last te_run_distance or te_run_distance_region took: counts[0] = its workgroups on the
+ * tiled route, counts[1] = on the route of any reach.  TE_ERR_NOT_READY before any call. */
+int te_distance_stats(te_ctx* ctx, uint64_t counts[2]);
+/* Measurement aid (tools/distance_bench.py), like te_time_radius_filter_samples: `iters` launches over the whole batch, one HIP
+ * event pair each, after `warmup` untimed ones; in_layer != out_layer is required.  mode = 0: a device copy of the layer.  One
+ * of the two bits below or-ed into a mode times that pass alone (the second on the column distances of one untimed first
+ * pass); out_layer then holds no distance layer if it is the first. */
+#define TE_DISTANCE_TIME_PASS1 0x100
+#define TE_DISTANCE_TIME_PASS2 0x200
+int te_time_distance_samples(te_ctx* ctx, int mode, double threshold, double max_distance, int in_layer, int out_layer, int warmup, int iters, float* ms);
 
 /* ---- gridMapFilters/SlidingWindowMathExpressionFilter on the device: an expression over a window around every cell ----
  * Like the median fill and the radius filters this contract is RESTATED from memory of grid_map_filters and EigenLab; nothing

@@ -38,6 +38,11 @@ EDGE_INSIDE, EDGE_CROP, EDGE_EMPTY, EDGE_MEAN = 0, 1, 2, 3  # te_window_expr_par
 EDGE_HANDLING = {"inside": EDGE_INSIDE, "crop": EDGE_CROP, "empty": EDGE_EMPTY, "mean": EDGE_MEAN}
 RADIUS_MEAN, RADIUS_MIN = 1, 2  # te_run_radius_filter: gridMapFilters/MeanInRadiusFilter, MinInRadiusFilter
 OPT_NORMALS_ALGORITHM = 13  # NormalVectorsFilter: 0 the area method (default), 1 the raster method (finite differences of the four neighbours; changes the layers)
+OPT_DISTANCE_ROUTE = 14  # te_run_distance: 0 by plan, 1 the tiled route wherever its tile fits in LDS, 2 the route of any reach always (identical layers)
+# te_run_distance: which cells are seeds (NAN_IS_SEED is or-ed in); the two TIME bits are te_time_distance_samples' alone
+DISTANCE_BELOW, DISTANCE_ABOVE, DISTANCE_NAN_IS_SEED = 1, 2, 4
+DISTANCE_TIME_PASS1, DISTANCE_TIME_PASS2 = 0x100, 0x200
+DISTANCE_MODES = {"below": DISTANCE_BELOW, "above": DISTANCE_ABOVE}
 OPT_FILTER_ANY_RADIUS = 8  # filter discs: 0 up to 32 cells (TE_ERR_UNSUPPORTED above), 1 any radius, 2 the route of any radius for every disc
 
 # every symbol include/travgpu.h declares (tests/test_cabi.py checks the library exports them all)
@@ -61,6 +66,7 @@ SYMBOLS = ["te_params_default", "te_params_validate", "te_device_count", "te_cre
            "te_median_fill_params_default", "te_median_fill_params_validate", "te_run_median_fill", "te_run_median_fill_region", "te_download_fill_mask",
            "te_time_median_fill_samples",
            "te_run_radius_filter", "te_run_radius_filter_region", "te_radius_filter_stats", "te_time_radius_filter_samples",
+           "te_run_distance", "te_run_distance_region", "te_distance_stats", "te_time_distance_samples",
            "te_window_expr_params_default", "te_window_expr_params_validate", "te_window_expr_check", "te_run_window_expression", "te_run_window_expression_region",
            "te_window_expression_stats", "te_time_window_expression_samples",
            "te_add_layer", "te_remove_layer", "te_layer_id", "te_layer_name",
@@ -333,6 +339,10 @@ def load():
         L.te_run_radius_filter.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int]
         L.te_radius_filter_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.te_time_radius_filter_samples.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.te_run_distance.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.te_run_distance_region.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.te_distance_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.te_time_distance_samples.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
         wp = C.POINTER(TeWindowExprParams)
         L.te_window_expr_params_default.argtypes = [wp]
         L.te_window_expr_params_validate.argtypes = [wp]
@@ -358,6 +368,10 @@ def load():
         L.te_version.restype = C.c_char_p
         _lib = L
     return _lib
+
+
+def _distance_mode(mode, nan_is_seed=False):
+    return int(DISTANCE_MODES.get(mode, mode)) | (DISTANCE_NAN_IS_SEED if nan_is_seed else 0)
 
 
 def _check(rc):
@@ -1089,6 +1103,33 @@ class Context:
     def time_radius_filter_samples(self, op, radius, in_layer="elevation", out_layer="traversability_roughness", warmup=3, iters=50):
         """Device time of each of `iters` radius filters (op 0: device copies of the layer), in ms."""
         return self._time_samples(load().te_time_radius_filter_samples, (int(op), float(radius)), in_layer, out_layer, warmup, iters)
+
+    def run_distance(self, mode, threshold, max_distance, in_layer="traversability", out_layer=None, map0=0, nmaps=None, nan_is_seed=False):
+        """The clearance layer (te_run_distance): `out_layer` (default: `in_layer`, in place) = the exact distance in metres of every
+        cell of `in_layer` to the nearest seed of its map -- a cell below (mode DISTANCE_BELOW or "below") or above (DISTANCE_ABOVE,
+        "above") `threshold`, with nan_is_seed (or DISTANCE_NAN_IS_SEED or-ed into the mode) a NaN cell too -- capped at `max_distance`."""
+        lid = lambda name: self._lid(name)
+        nmaps = self.batch - map0 if nmaps is None else nmaps
+        _check(load().te_run_distance(self._h, _distance_mode(mode, nan_is_seed), float(threshold), float(max_distance), lid(in_layer),
+                                      lid(in_layer if out_layer is None else out_layer), int(map0), int(nmaps)))
+
+    def run_distance_region(self, mode, threshold, max_distance, in_layer, out_layer, map_index, row0, col0, h, w, nan_is_seed=False):
+        """te_run_distance_region: `out_layer` = the distance layer of `in_layer` after it changed inside the rectangle only.
+        Returns (row0, col0, h, w) of the rectangle written: the given one grown by the cap in cells."""
+        lid = lambda name: self._lid(name)
+        rect = (C.c_int * 4)()
+        _check(load().te_run_distance_region(self._h, _distance_mode(mode, nan_is_seed), float(threshold), float(max_distance), lid(in_layer), lid(out_layer),
+                                             int(map_index), int(row0), int(col0), int(h), int(w), rect))
+        return tuple(int(v) for v in rect)
+
+    def distance_stats(self):
+        """(workgroups of the second pass on the tiled route, on the route of any reach) of the last run_distance(_region)."""
+        return self._block_counts(load().te_distance_stats)
+
+    def time_distance_samples(self, mode, threshold, max_distance, in_layer="traversability", out_layer="traversability_roughness", warmup=3, iters=50):
+        """Device time of each of `iters` distance layers (mode 0: device copies of the layer; DISTANCE_TIME_PASS1 / _PASS2 or-ed in:
+        that pass alone), in ms."""
+        return self._time_samples(load().te_time_distance_samples, (int(mode), float(threshold), float(max_distance)), in_layer, out_layer, warmup, iters)
 
     def run_window_expression(self, text, params, in_layer="elevation", out_layer=None, map0=0, nmaps=None):
         """gridMapFilters/SlidingWindowMathExpressionFilter on the device (te_run_window_expression): `out_layer` (default:

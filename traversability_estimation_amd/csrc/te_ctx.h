@@ -101,6 +101,8 @@ struct te_ctx {
     te::DevBuf radius_copy;
     // te_run_window_expression (te_window_expr.hip): the copy of the input layer a call with in_layer == out_layer reads
     te::DevBuf window_copy;
+    // te_run_distance (te_distance.hip): the column distances of pass 1, 16 bits per cell of the rectangle pass 2 reads; grown
+    te::DevBuf distance_g;
     // te_move_map (te_move.hip): one float layer of one map, the out-of-place target of a shift (te_slab.h: move_scratch_bytes);
     // allocated by the first move that needs it
     te::DevBuf move_scratch;
@@ -162,6 +164,10 @@ struct te_ctx {
   // TE_OPT_WINDOW_EXPR_ROUTE (te_window_plan.h); whether a te_run_window_expression has left block counts
   int opt_window_expr_route = 0;
   bool window_counts_valid = false;
+  // TE_OPT_DISTANCE_ROUTE (te_distance_plan.h); the workgroups of pass 2 the last te_run_distance launched on either route
+  int opt_distance_route = 0;
+  unsigned long long distance_counts[2] = {0, 0};
+  bool distance_counts_valid = false;
   // face flags (te_face_flags.h): the bytes live in the slab; what they describe: te::CtxState::face_crit
   uint8_t* face_flags = nullptr;
   int opt_face_flags = 1;  // TE_OPT_FACE_FLAGS

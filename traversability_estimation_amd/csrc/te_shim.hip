@@ -1054,6 +1054,10 @@ int te_set_option(te_ctx* c, int option, int value) {
       if (value < 0 || value > 2) return fail(TE_ERR_INVALID_ARG, "te_set_option: TE_OPT_WINDOW_EXPR_ROUTE takes 0 (by plan), 1 (the separable route wherever allowed), 2 (the direct walk)");
       c->opt_window_expr_route = value;
       return TE_OK;  // (read by te_run_window_expression alone, which is never captured; identical layers either way)
+    case TE_OPT_DISTANCE_ROUTE:
+      if (value < 0 || value > 2) return fail(TE_ERR_INVALID_ARG, "te_set_option: TE_OPT_DISTANCE_ROUTE takes 0 (by plan), 1 (the tiled route wherever it fits), 2 (the route of any reach)");
+      c->opt_distance_route = value;
+      return TE_OK;  // (read by te_run_distance alone, which is never captured; identical layers either way)
     case TE_OPT_NORMALS_RANK_RULE:
       c->opt_rank_rule = value != 0;
       c->st.filter_option_changed();
