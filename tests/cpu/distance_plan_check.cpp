@@ -7,7 +7,8 @@
 //                 tiled route stages no more columns than its LDS holds;
 //   routines      column_nearest and row_min, driven over the plan's geometry exactly as the kernels drive them, against brute
 //                 force on every cell, with the steps of row_min counted.
-//   distance_plan_check route ROWS COLS MAX_DISTANCE RES OPTION [ROW0 COL0 H W]  prints the plan of a call.
+//   distance_plan_check route ROWS COLS MAX_DISTANCE RES OPTION [ROW0 COL0 H W]  prints the plan of a call: route, cap2, R, LDS bytes, the blocks
+//   of both passes, seg_chunks, the rectangle out, p1_segs, the rectangles g and in (each rectangle as row0 col0 h w).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -302,8 +303,10 @@ int main(int argc, char** argv) {
     region::Rect dirty = {0, 0, rows, cols};
     if (argc == 11) dirty = region::Rect{atoi(argv[7]), atoi(argv[8]), atoi(argv[7]) + atoi(argv[9]), atoi(argv[8]) + atoi(argv[10])};
     const Plan p = plan(rows, cols, cap2, R, opt, dirty);
-    printf("%s %u %d %zu %llu %llu %d %d %d %d %d\n", p.route == kRouteTiled ? "tiled" : "any", cap2, R, p.lds_bytes, p.p1_blocks, p.p2_blocks, p.seg_chunks,
+    printf("%s %u %d %zu %llu %llu %d %d %d %d %d", p.route == kRouteTiled ? "tiled" : "any", cap2, R, p.lds_bytes, p.p1_blocks, p.p2_blocks, p.seg_chunks,
            p.out.i0, p.out.j0, region::height(p.out), region::width(p.out));
+    printf(" %u %d %d %d %d %d %d %d %d\n", p.p1_segs, p.g.i0, p.g.j0, region::height(p.g), region::width(p.g), p.in.i0, p.in.j0, region::height(p.in),
+           region::width(p.in));
     return 0;
   }
   check_cap();

@@ -1,7 +1,8 @@
 """The plan of te_run_distance (csrc/te_distance_plan.h) and its per-cell routines (csrc/te_distance.h) on the CPU:
 tests/cpu/distance_plan_check.cpp checks the cap against its defining loop, the rectangles of the region call by single-seed flips,
 the owners of every cell under the launch geometry, and column_nearest / row_min against brute force -- plain and, as a
-stand-alone program, under the sanitizers; and every case of tests/distance_cases.py takes the route its GPU test claims."""
+stand-alone program, under the sanitizers; and every case of tests/distance_cases.py takes the route its GPU test claims, the tall
+ones their segments and the region cases their rectangles as well."""
 import os
 import subprocess
 
@@ -44,8 +45,9 @@ def route(exe, rows, cols, max_distance, opt, rect=()):
     f = out(exe, "route", rows, cols, float(max_distance), K.RES, opt, *rect).split()
     if f[0] == "refused":
         return None
+    assert len(f) == 20, f
     return dict(route=f[0], cap2=int(f[1]), R=int(f[2]), lds=int(f[3]), p1_blocks=int(f[4]), p2_blocks=int(f[5]), seg_chunks=int(f[6]),
-                out_rect=tuple(int(v) for v in f[7:11]))
+                out_rect=tuple(int(v) for v in f[7:11]), p1_segs=int(f[11]), g_rect=tuple(int(v) for v in f[12:16]), in_rect=tuple(int(v) for v in f[16:20]))
 
 
 @pytest.mark.parametrize("rows,cols,reach,opt,claim", K.ROUTE_CLAIMS)
@@ -55,6 +57,53 @@ def test_gpu_cases_take_the_route_they_claim(exe, rows, cols, reach, opt, claim)
     assert p["cap2"] == D.cap_cells(K.cap_for(reach), K.RES)[0]
     assert p["p2_blocks"] == -(-rows // 64) * -(-cols // 64)
     assert (p["lds"] == K.staged_bytes(cols, reach)) if claim == "tiled" else p["lds"] == 0
+
+
+@pytest.mark.parametrize("rows,cols,reach,opt,claim,lds,seg_chunks,p1_segs", K.TALL_CASES)
+def test_tall_cases_take_the_route_and_the_segments_they_claim(exe, rows, cols, reach, opt, claim, lds, seg_chunks, p1_segs):
+    p = route(exe, rows, cols, K.cap_for(reach), opt)
+    assert p["route"] == claim and p["R"] == reach
+    assert p["cap2"] == D.cap_cells(K.cap_for(reach), K.RES)[0]
+    assert p["p2_blocks"] == -(-rows // 64) * -(-cols // 64)
+    assert p["lds"] == (K.staged_bytes(cols, reach) if claim == "tiled" else 0)
+    if lds is not None:
+        assert p["lds"] == lds
+    if seg_chunks is not None:
+        assert (p["seg_chunks"], p["p1_segs"]) == (seg_chunks, p1_segs)
+        assert p["p1_segs"] > 1 and (p1_segs - 1) * seg_chunks * 64 < rows <= p1_segs * seg_chunks * 64
+        assert p["p1_blocks"] == p1_segs * -(-cols // 4)
+    assert p["out_rect"] == p["g_rect"] == p["in_rect"] == (0, 0, rows, cols)
+
+
+def test_the_lds_limit_is_met_exactly_and_the_plan_route_turns_at_its_reach(exe):
+    by = {(r, c, reach, opt): (claim, lds) for (r, c, reach, opt, claim, lds, _s, _n) in K.TALL_CASES}
+    assert by[(3, 600, 224, 1)] == ("tiled", 64 * 1024) and by[(3, 600, 225, 1)] == ("any", 0) and by[(3, 600, 224, 0)] == ("any", 0)
+    assert by[(70, 200, 64, 0)][0] == "tiled" and by[(70, 200, 65, 0)][0] == "any"
+    assert K.staged_bytes(600, 224) == 64 * 1024 and K.staged_bytes(600, 225) > 64 * 1024
+
+
+@pytest.mark.parametrize("name", sorted(K.REGION_TALL))
+def test_tall_region_cases_have_the_rectangles_they_claim(exe, name):
+    case = K.REGION_TALL[name]
+    (rows, cols), reach = case["shape"], case["reach"]
+    for opt in (0, 1):
+        whole = route(exe, rows, cols, K.cap_for(reach), opt)
+        assert whole["seg_chunks"] == case["seg_chunks"] and whole["p1_segs"] > 1
+        for (r0, c0, h, w), claim in case["rects"]:
+            p = route(exe, rows, cols, K.cap_for(reach), opt, (r0, c0, h, w))
+            i0, j0, i1, j1 = max(0, r0 - reach), max(0, c0 - reach), min(rows, r0 + h + reach), min(cols, c0 + w + reach)
+            assert p["out_rect"] == (i0, j0, i1 - i0, j1 - j0)
+            assert p["g_rect"][0] == i0 and p["g_rect"][2] == i1 - i0 and p["in_rect"][0] == max(0, i0 - reach)
+            if "out" in claim:
+                assert p["out_rect"] == claim["out"]
+            if "g_i0" in claim:
+                assert (p["g_rect"][0], p["in_rect"][0]) == (claim["g_i0"], claim["in_i0"])
+            if "p1_segs" in claim:
+                assert (p["seg_chunks"], p["p1_segs"]) == (claim["plan_seg_chunks"], claim["p1_segs"])
+            assert p["route"] == ("tiled" if opt == 1 or reach <= 64 else "any")
+    # case A's first rectangle: its g starts inside a chunk, and its pre-halo is two chunks of which in.i0 masks a part
+    claim = K.REGION_TALL["A"]["rects"][0][1]
+    assert claim["g_i0"] % 64 != 0 and 64 < claim["g_i0"] - claim["in_i0"] <= 128 and (claim["g_i0"] - claim["in_i0"]) % 64 != 0
 
 
 def test_the_cap_is_the_reference_s(exe):

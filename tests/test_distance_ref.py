@@ -1,6 +1,9 @@
-"""tests/ref_py/distance_ref.py -- the definition of te_run_distance as a brute-force loop -- held to vectors computed by hand."""
+"""tests/ref_py/distance_ref.py -- the definition of te_run_distance as a brute-force loop -- held to vectors computed by hand; and the
+inputs of the tall and the edge cases of tests/distance_cases.py held, by that definition alone, to what they are named for."""
 import numpy as np
+import pytest
 
+from tests import distance_cases as K
 from tests.ref_py import distance_ref as D
 
 RES = 0.05
@@ -91,3 +94,87 @@ def test_the_cap_cuts_at_cap2():
     # R = 0: only the seeds themselves are within the cap
     e = D.distance(a, D.BELOW, 0.5, 0.01, RES)
     assert e[0, 0] == 0.0 and (e[0, 1:] == f32(0.01)).all()
+
+
+# --- the inputs of the tall cases of tests/distance_cases.py reach the branches they are named for (no GPU, nothing of csrc/) ---
+
+def column_nearest_rows(seed):
+    """Per cell of a [rows, cols] seed array: the distance along its column to the nearest seed before (or at) it and behind (or at)
+    it, and those seeds' rows; no seed: distance a large number."""
+    rows, cols = seed.shape
+    big = 1 << 40
+    idx = np.arange(rows)[:, None]
+    last = np.maximum.accumulate(np.where(seed, idx, -big), axis=0)
+    nxt = np.minimum.accumulate(np.where(seed, idx, big)[::-1], axis=0)[::-1]
+    return idx - last, last, nxt - idx, nxt
+
+
+def tall_inputs(rows, cols, reach, seg_chunks):
+    out = []
+    for a in K.designed(rows, cols, reach, seg_chunks, K.BELOW):
+        seed = D.seeds(a, K.BELOW, K.THRESHOLD)
+        out.append((seed, D.squared_cells(seed.T).T))  # (the definition is symmetric: the short axis goes first)
+    return out
+
+
+@pytest.mark.parametrize("rows,cols,reach,seg_chunks", K.TALL_SEGMENTED)
+def test_tall_inputs_reach_the_branches_they_are_named_for(rows, cols, reach, seg_chunks):
+    """Conditions on the inputs alone.  Each one asks for a cell whose column distance is also its distance in the map (d2 of the
+    definition equals it squared), so that the output shows what pass 1 made of it."""
+    b = seg_chunks * 64
+    assert rows > b
+    before_far = behind_far = at_reach = past_reach = saturated = False
+    seg = (np.arange(rows) // b)[:, None]
+    for seed, d2 in tall_inputs(rows, cols, reach, seg_chunks):
+        up, up_row, down, down_row = column_nearest_rows(seed)
+        col = np.minimum(up, down)
+        shows = col.astype(np.int64) ** 2 == d2
+        # the nearest seed of the column lies in an earlier / a later segment, more than a chunk away and within the reach
+        before_far |= bool((shows & (seg > 0) & (up < down) & (up_row // b < seg) & (up > 64) & (up <= reach)).any())
+        behind_far |= bool((shows & (down < up) & (down_row // b > seg) & (down > 64) & (down <= reach)).any())
+        at_reach |= bool((shows & (col == reach)).any())
+        past_reach |= bool((shows & (col == reach + 1)).any())
+        saturated |= bool((col > reach).all(axis=0).any())
+    if reach > 64:
+        assert before_far and behind_far
+    assert at_reach and past_reach and saturated
+    # the modes share their seeds: the NaN cells of the NAN_IS_SEED maps are the seeds the other maps hold as values
+    for mode in K.MODES:
+        for a, z in zip(K.designed(rows, cols, reach, seg_chunks, mode), K.designed(rows, cols, reach, seg_chunks, K.BELOW)):
+            assert np.array_equal(D.seeds(a, mode, K.THRESHOLD), D.seeds(z, K.BELOW, K.THRESHOLD))
+            assert mode & K.NAN_IS_SEED or not np.isnan(a).any()
+        if mode & K.NAN_IS_SEED:  # (the first map: some seeds are NaN cells, some are values)
+            assert np.isnan(a0 := K.designed(rows, cols, reach, seg_chunks, mode)[0]).any() and D.seeds(a0, mode & 3, K.THRESHOLD).any()
+
+
+def test_edge_inputs_hold_what_they_are_named_for():
+    zero = dict((float(t), p) for t, p in K.EDGE_POOLS)[0.0]
+    assert not D.seeds(np.float32([[-0.0, 0.0]]), D.BELOW, 0.0).any() and not D.seeds(np.float32([[-0.0, 0.0]]), D.ABOVE, 0.0).any()
+    tiny = zero[(zero != 0) & (np.abs(zero) < np.float32(1.1754944e-38))]
+    assert len(tiny) == 2 and D.seeds(tiny[None, :], D.BELOW, 0.0).sum() == 1 and D.seeds(tiny[None, :], D.ABOVE, 0.0).sum() == 1
+    near = dict((float(t), p) for t, p in K.EDGE_POOLS)[0.1]
+    assert D.seeds(near[None, :3], D.BELOW, 0.1).tolist() == [[False, True, False]] and D.seeds(near[None, :3], D.ABOVE, 0.1).tolist() == [[False, False, True]]
+    for threshold, pool in K.EDGE_POOLS:
+        for mode in K.MODES:
+            a, few, none = K.edge_maps(threshold, pool, mode, 7)
+            assert 0 < D.seeds(few, mode, threshold).sum() < D.seeds(a, mode, threshold).sum() / 20 and not D.seeds(none, mode, threshold).any()
+    # the ties: some cell of the single-seed map has d2 exactly k * k, and exactly k
+    d2 = D.squared_cells(D.seeds(K.tie_maps(3)[0], D.BELOW, K.THRESHOLD))
+    assert all((d2 == k * k).any() for k in K.TIE_CELLS) and all((d2 == k).any() for k in K.TIE_SQUARES)
+
+
+def test_the_tall_region_case_reads_a_seed_two_chunks_before_its_g():
+    """Case A, first rectangle, whatever the rectangle itself holds (here: all seeds): some cell of `out` has its nearest seed of
+    the map in its own column, before g, in the first of the two chunks of pre-halo and inside `in`."""
+    case = K.REGION_TALL["A"]
+    (rows, cols), reach = case["shape"], case["reach"]
+    (r0, c0, h, w), claim = case["rects"][0]
+    a = K.region_base("A", K.BELOW)[0]
+    a[r0:r0 + h, c0:c0 + w] = 0.0
+    seed = D.seeds(a, K.BELOW, K.THRESHOLD)
+    d2 = D.squared_cells(seed.T).T
+    up, up_row, _down, _down_row = column_nearest_rows(seed)
+    g0, in0 = claim["g_i0"], claim["in_i0"]
+    i = np.arange(rows)[:, None]
+    assert ((i >= g0) & (up_row >= in0) & (up_row < g0 - 64) & (up <= reach) & (up.astype(np.int64) ** 2 == d2)).any()
+    assert seed[in0 - 1].any()  # and a seed lies one row outside `in`

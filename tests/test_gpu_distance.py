@@ -2,7 +2,9 @@
 layer is defined bit for bit, so every comparison is array_equal on the bit patterns and no tolerance is involved anywhere, on
 both routes of the second pass (TE_OPT_DISTANCE_ROUTE 1: tiled wherever it fits, 2: the route of any reach);
 te_distance_stats shows which one ran.  Shapes, caps and inputs: tests/distance_cases.py (tests/test_distance_plan.py checks on
-the CPU that each of them takes the route claimed here)."""
+the CPU that each of them takes the route claimed here).  The wavefront's bookkeeping in pass 1 -- halos of several chunks, a
+mask per lane, the search behind the segment -- has no check outside the GPU: the tall cases and the tall region cases below
+are that check (DESIGN.md section 4.11 lists them)."""
 import numpy as np
 import pytest
 
@@ -61,10 +63,29 @@ def reference(maps, mode, max_distance):
     return np.stack([D.from_squared(d2, max_distance, K.RES) for d2 in squared(maps, mode)])
 
 
-def context(capi, rows, cols, batch, maps=None, route=0):
+_D2_ONE = {}
+
+
+def squared_of(a, mode, threshold=K.THRESHOLD):
+    """d2 of every cell of one map: computed once per set of seeds (the modes of a designed map share theirs), the short axis
+    first (the definition is symmetric in the axes, and its loop runs over the first one), never changed."""
+    seed = D.seeds(a, mode, threshold)
+    key = (seed.shape, seed.tobytes())
+    if key not in _D2_ONE:
+        d2 = np.ascontiguousarray(D.squared_cells(seed.T).T) if seed.shape[0] > seed.shape[1] else D.squared_cells(seed)
+        d2.setflags(write=False)
+        _D2_ONE[key] = d2
+    return _D2_ONE[key]
+
+
+def definition(maps, mode, max_distance, threshold=K.THRESHOLD, res=K.RES):
+    return np.stack([D.from_squared(squared_of(a, mode, threshold), max_distance, res) for a in maps])
+
+
+def context(capi, rows, cols, batch, maps=None, route=0, res=K.RES):
     ctx = capi.Context(0)
     ctx.set_params(capi.default_params())
-    ctx.set_geometry(rows, cols, batch, K.RES)
+    ctx.set_geometry(rows, cols, batch, res)
     ctx.set_option(capi.OPT_DISTANCE_ROUTE, route)
     if maps is not None:
         ctx.upload_layer(IN, to_device(maps))
@@ -166,6 +187,147 @@ def test_region_equals_the_whole_map_call(capi, route, reach):
             first, n = differing(got, whole)
             assert n == 0, f"route {route} reach {reach} rectangle {(r0, c0, h, w)}: {n} cells differ: {first}"
         assert np.array_equal(bits(whole), bits(np.stack([D.distance(a, mode, K.THRESHOLD, md, K.RES) for a in now])))
+
+
+@pytest.mark.parametrize("mode", K.MODES)
+@pytest.mark.parametrize("rows,cols,reach,opt,claim,lds,seg_chunks,p1_segs", K.TALL_CASES)
+def test_every_cell_of_the_tall_cases(capi, rows, cols, reach, opt, claim, lds, seg_chunks, p1_segs, mode):
+    """Several segments per column, halos of several chunks, a mask in every lane, the tile at the LDS limit and the route by plan
+    on either side of its reach (tests/distance_cases.py: TALL_CASES), under the option the case names."""
+    md = K.cap_for(reach)
+    blocks = K.BATCH * -(-rows // 64) * -(-cols // 64)
+    with context(capi, rows, cols, K.BATCH, None, opt) as ctx:
+        for n, maps in enumerate(K.tall_batches(rows, cols, reach, seg_chunks, mode, 1000 * rows + cols)):
+            if n == 0:
+                assert not D.seeds(maps[-1], K.BELOW, K.THRESHOLD).any()  # one map of the batch is empty under BELOW
+            want = definition(maps, mode, md)
+            ctx.upload_layer(IN, to_device(maps))
+            ctx.run_distance(mode, K.THRESHOLD, md, IN, OUT)
+            got = from_device(ctx.download(OUT), K.BATCH, rows, cols)
+            first, bad = differing(got, want)
+            assert bad == 0, f"mode {mode} option {opt} {(rows, cols)} reach {reach} batch {n}: {bad} cells differ, (map, i, j), got, want: {first}"
+            assert not np.isnan(got).any()
+            assert ctx.distance_stats() == ((blocks, 0) if claim == "tiled" else (0, blocks)), (reach, opt)
+            ctx.run_distance(mode, K.THRESHOLD, md, IN, OUT)  # a second run: the same bits
+            assert np.array_equal(bits(from_device(ctx.download(OUT), K.BATCH, rows, cols)), bits(want))
+            # the input is as it was
+            assert np.array_equal(bits(from_device(ctx.download(IN), K.BATCH, rows, cols)), bits(np.stack(maps)))
+
+
+def region_tile(rng, h, w):
+    """New cells of a rectangle: seeds of either mode, free cells and NaN cells (few of each in a large rectangle, so that the
+    definition stays quick)."""
+    p = 0.15 if h * w < 1000 else 0.01
+    u = rng.random((h, w))
+    return np.where(u < p, np.float32(0.1), np.where(u < 2 * p, np.float32(0.9), np.where(u < 3 * p, np.float32(np.nan), np.float32(K.THRESHOLD)))).astype(np.float32)
+
+
+@pytest.mark.parametrize("mode", K.MODES)
+@pytest.mark.parametrize("option", (0, 1))
+@pytest.mark.parametrize("name", sorted(K.REGION_TALL))
+def test_region_on_a_tall_map_in_every_mode(capi, name, option, mode):
+    """The region form where g starts inside a chunk, its pre-halo is cut by `in`, and a region holds more than one segment
+    (tests/distance_cases.py: REGION_TALL), on the first and the last map of the batch."""
+    case = K.REGION_TALL[name]
+    (rows, cols), reach = case["shape"], case["reach"]
+    md = K.cap_for(reach)
+    tiled = option == 1 or reach <= 64
+    rng = np.random.default_rng(reach + mode)
+    now = [a.copy() for a in K.region_base(name, mode)]
+    with context(capi, rows, cols, K.BATCH, now, option) as ctx, context(capi, rows, cols, K.BATCH, None, option) as fresh:
+        ctx.run_distance(mode, K.THRESHOLD, md, IN, OUT)
+        for m in (0, K.BATCH - 1):
+            for (r0, c0, h, w), _claim in case["rects"]:
+                tile = region_tile(rng, h, w)
+                now[m][r0:r0 + h, c0:c0 + w] = tile
+                ctx.upload_layer_tile(IN, np.ascontiguousarray(tile.T), m, r0, c0)
+                i0, j0, i1, j1 = max(0, r0 - reach), max(0, c0 - reach), min(rows, r0 + h + reach), min(cols, c0 + w + reach)
+                before = from_device(ctx.download(OUT), K.BATCH, rows, cols).copy()
+                poisoned = before.copy()
+                outside = np.ones((rows, cols), bool)
+                outside[i0:i1, j0:j1] = False
+                poisoned[m][outside] = MARK  # (the call must not write a cell outside out_rect, not even its old value)
+                ctx.upload_layer(OUT, to_device(list(poisoned)))
+                rect = ctx.run_distance_region(mode, K.THRESHOLD, md, IN, OUT, m, r0, c0, h, w)
+                assert rect == (i0, j0, i1 - i0, j1 - j0), (rect, (r0, c0, h, w))
+                got = from_device(ctx.download(OUT), K.BATCH, rows, cols).copy()
+                assert (got[m][outside] == MARK).all(), (m, r0, c0, h, w)
+                blocks = -(-(i1 - i0) // 64) * -(-(j1 - j0) // 64)
+                assert ctx.distance_stats() == ((blocks, 0) if tiled else (0, blocks))
+                got[m][outside] = before[m][outside]
+                ctx.upload_layer(OUT, to_device(list(got)))
+                # the whole layer equals a fresh whole-map call, and that equals the definition
+                fresh.upload_layer(IN, to_device(now))
+                fresh.run_distance(mode, K.THRESHOLD, md, IN, OUT)
+                whole = from_device(fresh.download(OUT), K.BATCH, rows, cols)
+                first, bad = differing(got, whole)
+                assert bad == 0, f"{name} option {option} mode {mode} map {m} rectangle {(r0, c0, h, w)}: {bad} cells differ: {first}"
+            first, bad = differing(whole, definition(now, mode, md))
+            assert bad == 0, f"{name} option {option} mode {mode} after map {m}: {bad} cells differ from the definition: {first}"
+        assert np.array_equal(bits(from_device(ctx.download(IN), K.BATCH, rows, cols)), bits(np.stack(now)))
+
+
+@pytest.mark.parametrize("option", (0, 1))
+def test_a_region_call_first_sizes_the_scratch(capi, option):
+    """On a fresh context the first distance call is a region call: the scratch of pass 1 is sized by the region.  A whole-map call
+    grows it; the same region call then reads its g at another column height than the one left behind."""
+    case = K.REGION_TALL["A"]
+    (rows, cols), reach, mode, m = case["shape"], case["reach"], K.BELOW | K.NAN_IS_SEED, 0
+    (r0, c0, h, w), claim = case["rects"][0]
+    i0, j0, oh, ow = claim["out"]
+    md = K.cap_for(reach)
+    now = [a.copy() for a in K.region_base("A", mode)]
+    now[m][r0:r0 + h, c0:c0 + w] = region_tile(np.random.default_rng(5), h, w)
+    want = definition(now, mode, md)
+    outside = np.ones((K.BATCH, rows, cols), bool)
+    outside[m, i0:i0 + oh, j0:j0 + ow] = False
+    with context(capi, rows, cols, K.BATCH, now, option) as ctx:
+        for step in ("region first", "whole map", "region again"):
+            if step == "whole map":
+                ctx.run_distance(mode, K.THRESHOLD, md, IN, OUT)
+                got = from_device(ctx.download(OUT), K.BATCH, rows, cols)
+                first, bad = differing(got, want)
+            else:
+                ctx.upload_layer(OUT, np.full(K.BATCH * rows * cols, MARK, np.float32))
+                assert ctx.run_distance_region(mode, K.THRESHOLD, md, IN, OUT, m, r0, c0, h, w) == claim["out"]
+                got = from_device(ctx.download(OUT), K.BATCH, rows, cols)
+                assert (got[outside] == MARK).all(), step
+                first, bad = differing(np.where(outside, want, got), want)
+            assert bad == 0, f"{step}, option {option}: {bad} cells differ from the definition: {first}"
+
+
+@pytest.mark.parametrize("route", (1, 2))
+def test_values_at_the_edges_of_the_comparison_and_of_the_cap(capi, route):
+    """Other resolutions; thresholds 0.0, -0.25 and 0.1 (a double) on cells around them -- both zeros, subnormals, the smallest
+    normals, infinities, NaN, the float neighbours of the threshold; and caps that are ties in cells (max_distance = k * res and
+    res * sqrt(k)): the definition's cap_cells says on which side each falls.  tests/test_distance_ref.py holds the inputs to that."""
+    rows, cols = K.EDGE_SHAPE
+    seed = 1000 * rows + cols
+    tie_maps = K.tie_maps(seed)
+
+    def check(ctx, maps, mode, threshold, md, res, what):
+        want = definition(maps, mode, md, threshold, res)
+        ctx.upload_layer(IN, to_device(maps))
+        ctx.run_distance(mode, threshold, md, IN, OUT)
+        got = from_device(ctx.download(OUT), K.BATCH, rows, cols)
+        first, bad = differing(got, want)
+        assert bad == 0, f"route {route} {what}: {bad} cells differ, (map, i, j), got, want: {first}"
+        assert not np.isnan(got).any()
+
+    for res in K.EDGE_RESOLUTIONS + [K.RES]:
+        with context(capi, rows, cols, K.BATCH, None, route, res) as ctx:
+            if res != K.RES:
+                md = K.cap_for(K.EDGE_REACH, res)
+                assert D.cap_cells(md, res)[1] == K.EDGE_REACH
+                for mode in K.MODES:
+                    check(ctx, maps_of(rows, cols), mode, K.THRESHOLD, md, res, f"res {res} mode {mode}")
+            else:
+                for threshold, pool in K.EDGE_POOLS:
+                    for mode in K.MODES:
+                        check(ctx, K.edge_maps(threshold, pool, mode, seed), mode, threshold, K.cap_for(K.EDGE_REACH), res, f"threshold {threshold} mode {mode}")
+            ties = [(f"{k} * res", k * res) for k in K.TIE_CELLS] + [(f"res * sqrt({k})", res * float(np.sqrt(np.float64(k)))) for k in K.TIE_SQUARES]
+            for name, md in ties:
+                check(ctx, tie_maps, K.BELOW, K.THRESHOLD, md, res, f"res {res} cap {name} = {md!r}: cap2 {D.cap_cells(md, res)[0]}")
 
 
 def test_refusals(capi):
