@@ -66,6 +66,9 @@
  *   te_run_distance / te_run_distance_region / te_distance_stats
  *                        <- no filter of grid_map: the clearance layer a planner asks a traversability map for, the exact
  *                           distance of every cell to the nearest untraversable one (defined below, not restated)
+ *   te_run_components / te_run_reachable / te_components_stats
+ *                        <- no filter of grid_map: the connected regions of the free cells -- the size of every cell's region,
+ *                           and what is connected to the robot (defined below, not restated)
  *
  * Data contract (identical to grid_map::Matrix = Eigen::MatrixXf): float32, COLUMN-major,
  * element (row i, col j) of map m at ptr[m*rows*cols + j*rows + i]; invalid cell = non-finite.
@@ -1146,6 +1149,43 @@ int te_distance_stats(te_ctx* ctx, uint64_t counts[2]);
 #define TE_DISTANCE_TIME_PASS1 0x100
 #define TE_DISTANCE_TIME_PASS2 0x200
 int te_time_distance_samples(te_ctx* ctx, int mode, double threshold, double max_distance, int in_layer, int out_layer, int warmup, int iters, float* ms);
+
+/* ---- Connected regions: the components of the free cells of a map, their sizes, and what a set of start cells reaches ----
+ * Like the clearance layer this is DEFINED here, not restated: a brute-force flood fill (tests/ref_py/components_ref.py) is the
+ * definition, the result is unique, and the device is held to it bit for bit.
+ *   1. blocked / free  a cell v of in_layer is blocked iff it is a seed of te_run_distance under the same mode and threshold
+ *      (TE_DISTANCE_BELOW / TE_DISTANCE_ABOVE, TE_DISTANCE_NAN_IS_SEED or-ed in, compared on the float; v == threshold is blocked
+ *      in neither mode).  Every other cell is free; without the NaN bit a NaN cell is free;
+ *   2. neighbours      connectivity 4: (i +- 1, j) and (i, j +- 1); 8: those and the four diagonals, and a diagonal step
+ *      connects two free cells whatever the two cells beside it are.  No wrap at the map border, no link between the maps of
+ *      a batch.  Any other value: TE_ERR_INVALID_ARG;
+ *   3. components      the classes of the free cells of one map under the transitive closure of 2;
+ *   4. sizes           te_run_components: a free cell gets (float)n, n the number of cells of its component as a 32-bit unsigned
+ *      integer converted to float, round to nearest (exact up to 2^24); a blocked cell gets 0.0f;
+ *   5. reachable       te_run_reachable: a free cell whose component holds at least one start cell gets 1.0f, every other cell
+ *      -- blocked ones included -- 0.0f, so traversability .* reachable is a planner's map.  A start on a blocked cell reaches
+ *      nothing.
+ * Limits: no region form (one changed cell can merge or split components anywhere), no chain-file type, no C++ plugin; the
+ * labels themselves are not exposed; v == threshold is free, so for "clearance <= r is blocked" pass the next float above r
+ * with TE_DISTANCE_BELOW. */
+#define TE_COMPONENTS_CONNECTIVITY_4 4
+#define TE_COMPONENTS_CONNECTIVITY_8 8
+#define TE_REACHABLE_MAX_STARTS 256
+/* out_layer = the size layer (4) of in_layer for maps [map0, map0 + nmaps) of the batch; the other maps are untouched.  Any two
+ * float layers of the context, user layers included; in_layer == out_layer needs no copy.  Identical run after run.
+ * Asynchronous on the context's stream unless out_layer is the elevation.
+ *   TE_ERR_INVALID_ARG (also: a mode that is neither comparison, a connectivity that is neither 4 nor 8), TE_ERR_NOT_READY, the
+ *   context afterwards and the joining of a prefetch: as te_run_distance.  TE_ERR_BAD_PARAM: a threshold that is not finite.
+ *   TE_ERR_UNSUPPORTED: a map of 2^31 cells or more, or the scratch (8 bytes per cell of the call) does not fit in device memory. */
+int te_run_components(te_ctx* ctx, int mode, double threshold, int connectivity, int in_layer, int out_layer, int map0, int nmaps);
+/* out_layer = the reachable layer (5) of map `map` of in_layer from the n_starts cells start_cells[2 k] = row, [2 k + 1] = column;
+ * layers, errors and the stream as te_run_components.  n_starts must be in [1, TE_REACHABLE_MAX_STARTS] and start_cells not NULL;
+ * a start outside the map: TE_ERR_INVALID_ARG, and nothing is written.  The starts are copied before the call returns. */
+int te_run_reachable(te_ctx* ctx, int mode, double threshold, int connectivity, int in_layer, int out_layer, int map, int n_starts, const int* start_cells /* row, col pairs */);
+/* The last te_run_components or te_run_reachable, over all its maps: counts[0] = components, counts[1] = free cells, counts[2] =
+ * cells of the largest component, counts[3] = cells written 1.0f (0 after te_run_components).  Unlike te_distance_stats the
+ * values come from the device: the call waits for the context's stream and reads 32 bytes.  TE_ERR_NOT_READY before any call. */
+int te_components_stats(te_ctx* ctx, uint64_t counts[4]);
 
 /* ---- gridMapFilters/SlidingWindowMathExpressionFilter on the device: an expression over a window around every cell ----
  * Like the median fill and the radius filters this contract is RESTATED from memory of grid_map_filters and EigenLab; nothing

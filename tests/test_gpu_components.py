@@ -1,0 +1,191 @@
+"""te_run_components / te_run_reachable on the device, through capi, against their definition as a flood fill
+(tests/ref_py/components_ref.py).  The result is unique, so every comparison is array_equal on the bit patterns and no tolerance
+is involved anywhere.  Shapes and inputs: tests/components_cases.py (tests/test_components_plan.py checks on the CPU that the
+shapes marked multi-tile have the tiles claimed and that the designed inputs cross a seam both ways).  Largest map: 512 x 384."""
+import numpy as np
+import pytest
+
+from tests import components_cases as K
+from tests.ref_py import components_ref as R
+
+pytestmark = pytest.mark.gpu
+
+IN, OUT = "traversability", "traversability_roughness"
+MARK = np.float32(-77.25)
+
+
+@pytest.fixture(scope="module")
+def capi():
+    from traversability_estimation_amd import build, capi
+    build.build_lib()
+    return capi
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def to_device(maps):
+    return np.ascontiguousarray(np.stack([m.T for m in maps]), np.float32).reshape(-1)
+
+
+def from_device(flat, batch, rows, cols):
+    return flat.reshape(batch, cols, rows).transpose(0, 2, 1)
+
+
+_LABELS = {}
+
+
+def labels_of(free, connectivity):
+    """The reference's labels of a free mask: computed once, shared by the modes and the calls, never changed."""
+    key = (free.shape, free.tobytes(), connectivity)
+    if key not in _LABELS:
+        lab = R.labels(free, connectivity)
+        lab.setflags(write=False)
+        _LABELS[key] = lab
+    return _LABELS[key]
+
+
+def context(capi, rows, cols, batch=1):
+    ctx = capi.Context(0)
+    ctx.set_params(capi.default_params())
+    ctx.set_geometry(rows, cols, batch, K.RES)
+    return ctx
+
+
+def same(got, want, what):
+    bad = np.argwhere(bits(got) != bits(want))
+    assert len(bad) == 0, f"{what}: {len(bad)} cells differ, first {[(tuple(b), float(got[tuple(b)]), float(want[tuple(b)])) for b in bad[:5]]}"
+
+
+@pytest.mark.parametrize("rows,cols", K.SHAPES)
+def test_every_case_both_connectivities_both_modes_both_calls(capi, rows, cols):
+    with context(capi, rows, cols) as ctx:
+        for name, extra, free, layer in K.cases(rows, cols):
+            for mode in K.MODES:
+                v = layer(mode)
+                assert np.array_equal(R.free(v, mode | extra, K.THRESHOLD), free), name
+                ctx.upload_layer(IN, to_device([v]))
+                for conn in K.CONNECTIVITIES:
+                    what = f"{rows} x {cols} {name} mode {mode | extra} connectivity {conn}"
+                    lab = labels_of(free, conn)
+                    ctx.run_components(mode | extra, K.THRESHOLD, conn, IN, OUT)
+                    same(from_device(ctx.download(OUT), 1, rows, cols)[0], R.sizes_of(lab), what)
+                    assert ctx.components_stats() == R.stats_of(lab), what
+                    for sname, starts in K.start_sets(lab, free).items():
+                        ctx.run_reachable(mode | extra, K.THRESHOLD, starts, conn, IN, OUT)
+                        same(from_device(ctx.download(OUT), 1, rows, cols)[0], R.reachable_of(lab, starts), f"{what} starts {sname}")
+                        assert ctx.components_stats() == R.stats_of(lab, starts), f"{what} starts {sname}"
+
+
+def test_in_place_equals_out_of_place_and_a_user_layer_takes_the_output(capi):
+    rows, cols = 130, 67
+    name, extra, free, layer = [c for c in K.cases(rows, cols) if c[0] == "random593"][0]
+    v = layer(K.BELOW)
+    with context(capi, rows, cols) as ctx:
+        ctx.upload_layer(IN, to_device([v]))
+        user = ctx.add_layer("regions")
+        ctx.run_components(K.BELOW, K.THRESHOLD, 8, IN, OUT)
+        ctx.run_components(K.BELOW, K.THRESHOLD, 8, IN, user)
+        want = ctx.download(OUT).copy()
+        assert np.array_equal(bits(ctx.download(user)), bits(want))
+        ctx.run_components(K.BELOW, K.THRESHOLD, 8, IN, IN)
+        assert np.array_equal(bits(ctx.download(IN)), bits(want))
+        same(from_device(want, 1, rows, cols)[0], R.sizes_of(labels_of(free, 8)), "out of place")
+        ctx.upload_layer(IN, to_device([v]))
+        start = [tuple(int(x) for x in np.argwhere(free)[0])]
+        ctx.run_reachable(K.BELOW, K.THRESHOLD, start, 4, IN, user)
+        want = ctx.download(user).copy()
+        ctx.run_reachable(K.BELOW, K.THRESHOLD, start, 4, IN, IN)
+        assert np.array_equal(bits(ctx.download(IN)), bits(want))
+        same(from_device(want, 1, rows, cols)[0], R.reachable_of(labels_of(free, 4), start), "reachable into a user layer")
+
+
+def test_one_map_of_a_batch_and_the_others_keep_their_marker(capi):
+    rows, cols = 70, 70
+    maps = [c[3](K.BELOW) for c in K.cases(rows, cols) if c[0] in ("random50", "random593", "spiral")]
+    frees = [c[2] for c in K.cases(rows, cols) if c[0] in ("random50", "random593", "spiral")]
+    with context(capi, rows, cols, 3) as ctx:
+        ctx.upload_layer(IN, to_device(maps))
+        ctx.upload_layer(OUT, np.full(3 * rows * cols, MARK, np.float32))
+        ctx.run_components(K.BELOW, K.THRESHOLD, 4, IN, OUT, map0=1, nmaps=1)
+        got = from_device(ctx.download(OUT), 3, rows, cols)
+        assert (got[0] == MARK).all() and (got[2] == MARK).all()
+        same(got[1], R.sizes_of(labels_of(frees[1], 4)), "map 1 of 3")
+        assert ctx.components_stats() == R.stats_of(labels_of(frees[1], 4))
+        ctx.run_reachable(K.BELOW, K.THRESHOLD, [(0, 0)], 4, IN, OUT, map_index=2)
+        got = from_device(ctx.download(OUT), 3, rows, cols)
+        assert (got[0] == MARK).all()
+        same(got[2], R.reachable_of(labels_of(frees[2], 4), [(0, 0)]), "map 2 of 3")
+        # the whole batch in one call: no link between the maps, the totals over all of them
+        ctx.run_components(K.BELOW, K.THRESHOLD, 8, IN, OUT)
+        got = from_device(ctx.download(OUT), 3, rows, cols)
+        each = [R.stats_of(labels_of(f, 8)) for f in frees]
+        for k in range(3):
+            same(got[k], R.sizes_of(labels_of(frees[k], 8)), f"map {k} of the batch")
+        assert ctx.components_stats() == (sum(e[0] for e in each), sum(e[1] for e in each), max(e[2] for e in each), 0)
+
+
+def test_a_call_as_the_first_call_of_a_context_and_twice_with_identical_bits(capi):
+    rows, cols = 512, 384
+    name, extra, free, layer = [c for c in K.cases(rows, cols) if c[0] == "random593"][0]
+    v = layer(K.ABOVE)
+    with context(capi, rows, cols) as ctx:
+        with pytest.raises(capi.TeError) as err:
+            ctx.components_stats()
+        assert err.value.code == capi.TE_ERR_NOT_READY
+        ctx.upload_layer(IN, to_device([v]))
+        ctx.run_components(K.ABOVE, K.THRESHOLD, 4, IN, OUT)
+        first = ctx.download(OUT).copy()
+        for _ in range(3):
+            ctx.run_components(K.ABOVE, K.THRESHOLD, 4, IN, OUT)
+            assert np.array_equal(bits(ctx.download(OUT)), bits(first))
+        same(from_device(first, 1, rows, cols)[0], R.sizes_of(labels_of(free, 4)), "first call")
+    with context(capi, rows, cols) as ctx:
+        ctx.upload_layer(IN, to_device([v]))
+        ctx.run_reachable(K.ABOVE, K.THRESHOLD, [(0, 0), (rows - 1, cols - 1)], 8, IN, OUT)
+        first = ctx.download(OUT).copy()
+        ctx.run_reachable(K.ABOVE, K.THRESHOLD, [(0, 0), (rows - 1, cols - 1)], 8, IN, OUT)
+        assert np.array_equal(bits(ctx.download(OUT)), bits(first))
+        same(from_device(first, 1, rows, cols)[0], R.reachable_of(labels_of(free, 8), [(0, 0), (rows - 1, cols - 1)]), "first call")
+
+
+def test_where_a_robot_of_radius_r_can_go(capi):
+    """The example of INTEGRATION.md: te_run_distance, then te_run_reachable on the clearance layer.  A wall with one gap of 3 cells:
+    a robot of radius 1 cell passes, a robot of radius 2 cells does not."""
+    rows, cols = 130, 67
+    trav = np.ones((rows, cols), np.float32)
+    trav[:, 30] = 0.0
+    trav[60:63, 30] = 1.0
+    robot = (10, 5)
+    with context(capi, rows, cols) as ctx:
+        clearance = ctx.add_layer("clearance")
+        for radius_cells, passes in ((1, True), (2, False)):
+            ctx.upload_layer(IN, to_device([trav]))
+            ctx.run_distance("below", 0.5, 1.0, IN, clearance)
+            r = np.float32(radius_cells * K.RES)
+            ctx.run_reachable("below", float(np.nextafter(r, np.float32(np.inf))), [robot], 4, clearance, OUT)
+            got = from_device(ctx.download(OUT), 1, rows, cols)[0]
+            assert got[robot] == 1.0 and got[61, 5] == 1.0
+            assert (got[61, 60] == 1.0) == passes and (got[61, 30] == 1.0) == passes
+            assert got[0, 30] == 0.0 and set(np.unique(got)) <= {0.0, 1.0}
+
+
+def test_bad_arguments_leave_the_output_untouched(capi):
+    rows, cols = 9, 9
+    with context(capi, rows, cols) as ctx:
+        ctx.upload_layer(IN, np.ones(rows * cols, np.float32))
+        ctx.upload_layer(OUT, np.full(rows * cols, MARK, np.float32))
+        for starts in ([(rows, 0)], [(0, cols)], [(-1, 0)], [(0, 0), (0, -1)]):
+            with pytest.raises(capi.TeError) as err:
+                ctx.run_reachable(K.BELOW, K.THRESHOLD, starts, 4, IN, OUT)
+            assert err.value.code == capi.TE_ERR_INVALID_ARG
+        for bad in (lambda: ctx.run_components(K.BELOW, K.THRESHOLD, 5, IN, OUT), lambda: ctx.run_components(3, K.THRESHOLD, 4, IN, OUT),
+                    lambda: ctx.run_reachable(K.BELOW, K.THRESHOLD, [], 4, IN, OUT),
+                    lambda: ctx.run_reachable(K.BELOW, K.THRESHOLD, [(0, 0)] * 257, 4, IN, OUT)):
+            with pytest.raises(capi.TeError) as err:
+                bad()
+            assert err.value.code == capi.TE_ERR_INVALID_ARG
+        assert (ctx.download(OUT) == MARK).all()
+        ctx.run_reachable(K.BELOW, K.THRESHOLD, [(0, 0)] * 256, 4, IN, OUT)
+        assert (ctx.download(OUT) == 1.0).all()

@@ -43,6 +43,9 @@ OPT_DISTANCE_ROUTE = 14  # te_run_distance: 0 by plan, 1 the tiled route whereve
 DISTANCE_BELOW, DISTANCE_ABOVE, DISTANCE_NAN_IS_SEED = 1, 2, 4
 DISTANCE_TIME_PASS1, DISTANCE_TIME_PASS2 = 0x100, 0x200
 DISTANCE_MODES = {"below": DISTANCE_BELOW, "above": DISTANCE_ABOVE}
+# te_run_components / te_run_reachable: the neighbours of a cell, and the most start cells of one call
+COMPONENTS_CONNECTIVITY_4, COMPONENTS_CONNECTIVITY_8 = 4, 8
+REACHABLE_MAX_STARTS = 256
 OPT_FILTER_ANY_RADIUS = 8  # filter discs: 0 up to 32 cells (TE_ERR_UNSUPPORTED above), 1 any radius, 2 the route of any radius for every disc
 
 # every symbol include/travgpu.h declares (tests/test_cabi.py checks the library exports them all)
@@ -67,6 +70,7 @@ SYMBOLS = ["te_params_default", "te_params_validate", "te_device_count", "te_cre
            "te_time_median_fill_samples",
            "te_run_radius_filter", "te_run_radius_filter_region", "te_radius_filter_stats", "te_time_radius_filter_samples",
            "te_run_distance", "te_run_distance_region", "te_distance_stats", "te_time_distance_samples",
+           "te_run_components", "te_run_reachable", "te_components_stats",
            "te_window_expr_params_default", "te_window_expr_params_validate", "te_window_expr_check", "te_run_window_expression", "te_run_window_expression_region",
            "te_window_expression_stats", "te_time_window_expression_samples",
            "te_add_layer", "te_remove_layer", "te_layer_id", "te_layer_name",
@@ -343,6 +347,9 @@ def load():
         L.te_run_distance_region.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.te_distance_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.te_time_distance_samples.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.te_run_components.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.te_run_reachable.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.te_components_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         wp = C.POINTER(TeWindowExprParams)
         L.te_window_expr_params_default.argtypes = [wp]
         L.te_window_expr_params_validate.argtypes = [wp]
@@ -1130,6 +1137,33 @@ class Context:
         """Device time of each of `iters` distance layers (mode 0: device copies of the layer; DISTANCE_TIME_PASS1 / _PASS2 or-ed in:
         that pass alone), in ms."""
         return self._time_samples(load().te_time_distance_samples, (int(mode), float(threshold), float(max_distance)), in_layer, out_layer, warmup, iters)
+
+    def run_components(self, mode, threshold, connectivity=4, in_layer="traversability", out_layer=None, map0=0, nmaps=None, nan_is_seed=False):
+        """Connected regions (te_run_components): `out_layer` (default: `in_layer`, in place) = for every free cell of `in_layer` the
+        number of cells of its component under `connectivity` (4 or 8), 0 for a blocked cell.  Blocked: a seed of run_distance under
+        the same mode ("below" / "above"), threshold and nan_is_seed."""
+        lid = lambda name: self._lid(name)
+        nmaps = self.batch - map0 if nmaps is None else nmaps
+        _check(load().te_run_components(self._h, _distance_mode(mode, nan_is_seed), float(threshold), int(connectivity), lid(in_layer),
+                                        lid(in_layer if out_layer is None else out_layer), int(map0), int(nmaps)))
+
+    def run_reachable(self, mode, threshold, starts, connectivity=4, in_layer="traversability", out_layer=None, map_index=0, nan_is_seed=False):
+        """te_run_reachable: `out_layer` (default: `in_layer`, in place) = 1 on every free cell of map `map_index` connected to one of
+        `starts` = [(row, col), ...], 0 on every other cell."""
+        lid = lambda name: self._lid(name)
+        flat = [int(v) for rc in starts for v in rc]
+        if len(flat) != 2 * len(starts):
+            raise ValueError("starts must be (row, col) pairs")
+        cells = (C.c_int * max(1, len(flat)))(*flat)
+        _check(load().te_run_reachable(self._h, _distance_mode(mode, nan_is_seed), float(threshold), int(connectivity), lid(in_layer),
+                                       lid(in_layer if out_layer is None else out_layer), int(map_index), len(starts), cells))
+
+    def components_stats(self):
+        """(components, free cells, cells of the largest component, cells written 1.0) of the last run_components / run_reachable,
+        over all its maps; read from the device (waits for the stream)."""
+        counts = (C.c_uint64 * 4)()
+        _check(load().te_components_stats(self._h, counts))
+        return tuple(int(v) for v in counts)
 
     def run_window_expression(self, text, params, in_layer="elevation", out_layer=None, map0=0, nmaps=None):
         """gridMapFilters/SlidingWindowMathExpressionFilter on the device (te_run_window_expression): `out_layer` (default:

@@ -103,6 +103,8 @@ struct te_ctx {
     te::DevBuf window_copy;
     // te_run_distance (te_distance.hip): the column distances of pass 1, 16 bits per cell of the rectangle pass 2 reads; grown
     te::DevBuf distance_g;
+    // te_run_components / te_run_reachable (te_components.hip): a label and a count of 32 bits each per cell of the call; grown
+    te::DevBuf components_scratch;
     // te_move_map (te_move.hip): one float layer of one map, the out-of-place target of a shift (te_slab.h: move_scratch_bytes);
     // allocated by the first move that needs it
     te::DevBuf move_scratch;
@@ -130,6 +132,7 @@ struct te_ctx {
     // te_run_radius_filter: the window table of the last call (device copy of radius_tab_host; grown) and its two block counts
     te::DevBuf radius_tab, radius_counts;
     te::DevBuf window_counts;  // te_run_window_expression: its two block counts
+    te::DevBuf components_counts;  // te_run_components / te_run_reachable: the four totals of te_components_stats
   } cmem;
   float* poly_rot = nullptr;  // (derived: lmem.poly)
   bool check_inclination = false;  // footprint/check_robot_inclination (:114)
@@ -168,6 +171,8 @@ struct te_ctx {
   int opt_distance_route = 0;
   unsigned long long distance_counts[2] = {0, 0};
   bool distance_counts_valid = false;
+  // whether a te_run_components or te_run_reachable has left its totals in cmem.components_counts
+  bool components_counts_valid = false;
   // face flags (te_face_flags.h): the bytes live in the slab; what they describe: te::CtxState::face_crit
   uint8_t* face_flags = nullptr;
   int opt_face_flags = 1;  // TE_OPT_FACE_FLAGS
