@@ -117,6 +117,88 @@ def cases(rows, cols):
     return out
 
 
+# ---- what only the device runs: the write pass beyond one turn, the starts kernel beyond its first lanes, unions that meet ----
+# The write pass has at most 4096 workgroups of 256 threads: a map of more than WRITE_TURN cells makes some threads take a
+# second turn.  BIG has 7,424 cells more (storage indices WRITE_TURN ...), BIG_THIN is 257 x 2 tiles for the batch form.
+WRITE_TURN = 4096 * 256
+BIG = (1100, 960)
+BIG_THIN = (16400, 65)
+ISLANDS_SHAPE = (130, 67)
+PERFORATED_SHAPES = [(200, 200), (512, 384)]
+SPLIT_ROW = 100
+FLOAT_INEXACT = (4097, 4097)  # 2^24 + 8193 cells, odd: the smallest square whose cell count float32 cannot hold
+MAX_STARTS = 256
+B_FREE_POSITIONS = (63, 64, 127, 128, 191, 192, 255)  # list b of island_starts
+
+
+def big_random(rows, cols, seed):
+    """The free mask `random593` of a shape too large to build every mask of masks() for."""
+    return np.random.default_rng(seed).random((rows, cols)) < RANDOM_FREE["random593"]
+
+
+def islands(rows, cols):
+    """Free 2 x 2 blocks at a pitch of 3 cells: block (a, b) is rows 3a .. 3a + 1, columns 3b .. 3b + 1 (whole blocks only).
+    Every block is a component of 4 cells under both connectivities."""
+    i, j = np.indices((rows, cols))
+    return (i % 3 < 2) & (j % 3 < 2) & (i // 3 < island_grid(rows, cols)[0]) & (j // 3 < island_grid(rows, cols)[1])
+
+
+def island_grid(rows, cols):
+    """(blocks along the rows, along the columns) of islands(rows, cols)"""
+    return (rows + 1) // 3, (cols + 1) // 3
+
+
+def island_starts(rows, cols, seed):
+    """Lists of MAX_STARTS starts on islands(rows, cols), from a seeded shuffle.  name -> (starts, islands hit):
+    a  every start in an island of its own;
+    b  positions 63, 64, 127, 128, 191, 192 and 255 (the last lane of a wavefront, the first of the next, the last start) on free
+       cells of different islands, every other position on a blocked cell;
+    c  the last start on a free cell, every other one on a blocked cell;
+    d  128 islands, each hit twice (by different cells)."""
+    rng = np.random.default_rng(seed)
+    na, nb = island_grid(rows, cols)
+    assert na * nb >= MAX_STARTS
+    order = rng.permutation(na * nb)
+
+    def cell(block, corner):
+        return (3 * int(block // nb) + corner // 2, 3 * int(block % nb) + corner % 2)
+
+    blocked = np.argwhere(~islands(rows, cols))
+    walls = [tuple(int(v) for v in blocked[k]) for k in rng.permutation(len(blocked))[:MAX_STARTS]]
+    a = [cell(order[k], int(rng.integers(4))) for k in range(MAX_STARTS)]
+    b = list(walls)
+    for n, k in enumerate(B_FREE_POSITIONS):
+        b[k] = cell(order[300 + n], int(rng.integers(4)))
+    c = list(walls)
+    c[MAX_STARTS - 1] = cell(order[400], int(rng.integers(4)))
+    corners = rng.permutation(4)
+    d = [cell(order[500 + k % 128], int(corners[k // 128])) for k in rng.permutation(MAX_STARTS)]
+    return {"a": (a, MAX_STARTS), "b": (b, len(B_FREE_POSITIONS)), "c": (c, 1), "d": (d, 128)}
+
+
+
+def perforated(rows, cols, split=False):
+    """All free, except every second cell of every seam column (i odd, j = 64, 128, ...) and of every seam row (i = 64, 128, ...,
+    j odd).  A free seam cell then has a blocked cell before it along its seam, so the seam pass can save no union: every free
+    seam cell of a tile edge unites the same two tile-local components, about 32 threads on the same two roots at once.  One
+    component under both connectivities; split: row SPLIT_ROW is blocked as well, two components of different sizes."""
+    i, j = np.indices((rows, cols))
+    f = ~(((i % 2 == 1) & (j % 64 == 0) & (j >= 64)) | ((i % 64 == 0) & (i >= 64) & (j % 2 == 1)))
+    if split:
+        f[SPLIT_ROW, :] = False
+    return f
+
+
+def rake(rows, cols):
+    """A hub on every column seam: the seam column (j = 64, 128, ...) is free over all rows, and every even row is free over the 32
+    columns before it.  The teeth of a tile meet nowhere but in the seam column, so the seam pass unites 32 tile-local components
+    with smaller roots to the one root of the seam column's piece: 32 threads lower the same entry to different values, and a
+    union dropped on the way (the retry of `unite`) leaves a tooth outside.  Components: one per seam column, of
+    rows + 32 * ceil(rows / 2) cells, and the teeth behind the last seam column alone."""
+    i, j = np.indices((rows, cols))
+    return ((j % 64 == 0) & (j >= 64)) | ((i % 2 == 0) & (j % 64 >= 32))
+
+
 def start_sets(lab, free):
     """The start lists of a case: one in the largest component; one on a blocked cell; two in different components; one start
     repeated; the map's four corners.  Lists that the map cannot supply are left out."""

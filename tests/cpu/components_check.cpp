@@ -1,6 +1,7 @@
 // components_check.cpp -- the routines of csrc/te_components.h and the plan of csrc/te_components_plan.h on the host.
 //   (no argument)            every check below; prints "<n> checks, <k> failed checks"
-//   tiles <rows> <cols>      prints "<tiles_i> <tiles_j> <ti> <tj> <seam_cells> <scratch_bytes> <fits>" of the device's plan
+//   tiles <rows> <cols>      prints "<tiles_i> <tiles_j> <ti> <tj> <seam_cells> <scratch_bytes> <fits> <flat_blocks> <write_blocks>" of
+//                            the device's plan
 // The labelling runs the headers' own per-lane and per-cell routines under the Plain policy, tile by tile and seam cell by seam
 // cell in the order the plan gives, exactly as the kernels of te_components.hip call them.
 #include <stdint.h>
@@ -190,7 +191,7 @@ static void check_plan(int rows, int cols, int ti, int tj) {
 int main(int argc, char** argv) {
   if (argc == 4 && !strcmp(argv[1], "tiles")) {
     const Plan p = plan(atoi(argv[2]), atoi(argv[3]), 1);
-    printf("%u %u %d %d %llu %zu %d\n", p.tiles_i, p.tiles_j, p.ti, p.tj, p.seam_cells, p.scratch_bytes, p.fits ? 1 : 0);
+    printf("%u %u %d %d %llu %zu %d %llu %u\n", p.tiles_i, p.tiles_j, p.ti, p.tj, p.seam_cells, p.scratch_bytes, p.fits ? 1 : 0, p.flat_blocks, p.write_blocks);
     return 0;
   }
   // runs of a mask: every mask of a 12-bit chunk at three places of the word, and random words

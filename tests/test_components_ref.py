@@ -1,6 +1,7 @@
 """The definition of the connected regions (tests/ref_py/components_ref.py) held to itself: the counts of the designed inputs of
 tests/components_cases.py, scipy.ndimage.label up to renaming, the two connectivities differing exactly where designed, the
-axes swapped, and the free cells of the contract (the threshold itself, NaN with and without the bit)."""
+axes swapped, and the free cells of the contract (the threshold itself, NaN with and without the bit); and the inputs designed for the paths only the
+device runs (islands and their start lists, perforated) are what tests/test_gpu_components.py takes them for."""
 import numpy as np
 import pytest
 
@@ -98,3 +99,88 @@ def test_sizes_reachable_and_stats():
     assert R.reachable(v, R.BELOW, 0.5, 4, [(1, 1)]).sum() == 0  # a start on a blocked cell reaches nothing
     assert R.stats(v, R.BELOW, 0.5, 4) == (4, 6, 2, 0) and R.stats(v, R.BELOW, 0.5, 8, [(0, 0), (0, 1), (2, 0)]) == (3, 6, 3, 3)
     assert R.sizes_of(R.labels(free, 4)).dtype == np.float32
+
+
+def test_islands_are_946_components_of_4_cells():
+    rows, cols = K.ISLANDS_SHAPE
+    f = K.islands(rows, cols)
+    assert K.island_grid(rows, cols) == (43, 22)
+    for conn in (4, 8):
+        lab = R.labels(f, conn)
+        assert R.stats_of(lab) == (946, 4 * 946, 4, 0)
+        assert set(np.unique(R.sizes_of(lab))) == {0.0, 4.0}
+
+
+def test_island_start_lists_hit_the_islands_they_claim():
+    rows, cols = K.ISLANDS_SHAPE
+    f = K.islands(rows, cols)
+    lists = K.island_starts(rows, cols, 5)
+    assert {k: n for k, (_s, n) in lists.items()} == {"a": 256, "b": 7, "c": 1, "d": 128}
+    for conn in (4, 8):
+        lab = R.labels(f, conn)
+        for name, (starts, n) in lists.items():
+            assert len(starts) == K.MAX_STARTS
+            hit = [int(lab[r, c]) for r, c in starts if lab[r, c] >= 0]
+            assert len(set(hit)) == n, name
+            assert R.stats_of(lab, starts) == (946, 4 * 946, 4, 4 * n), name
+        assert len([1 for r, c in lists["a"][0] if f[r, c]]) == 256
+        # b: exactly the seven positions are free, and each of them alone carries an island
+        b = lists["b"][0]
+        assert tuple(k for k, (r, c) in enumerate(b) if f[r, c]) == K.B_FREE_POSITIONS == (63, 64, 127, 128, 191, 192, 255)
+        whole = R.reachable_of(lab, b)
+        for k in K.B_FREE_POSITIONS:
+            assert not np.array_equal(R.reachable_of(lab, b[:k] + b[k + 1:]), whole), k
+        c = lists["c"][0]
+        assert [k for k, (r, c_) in enumerate(c) if f[r, c_]] == [255]
+        # d: every island hit is hit twice, by two different cells
+        d = lists["d"][0]
+        assert len(set(d)) == 256 and sorted(np.unique([int(lab[r, c_]) for r, c_ in d], return_counts=True)[1].tolist()) == [2] * 128
+    # seeded: the same lists again
+    assert K.island_starts(rows, cols, 5) == lists
+
+
+@pytest.mark.parametrize("rows,cols", K.PERFORATED_SHAPES)
+def test_perforated_is_one_component_but_for_the_tile_corners(rows, cols):
+    """A corner cell (64a, 64b) is free and all four of its straight neighbours are blocked, so under connectivity 4 it is a
+    component of its own; every other free cell is in the one large component.  Under connectivity 8 all is one component."""
+    f = K.perforated(rows, cols)
+    corners = ((rows - 1) // 64) * ((cols - 1) // 64)
+    blocked = sum(len(range(1, rows, 2)) for _ in range(64, cols, 64)) + sum(len(range(1, cols, 2)) for _ in range(64, rows, 64))
+    nfree = rows * cols - blocked
+    assert int(f.sum()) == nfree
+    assert R.stats_of(R.labels(f, 8)) == (1, nfree, nfree, 0)
+    lab = R.labels(f, 4)
+    assert R.stats_of(lab) == (1 + corners, nfree, nfree - corners, 0)
+    assert (R.sizes_of(lab)[64:rows:64, 64:cols:64] == 1.0).all() and int((R.sizes_of(lab) == 1.0).sum()) == corners
+
+
+@pytest.mark.parametrize("rows,cols", K.PERFORATED_SHAPES)
+def test_perforated_split_has_two_components_of_different_sizes(rows, cols):
+    f = K.perforated(rows, cols, split=True)
+    assert not f[K.SPLIT_ROW].any() and np.array_equal(np.delete(f, K.SPLIT_ROW, 0), np.delete(K.perforated(rows, cols), K.SPLIT_ROW, 0))
+    corners = ((rows - 1) // 64) * ((cols - 1) // 64)
+    lab = R.labels(f, 8)
+    ids, counts = np.unique(lab[lab >= 0], return_counts=True)
+    assert len(ids) == 2 and counts[0] != counts[1] and lab[0, 0] != lab[rows - 1, cols - 1]
+    assert (lab[:K.SPLIT_ROW][f[:K.SPLIT_ROW]] == lab[0, 0]).all() and (lab[K.SPLIT_ROW + 1:][f[K.SPLIT_ROW + 1:]] == lab[rows - 1, cols - 1]).all()
+    lab = R.labels(f, 4)
+    ids, counts = np.unique(lab[lab >= 0], return_counts=True)
+    large = sorted(counts[counts > 1].tolist())
+    assert len(ids) == 2 + corners and len(large) == 2 and large[0] != large[1] and lab[0, 0] != lab[rows - 1, cols - 1]
+
+
+@pytest.mark.parametrize("rows,cols", K.PERFORATED_SHAPES)
+def test_rake_is_one_component_per_seam_column_held_together_by_that_column_alone(rows, cols):
+    f = K.rake(rows, cols)
+    seams = list(range(64, cols, 64))
+    loose = len(range(0, rows, 2)) if cols - seams[-1] > 32 else 0  # teeth behind the last seam column
+    for conn in (4, 8):
+        lab = R.labels(f, conn)
+        size = R.sizes_of(lab)
+        assert R.stats_of(lab)[0] == len(seams) + loose and R.stats_of(lab)[2] == rows + 32 * len(range(0, rows, 2))
+        for j in seams:
+            assert (lab[:, j] == lab[0, j]).all() and (lab[0::2, j - 32:j] == lab[0, j]).all() and size[0, j] == rows + 32 * len(range(0, rows, 2))
+            # without the seam column every tooth is alone: no union of the seam pass is implied by the others
+            g = f.copy()
+            g[:, j] = False
+            assert (R.sizes_of(R.labels(g, conn))[0::2, j - 32:j] == 32.0).all()

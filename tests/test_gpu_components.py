@@ -1,7 +1,11 @@
 """te_run_components / te_run_reachable on the device, through capi, against their definition as a flood fill
 (tests/ref_py/components_ref.py).  The result is unique, so every comparison is array_equal on the bit patterns and no tolerance
 is involved anywhere.  Shapes and inputs: tests/components_cases.py (tests/test_components_plan.py checks on the CPU that the
-shapes marked multi-tile have the tiles claimed and that the designed inputs cross a seam both ways).  Largest map: 512 x 384."""
+shapes marked multi-tile have the tiles claimed and that the designed inputs cross a seam both ways).  The sweep over K.SHAPES
+stops at 512 x 384; the tests at the end of this file run what only the device has and that sweep cannot reach: a write pass whose
+threads take a second turn (1100 x 960, 16400 x 65 in a batch, 4097 x 4097 -- the largest map, and the smallest square one whose
+size float32 rounds), 256 starts that each matter, and seams on which many threads lower the same two roots at once
+(perforated) or one root to different values (rake)."""
 import numpy as np
 import pytest
 
@@ -189,3 +193,149 @@ def test_bad_arguments_leave_the_output_untouched(capi):
         assert (ctx.download(OUT) == MARK).all()
         ctx.run_reachable(K.BELOW, K.THRESHOLD, [(0, 0)] * 256, 4, IN, OUT)
         assert (ctx.download(OUT) == 1.0).all()
+
+
+def check_components(ctx, mode, conn, lab, what, batch=1):
+    rows, cols = lab.shape
+    ctx.run_components(mode, K.THRESHOLD, conn, IN, OUT)
+    got = from_device(ctx.download(OUT), batch, rows, cols)
+    want = R.sizes_of(lab)
+    for k in range(batch):
+        same(got[k], want, f"{what} map {k}")
+    one = R.stats_of(lab)
+    assert ctx.components_stats() == (batch * one[0], batch * one[1], one[2], 0), what
+
+
+def check_reachable(ctx, mode, conn, lab, starts, what):
+    rows, cols = lab.shape
+    ctx.run_reachable(mode, K.THRESHOLD, starts, conn, IN, OUT)
+    same(from_device(ctx.download(OUT), 1, rows, cols)[0], R.reachable_of(lab, starts), what)
+    assert ctx.components_stats() == R.stats_of(lab, starts), what
+
+
+@pytest.mark.parametrize("conn,mode", [(4, K.BELOW), (8, K.ABOVE)])
+def test_the_write_pass_takes_a_second_turn_on_one_large_map(capi, conn, mode):
+    """1100 x 960 is 7,424 cells more than the 4096 x 256 threads of the write pass: the threads that take a second cell write it,
+    and count it in all four totals."""
+    rows, cols = K.BIG
+    free = K.big_random(rows, cols, 1000 * rows + cols)
+    lab = labels_of(free, conn)
+    # two starts in different components: the largest one, and the last free cell in storage order outside it (a cell of the
+    # second turn)
+    big = K.start_sets(lab, free)["largest"][0]
+    x = int(np.flatnonzero((free & (lab != lab[big])).T.reshape(-1))[-1])
+    assert x >= K.WRITE_TURN
+    tail = (x % rows, x // rows)
+    assert lab[tail] != lab[big] and lab[tail] >= 0 and lab[big] >= 0
+    with context(capi, rows, cols) as ctx:
+        ctx.upload_layer(IN, to_device([K.layer_of(free, mode, 3)]))
+        what = f"{rows} x {cols} connectivity {conn}"
+        check_components(ctx, mode, conn, lab, what)
+        check_reachable(ctx, mode, conn, lab, [tail, big], what + " two starts")
+        check_components(ctx, mode, conn, lab, what + " after the starts")
+
+
+def test_the_write_pass_takes_a_second_turn_on_each_map_of_a_batch(capi):
+    rows, cols = K.BIG_THIN
+    frees = [K.big_random(rows, cols, seed) for seed in (11, 12)]
+    labs = [labels_of(f, 4) for f in frees]
+    each = [R.stats_of(lab) for lab in labs]
+    marker = np.full(2 * rows * cols, MARK, np.float32)
+    with context(capi, rows, cols, 2) as ctx:
+        ctx.upload_layer(IN, to_device([K.layer_of(f, K.BELOW, 5 + k) for k, f in enumerate(frees)]))
+        ctx.upload_layer(OUT, marker)
+        ctx.run_components(K.BELOW, K.THRESHOLD, 4, IN, OUT)
+        got = from_device(ctx.download(OUT), 2, rows, cols)
+        for k in range(2):
+            same(got[k], R.sizes_of(labs[k]), f"map {k} of the batch")
+        assert ctx.components_stats() == (each[0][0] + each[1][0], each[0][1] + each[1][1], max(each[0][2], each[1][2]), 0)
+        ctx.upload_layer(OUT, marker)
+        ctx.run_components(K.BELOW, K.THRESHOLD, 4, IN, OUT, map0=1, nmaps=1)
+        got = from_device(ctx.download(OUT), 2, rows, cols)
+        assert (bits(got[0]) == bits(MARK)).all()
+        same(got[1], R.sizes_of(labs[1]), "map 1 alone")
+        assert ctx.components_stats() == each[1]
+
+
+@pytest.mark.parametrize("conn", K.CONNECTIVITIES)
+@pytest.mark.parametrize("mode", K.MODES)
+def test_each_of_256_starts_counts(capi, conn, mode):
+    """946 islands of 4 cells: a start reaches its own island and nothing else, so a start that the starts kernel drops shows."""
+    rows, cols = K.ISLANDS_SHAPE
+    free = K.islands(rows, cols)
+    lab = labels_of(free, conn)
+    with context(capi, rows, cols) as ctx:
+        ctx.upload_layer(IN, to_device([K.layer_of(free, mode, 7)]))
+        for name, (starts, hit) in K.island_starts(rows, cols, 5).items():
+            what = f"islands mode {mode} connectivity {conn} starts {name}"
+            check_reachable(ctx, mode, conn, lab, starts, what)
+            assert ctx.components_stats()[3] == 4 * hit, what
+            check_components(ctx, mode, conn, lab, what + ", components after them")
+
+
+@pytest.mark.parametrize("rows,cols", K.PERFORATED_SHAPES)
+@pytest.mark.parametrize("split", [False, True])
+def test_many_threads_lower_the_same_two_roots(capi, rows, cols, split):
+    """perforated: every free seam cell of a tile edge unites the same two tile-local components, cell by cell -- the retry of
+    `unite`.  Every call is held to the reference, not to the first call."""
+    free = K.perforated(rows, cols, split)
+    starts = {"a corner": [(0, 0)], "beyond the split row": [(rows - 1, cols - 2)], "both": [(0, 0), (rows - 1, cols - 2)]}
+    with context(capi, rows, cols) as ctx:
+        for mode in K.MODES:
+            ctx.upload_layer(IN, to_device([K.layer_of(free, mode, 9)]))
+            for conn in K.CONNECTIVITIES:
+                lab = labels_of(free, conn)
+                what = f"perforated {rows} x {cols} split {split} mode {mode} connectivity {conn}"
+                for turn in range(3):
+                    check_components(ctx, mode, conn, lab, f"{what} call {turn}")
+                for sname, st in starts.items():
+                    assert all(lab[s] >= 0 for s in st)
+                    check_reachable(ctx, mode, conn, lab, st, f"{what} from {sname}")
+    # three copies in one call: three times the workgroups in flight in the seam pass
+    with context(capi, rows, cols, 3) as ctx:
+        ctx.upload_layer(IN, to_device([K.layer_of(free, K.BELOW, 9)] * 3))
+        for conn in K.CONNECTIVITIES:
+            check_components(ctx, K.BELOW, conn, labels_of(free, conn), f"perforated {rows} x {cols} split {split} connectivity {conn}, 3 copies", batch=3)
+
+
+@pytest.mark.parametrize("rows,cols", K.PERFORATED_SHAPES)
+def test_many_threads_lower_one_root_to_different_values(capi, rows, cols):
+    """rake: per tile edge, 32 tile-local components with smaller roots are united with the one root of the seam column's piece, and
+    nothing else holds them together -- `unite` has to carry on with what its atomic returned, or a tooth is left outside.  (On
+    `perforated` every union of a tile edge is the same pair and the map is connected many times over; a union dropped there is
+    made good by another.)"""
+    free = K.rake(rows, cols)
+    with context(capi, rows, cols) as ctx:
+        for mode in K.MODES:
+            ctx.upload_layer(IN, to_device([K.layer_of(free, mode, 13)]))
+            for conn in K.CONNECTIVITIES:
+                lab = labels_of(free, conn)
+                what = f"rake {rows} x {cols} mode {mode} connectivity {conn}"
+                for turn in range(3):
+                    check_components(ctx, mode, conn, lab, f"{what} call {turn}")
+                check_reachable(ctx, mode, conn, lab, [(rows - 2, 40)], f"{what} from the last tooth of the first seam column")
+    with context(capi, rows, cols, 3) as ctx:
+        ctx.upload_layer(IN, to_device([K.layer_of(free, K.ABOVE, 13)] * 3))
+        for conn in K.CONNECTIVITIES:
+            check_components(ctx, K.ABOVE, conn, labels_of(free, conn), f"rake {rows} x {cols} connectivity {conn}, 3 copies", batch=3)
+
+
+def test_a_size_that_float32_cannot_hold(capi):
+    """4097 x 4097 all free: one component of 16,785,409 cells, which float32 rounds to 16,785,408 (uint32 -> float32, to nearest
+    even).  No smaller square map has a size that the conversion can get wrong."""
+    rows, cols = K.FLOAT_INEXACT
+    n = rows * cols
+    want = R.sizes_of(np.zeros((rows, cols), np.int64))
+    assert bits(want[:1, :1])[0, 0] == bits(np.float32(np.uint32(n))) and float(want[0, 0]) == n - 1 and (want == want[0, 0]).all()
+    with context(capi, rows, cols) as ctx:
+        ctx.upload_layer(IN, np.ones(n, np.float32))
+        ctx.run_components(K.BELOW, K.THRESHOLD, 4, IN, OUT)
+        got = ctx.download(OUT)
+        bad = np.flatnonzero(bits(got) != bits(want[0, 0]))
+        assert len(bad) == 0, f"{len(bad)} cells differ, first {[(int(x), float(got[x])) for x in bad[:5]]}, want {float(want[0, 0])}"
+        assert ctx.components_stats() == (1, n, n, 0)
+        ctx.run_reachable(K.BELOW, K.THRESHOLD, [(rows - 1, cols - 1)], 8, IN, OUT)
+        got = ctx.download(OUT)
+        bad = np.flatnonzero(bits(got) != bits(np.float32(1.0)))
+        assert len(bad) == 0, f"{len(bad)} cells are not 1.0, first {[(int(x), float(got[x])) for x in bad[:5]]}"
+        assert ctx.components_stats() == (1, n, n, n)
