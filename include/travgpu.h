@@ -429,9 +429,13 @@ int te_check_inclination(te_ctx* ctx, int map, int n_segments, const double* sta
 /* TraversabilityMap::traversabilityFootprint(footprintYaw) (TraversabilityMap.cpp:239-305): for every cell of every map the
  * footprint polygon (n_points vertices points_xy = x0 y0 x1 y1 .. in the footprint frame, footprint/footprint_polygon
  * :91-103) centred on the cell, as given -> layer traversability_x, and turned by `yaw` about z -> traversability_rot;
- * each cell gets isTraversable(polygon)'s mean (:586-645) or 0 when the polygon touches an untraversable cell.  Needs the
- * untraversable-cell mask the circular footprint pass leaves behind (te_run_chain with TE_RUN_FOOTPRINT or
- * te_run_footprint first).  At most TE_MAX_POLYGON_VERTICES points.  Asynchronous like te_run_chain; read the layers
+ * each cell gets isTraversable(polygon)'s mean (:586-645) or 0 when the polygon touches an untraversable cell.  Needs a
+ * footprint pass over the resident chain (te_run_chain with TE_RUN_FOOTPRINT or te_run_footprint first; TE_ERR_NOT_READY
+ * otherwise).  The untraversable-cell mask that pass leaves behind is what the kernels read; where a score layer was
+ * written since (te_upload_layer, a prefetch, te_device_ptr), after te_move_map with results kept, or after a region run
+ * that found the mask not done, the call builds the mask again from the scores now resident before it reads it -- as
+ * te_check_footprint_paths_radius does, and as the reference, which evaluates isTraversableForFilters on the live score
+ * layers.  At most TE_MAX_POLYGON_VERTICES points.  Asynchronous like te_run_chain; read the layers
  * with te_download_layer(TE_LAYER_TRAVERSABILITY_X / _ROT). */
 #define TE_MAX_POLYGON_VERTICES 32
 int te_run_polygon_footprint(te_ctx* ctx, int n_points, const double* points_xy, double yaw);
@@ -439,7 +443,7 @@ int te_run_polygon_footprint(te_ctx* ctx, int n_points, const double* points_xy,
  * vertex_xy[2*vertex_offset[k] .. 2*vertex_offset[k+1]) in the map frame (at least one each; vertex_offset[0] == 0).
  * traversability[k] = mean over the polygon's cells, traversabilityDefault_ when it covers no cell centre, 0 when
  * is_traversable[k] == 0.  The per-segment polygons of checkPolygonalFootprintPath (:464-584) go through this.  Same
- * precondition as above.  Host buffers; synchronous. */
+ * precondition, and the same rule for a mask that is not done, as above.  Host buffers; synchronous. */
 int te_polygons_traversable(te_ctx* ctx, int map, int n_polygons, const int* vertex_offset, const double* vertex_xy,
                             unsigned char* is_traversable, double* traversability);
 /* TraversabilityMap::isTraversable(polygon, computeUntraversablePolygon = true, traversability, untraversablePolygon)

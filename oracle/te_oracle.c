@@ -1245,7 +1245,7 @@ int teo_polygon_untraversable_hull(const teo_geom* g, const teo_params* p, const
     }
   }
   *is_traversable = (unsigned char)ok;
-  *traversability = ok ? value : 0.0;
+  *traversability = nbad == 0 ? value : 0.0; /* no cell at all: traversabilityDefault_ as it is (:627), also where that is 0 or -0 and the polygon counts as untraversable (:628) */
   int rc = 0;
   *n_hull = 0;
   if (!ok) { /* :634-640 */

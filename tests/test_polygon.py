@@ -7,18 +7,7 @@ import numpy as np
 import pytest
 
 from tests.helpers import OUT_LAYERS, to_te_params
-
-FOOTPRINT = [[0.45, 0.30], [0.45, -0.30], [-0.45, -0.30], [-0.45, 0.30]]  # robot_footprint_parameter.yaml:3
-
-
-def terrain(rows, cols, seed, holes=0.02, boxes=6):
-    from traversability_estimation_amd import synth
-    e = synth.perlin_elevation(rows, cols, seed=seed)
-    if boxes and rows > 8 and cols > 8:
-        e = synth.with_steps(e, boxes, seed=seed + 1)
-    if holes:
-        e = synth.with_holes(e, holes, seed=seed + 2)
-    return np.ascontiguousarray(e, dtype=np.float32).reshape(-1)
+from tests.polygon_cases import EXISTING, FOOTPRINT, POINTS_XYZ, terrain  # noqa: F401  (other test modules import them from here)
 
 
 def chain_layers(oracle, g, p, elev):
@@ -168,20 +157,11 @@ def gpu_setup(capi, oracle, rows, cols, res, pos, elev, **over):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", [
-    dict(rows=100, cols=133, res=0.03, pts=FOOTPRINT, yaw=math.pi / 2),
-    dict(rows=150, cols=70, res=0.05, pts=FOOTPRINT, yaw=0.4),
-    dict(rows=64, cols=64, res=0.05, pts=[[0.3, 0.0], [-0.2, 0.25], [-0.2, -0.25]], yaw=-2.2),
-    dict(rows=61, cols=90, res=0.04, pts=[[0.3, 0.3], [0.3, -0.3], [0.0, -0.3], [0.0, 0.0], [-0.3, 0.0], [-0.3, 0.3]], yaw=1.0),
-    dict(rows=33, cols=20, res=0.1, pts=[[0.01, 0.01], [0.01, -0.01], [-0.01, -0.01]], yaw=0.3),  # covers no cell centre
-    dict(rows=5, cols=7, res=0.1, pts=FOOTPRINT, yaw=0.9),  # footprint larger than the map
-    dict(rows=300, cols=40, res=0.05, pts=FOOTPRINT, yaw=math.pi / 2),  # several workgroups along the rows
-    dict(rows=120, cols=60, res=0.02, pts=[[0.72, 0.48], [0.72, -0.48], [-0.72, -0.48], [-0.72, 0.48]], yaw=0.3,
-         over=dict(fp_radius=0.2, fp_offset=0.1)),  # 72 x 48 cells: too large for the offset table
-])
+@pytest.mark.parametrize("case", EXISTING)  # (tests/polygon_cases.py: the eight footprints, each with the kernel it claims)
 @pytest.mark.parametrize("per_cell", [False, True])
 def test_polygon_footprint_layers(capi, oracle, case, per_cell):
-    """Both kernels (offset table + LDS tile; every cell of every bounding box) against the oracle, bit for bit."""
+    """Both kernels (offset table + LDS tile; every cell of every bounding box) against the oracle, bit for bit.  Which kernel
+    a footprint takes without the option is claimed in tests/polygon_cases.py and asserted in tests/test_polygon_table.py."""
     rows, cols, res = case["rows"], case["cols"], case["res"]
     elev = terrain(rows, cols, seed=rows + cols)
     ctx, g, op, layers = gpu_setup(capi, oracle, rows, cols, res, (0.7, -0.2), elev, fp_default=0.3, **case.get("over", {}))
@@ -246,9 +226,6 @@ def test_polygon_calls_need_the_mask(capi, oracle):
 
 
 # ---------------------------------------------------------------- polygonal footprint paths (:464-584)
-POINTS_XYZ = [[0.45, 0.30, 0.0], [0.45, -0.30, 0.0], [-0.45, -0.30, 0.0], [-0.45, 0.30, 0.0]]
-
-
 def random_pose_paths(g, rng, count, scale=1.0):
     """MPC-style candidates: 1..5 poses, mostly yaw-only orientations, a few tilted, some starting outside the map."""
     paths, cons = [], []
@@ -409,6 +386,27 @@ def test_library_path_polygons_match_python_restatement(capi):
                     assert ga == wa, (k, ga, wa)
     with pytest.raises(capi.TeError, match="footprint points"):
         capi.path_polygons(paths[:1], np.zeros((0, 3)))
+
+
+def test_library_path_polygons_end_at_the_vertex_cap(capi):
+    """A conservative path's vertex lists grow by the footprint's points with every pose.  With four points the 256th pose
+    reaches kMaxPathPolygonVertices = 1024: te_path_polygons ends a longer path with the polygon of that pose, the last that
+    fits -- vertex for vertex the restatement's first 255 polygons -- and gives a path of 256 poses or fewer whole."""
+    t = np.arange(300)
+    yaw = 0.2 + 0.002 * t
+    path = np.stack([0.008 * t, 0.3 + 0.002 * t, np.zeros(300), np.zeros(300), np.zeros(300), np.sin(yaw / 2), np.cos(yaw / 2)], axis=1)
+    pts = [tuple(float(v) for v in p) for p in POINTS_XYZ]
+    want = py_path_polygons(path, pts, True)
+    assert len(want) == 299 and len(want[254][0]) <= 2048
+    got = capi.path_polygons([path, path[:256], path[:255], path], POINTS_XYZ, np.array([1, 1, 1, 0], np.uint8))
+    assert [len(g) for g in got] == [255, 255, 254, 299]
+    for k, n in enumerate((255, 255, 254)):
+        for (gv, ga), (wv, wa) in zip(got[k], want[:n]):
+            assert gv.shape == (len(wv), 2) and np.array_equal(gv, np.array(wv, dtype=np.float64).reshape(-1, 2))
+            assert ga == wa
+    plain = py_path_polygons(path, pts, False)  # (not conservative: four points per pose, no cap)
+    for (gv, ga), (wv, wa) in zip(got[3], plain):
+        assert np.array_equal(gv, np.array(wv, dtype=np.float64).reshape(-1, 2)) and ga == wa
 
 
 @pytest.mark.gpu

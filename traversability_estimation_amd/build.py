@@ -21,7 +21,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 SOURCES = ["csrc/te_kernels.hip", "csrc/te_shim.hip", "csrc/te_transfer.hip", "csrc/te_paths_api.hip", "csrc/te_multi.hip", "csrc/te_stage.hip", "csrc/te_fast_step.hip", "csrc/te_step5.hip", "csrc/te_slide_normals.hip", "csrc/te_normals3.hip", "csrc/te_normals_small.hip", "csrc/te_normals_raster.hip", "csrc/te_footprint.hip", "csrc/te_footprint3.hip", "csrc/te_footprint4.hip", "csrc/te_footprint5.hip", "csrc/te_footprint_any.hip", "csrc/te_filter_any.hip", "csrc/te_paths.hip", "csrc/te_path_discs.hip", "csrc/te_gridmap_msg.hip", "csrc/te_image.hip", "csrc/te_occupancy.hip", "csrc/te_cloud.hip", "csrc/te_submap.hip", "csrc/te_move.hip", "csrc/te_expr.hip", "csrc/te_expr_api.hip", "csrc/te_median.hip", "csrc/te_median_api.hip", "csrc/te_radius.hip", "csrc/te_radius_api.hip", "csrc/te_distance.hip", "csrc/te_distance_api.hip", "csrc/te_components.hip", "csrc/te_components_api.hip", "csrc/te_window_expr.hip", "csrc/te_window_expr_api.hip", "csrc/te_pointwise.hip", "csrc/te_pointwise_api.hip", "csrc/te_polygon.hip", "csrc/te_trace.hip"]
 # (every header of csrc/ and the public one; an object's key covers the ones it includes, see _deps)
-HEADERS = ["csrc/te_internal.h", "csrc/te_march.h", "csrc/te_march5.h", "csrc/te_cell.h", "csrc/te_eig.h", "csrc/te_eig3.h", "csrc/te_geom.h", "csrc/te_msg.h", "csrc/te_image.h", "csrc/te_occupancy.h", "csrc/te_cloud.h", "csrc/te_out_kernels.h", "csrc/te_ctx.h", "csrc/te_ctx_state.h", "csrc/te_devbuf.h", "csrc/te_slab.h", "csrc/te_submap_plan.h", "csrc/te_move_plan.h", "csrc/te_n3_plan.h", "csrc/te_hole_routing.h", "csrc/te_face_flags.h", "csrc/te_tie_triple.h", "csrc/te_fp_table.h", "csrc/te_disc.h", "csrc/te_disc_table.h", "csrc/te_fp_route.h", "csrc/te_chain_route.h", "csrc/te_shapes.h", "csrc/te_path_visit.h", "csrc/te_path_walk.h", "csrc/te_strips.h", "csrc/te_expr.h", "csrc/te_expr_launch.h", "csrc/te_median.h", "csrc/te_median_plan.h", "csrc/te_median_launch.h", "csrc/te_radius_plan.h", "csrc/te_radius_launch.h", "csrc/te_region_plan.h", "csrc/te_distance.h", "csrc/te_distance_plan.h", "csrc/te_distance_launch.h", "csrc/te_components.h", "csrc/te_components_plan.h", "csrc/te_components_launch.h", "csrc/te_window_plan.h", "csrc/te_window_expr_launch.h", "csrc/te_user_layers.h", "csrc/te_layer_call.h", "csrc/te_pointwise_launch.h", "../include/travgpu.h"]
+HEADERS = ["csrc/te_internal.h", "csrc/te_march.h", "csrc/te_march5.h", "csrc/te_cell.h", "csrc/te_eig.h", "csrc/te_eig3.h", "csrc/te_geom.h", "csrc/te_msg.h", "csrc/te_image.h", "csrc/te_occupancy.h", "csrc/te_cloud.h", "csrc/te_out_kernels.h", "csrc/te_ctx.h", "csrc/te_ctx_state.h", "csrc/te_devbuf.h", "csrc/te_slab.h", "csrc/te_submap_plan.h", "csrc/te_move_plan.h", "csrc/te_n3_plan.h", "csrc/te_hole_routing.h", "csrc/te_face_flags.h", "csrc/te_tie_triple.h", "csrc/te_fp_table.h", "csrc/te_disc.h", "csrc/te_disc_table.h", "csrc/te_fp_route.h", "csrc/te_chain_route.h", "csrc/te_shapes.h", "csrc/te_path_visit.h", "csrc/te_polygon_table.h", "csrc/te_path_walk.h", "csrc/te_strips.h", "csrc/te_expr.h", "csrc/te_expr_launch.h", "csrc/te_median.h", "csrc/te_median_plan.h", "csrc/te_median_launch.h", "csrc/te_radius_plan.h", "csrc/te_radius_launch.h", "csrc/te_region_plan.h", "csrc/te_distance.h", "csrc/te_distance_plan.h", "csrc/te_distance_launch.h", "csrc/te_components.h", "csrc/te_components_plan.h", "csrc/te_components_launch.h", "csrc/te_window_plan.h", "csrc/te_window_expr_launch.h", "csrc/te_user_layers.h", "csrc/te_layer_call.h", "csrc/te_pointwise_launch.h", "../include/travgpu.h"]
 LIB = os.path.join(_HERE, "libtravgpu.so")
 LAB_LIB = os.path.join(_HERE, "libtravgpu_lab.so")
 OBJDIR = os.path.join(_HERE, "_build")

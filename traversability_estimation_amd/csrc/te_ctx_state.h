@@ -53,7 +53,7 @@ struct CtxState {
   // of the parameters has a tie cell, so what was computed at the old position stands wherever no cell left or entered a disc
   // -- the region contract, as after elevation_tile_written: the caller hands the exposed rectangles and the trailing lines
   // to te_run_chain_region.  The count and the face flags (built per 64 x 4 tile, which a shift misaligns) are unknown, and
-  // the untraversable mask counts as not built until a whole pass or a path check rebuilds it.  Without results_kept the
+  // the untraversable mask counts as not built until a whole pass, a path check or a polygon call rebuilds it.  Without results_kept the
   // elevation is still shifted and valid, and everything computed from it is dropped: as a whole upload.
   void map_moved(bool results_kept) {
     if (!results_kept) {
@@ -230,7 +230,8 @@ struct CtxState {
     trav_external_ = true;
     if (filter == TE_FILTER_NORMALS) layers_written_ |= kNormalLayers;
   }
-  // te_check_footprint_paths_radius built the untraversable mask on its own (and with it a deferred combined layer).
+  // A reader of the mask outside a footprint pass -- te_check_footprint_paths_radius, the four polygon entry points -- found
+  // it not done and built it on its own (and with it a deferred combined layer): ensure_mask, te_paths_api.hip.
   void mask_built() {
     combine_deferred_ = false;
     mask_done_ = true;
@@ -275,8 +276,8 @@ struct CtxState {
   // ... and the footprint layer is complete over them
   bool footprint_done_ = false;
   // The untraversable mask (Layers::untrav) is complete for the scores and the three parameters it reads (fp_max_gap,
-  // fp_critical_step, fp_check_roughness).  Set by every footprint pass and by te_check_footprint_paths_radius, which builds
-  // the mask on its own when it is not; cleared wherever footprint_done is cleared -- except that params_changed keeps it
+  // fp_critical_step, fp_check_roughness).  Set by every footprint pass and by te_check_footprint_paths_radius and the polygon
+  // entry points, which build the mask on their own when it is not; cleared wherever footprint_done is cleared -- except that params_changed keeps it
   // when nothing the mask reads changed -- and by a write to a score layer (which leaves footprint_done as it was).
   bool mask_done_ = false;
   // the chain left the combined layer to the mask kernel of the footprint pass behind it, which has not run yet

@@ -1,30 +1,15 @@
 // te_geom.h -- grid_map_core geometry on the device: cell centres, checkIfPositionWithinMap,
-// getIndexFromPosition and the Bresenham LineIterator, in the reference's own double arithmetic.
+// getIndexFromPosition (both in te_polygon_table.h) and the Bresenham LineIterator, in the reference's own double arithmetic.
 // (te_path_visit.h holds a plain C++ copy of pos_inside, pos_to_index and LineIt -- pv::Geom, for the host driver's sizing and
-// the CPU check of the visit plan: a change here is a change there.  te_check_footprint_paths_radius compares the two walks'
-// visit counts on every call.)
+// the CPU check of the visit plan: a change here or there is a change in both.  te_check_footprint_paths_radius compares the
+// two walks' visit counts on every call.)
 #pragma once
 #include "te_internal.h"
 
 namespace te {
 
-__device__ __forceinline__ double cell_x(const Geo& g, int i) { return g.ax + g.res * (double)(-i); }
-__device__ __forceinline__ double cell_y(const Geo& g, int j) { return g.ay + g.res * (double)(-j); }
-
-// checkIfPositionWithinMap (grid_map_core)
-__device__ __forceinline__ bool pos_inside(const Geo& g, double x, double y) {
-  const double tx = -((x - g.pos_x) - 0.5 * g.len_x);
-  const double ty = -((y - g.pos_y) - 0.5 * g.len_y);
-  return tx >= 0.0 && ty >= 0.0 && tx < g.len_x && ty < g.len_y;
-}
-// getIndexFromPosition (grid_map_core)
-__device__ __forceinline__ bool pos_to_index(const Geo& g, double x, double y, int& i, int& j) {
-  const double vx = ((x - 0.5 * g.len_x) - g.pos_x) / g.res;
-  const double vy = ((y - 0.5 * g.len_y) - g.pos_y) / g.res;
-  i = (int)(-vx);
-  j = (int)(-vy);
-  return pos_inside(g, x, y) && i >= 0 && j >= 0 && i < g.rows && j < g.cols;
-}
+// cell_x, cell_y, pos_inside (checkIfPositionWithinMap) and pos_to_index (getIndexFromPosition): te_polygon_table.h, which
+// te_internal.h includes -- plain C++ for the host and the device, so that the CPU check of the polygon table runs them too.
 
 // grid_map::LineIterator (Bresenham from (si,sj) to (ei,ej), both included)
 struct LineIt {

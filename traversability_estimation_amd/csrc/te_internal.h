@@ -12,6 +12,7 @@
 #include "te_disc.h"
 #include "te_face_flags.h"
 #include "te_fp_route.h"
+#include "te_polygon_table.h"
 #include "te_slab.h"
 #include "travgpu.h"
 
@@ -51,14 +52,7 @@ bool trace_available();
 static_assert(kSlabGuardRows == kMaxRadiusCells + 16, "te_slab.h: the guard rows cover the largest radius and the prefetch distance");
 constexpr int kMaxSpiral = 4096;     // ordered offsets of the footprint spiral
 
-// Map geometry as the kernels need it.  Device layout of every layer: [batch][cols][rows] float32,
-// i.e. grid_map's column-major matrix; the FAST axis is the grid_map row index i ("x" below).
-struct Geo {
-  int rows, cols, batch;
-  double res;
-  double ax, ay;  // position of cell 0: pos + (0.5*len - 0.5*res); x(i) = ax + res*(-i)
-  double len_x, len_y, pos_x, pos_y;
-};
+// (struct Geo, the map geometry as the kernels need it: te_polygon_table.h, plain C++ the CPU checks can include)
 
 struct ChainParams {
   Disc normals, rough, step1, step2;
@@ -165,23 +159,10 @@ struct PolygonArgs {
   double def;                                       // traversabilityDefault_
   double off[2][2 * TE_MAX_POLYGON_VERTICES];       // vertex offsets from the centre cell: [0] as given, [1] turned by yaw
 };
-// offset table of one footprint polygon (build_polygon_table): rows of the bounding box that hold cells, each a header
-// word (di index | items << 8) followed by its items (dj index | run length << 8 | "decided per cell" << 31)
-struct PolygonTable {
-  int first;              // index of the first word in the stream
-  int n_rows;
-  int n_uncertain;
-  int di_min, dj_min;     // offset of table index 0
-  int di_span, dj_span;   // extent of the staged tile in offsets
-};
-struct PolygonTables {
-  PolygonTable t[2];
-};
-bool build_polygon_table(const Geo& g, int n, const double* off, std::vector<unsigned>& stream, PolygonTable& tb);
+// (PolygonTable, PolygonTables and build_polygon_table, the offset table of one footprint polygon: te_polygon_table.h)
 hipError_t launch_polygon_footprint_table(const Geo& g, const PolygonArgs& a, const PolygonTables& tabs, const unsigned* d_stream,
                                           const float* trav, const uint8_t* untrav, float* out_x, float* out_rot,
                                           hipStream_t stream);
-void rotate_footprint(int n_points, const double* points_xy, double yaw, double* out_xy);
 hipError_t launch_polygon_footprint(const Geo& g, const PolygonArgs& a, const float* trav, const uint8_t* untrav, float* out_x,
                                     float* out_rot, hipStream_t stream);
 hipError_t launch_polygons_traversable(const Geo& g, double def, int n_polygons, const int* vertex_offset, const double* vertex_xy,

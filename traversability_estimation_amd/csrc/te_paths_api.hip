@@ -57,6 +57,16 @@ int path_disc_table(te_ctx* c, double radius, double offset, unsigned long long 
   }
   return TE_OK;
 }
+
+// The untraversable mask (Layers::untrav), built on the first call after the scores (or one of the three parameters it
+// reads) changed: every entry point whose kernels read the mask calls this before it launches one.  Queued on the
+// context's stream, c->mu held.
+hipError_t ensure_mask(te_ctx* c) {
+  if (c->st.mask_done()) return hipSuccess;
+  const hipError_t e = launch_footprint_mask(c->geo, c->fp, c->L, usable_face_flags(c), c->st.combine_deferred() ? &c->cp : nullptr, c->stream);
+  if (e == hipSuccess) c->st.mask_built();
+  return e;
+}
 }  // namespace
 
 extern "C" {
@@ -141,11 +151,7 @@ int te_check_footprint_paths_radius(te_ctx* c, int map, int n_paths, const int* 
   if (e == hipSuccess) e = hipMemcpyAsync(d_classes, classes.data(), p_classes.bytes(), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemsetAsync(s.keys, 0xFF, p_keys.bytes(), c->stream);  // pv::kEmptyKey
   if (e == hipSuccess) e = hipMemsetAsync(s.counters, 0, p_cnt.bytes(), c->stream);
-  // the untraversable mask: built on the first call after the scores (or one of the three parameters it reads) changed
-  if (e == hipSuccess && !c->st.mask_done()) {
-    e = launch_footprint_mask(g, c->fp, c->L, usable_face_flags(c), c->st.combine_deferred() ? &c->cp : nullptr, c->stream);
-    if (e == hipSuccess) c->st.mask_built();
-  }
+  if (e == hipSuccess) e = ensure_mask(c);
   const size_t per = (size_t)g.rows * g.cols;
   if (e == hipSuccess)
     e = launch_path_discs(g, s, d_classes, c->L.trav + per * map, c->L.untrav + per * map, c->params.fp_default,
@@ -287,6 +293,7 @@ int te_run_polygon_footprint(te_ctx* c, int n_points, const double* points_xy, d
   // offset tables (te_polygon.hip); polygons that do not fit the table format, or te_set_option(TE_OPT_POLYGON_PER_CELL) (a debugging
   // aid: both kernels give identical layers), take the kernel that evaluates every cell of every bounding box
   PolygonTables tabs;
+  HIP_TRY(ensure_mask(c));  // (a score layer written since the footprint pass: the mask is rebuilt from the scores now resident)
   HIP_TRY(hipStreamSynchronize(c->stream));  // the previous call's table upload has been consumed
   c->poly_stream_host.clear();
   bool table = !c->opt_polygon_per_cell;
@@ -308,7 +315,8 @@ int te_run_polygon_footprint(te_ctx* c, int n_points, const double* points_xy, d
 }
 
 namespace {
-// isTraversable(polygon) for a batch of validated polygons; context locked, mask present
+// isTraversable(polygon) for a batch of validated polygons; context locked, footprint pass done (the mask is rebuilt here
+// when a score layer was written since: ensure_mask)
 int polygons_traversable_locked(te_ctx* c, int map, int n_polygons, const int* vertex_offset, const double* vertex_xy,
                                 unsigned char* is_traversable, double* traversability, const char* who) {
   if (n_polygons == 0) return TE_OK;
@@ -326,7 +334,8 @@ int polygons_traversable_locked(te_ctx* c, int map, int n_polygons, const int* v
   double* d_trav = p_trav.in(tmp);
   unsigned char* d_ok = p_ok.in(tmp);
   const size_t per = (size_t)c->geo.rows * c->geo.cols;
-  hipError_t e = hipMemcpyAsync(d_off, vertex_offset, p_off.bytes(), hipMemcpyHostToDevice, c->stream);
+  hipError_t e = ensure_mask(c);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_off, vertex_offset, p_off.bytes(), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_xy, vertex_xy, p_xy.bytes(), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess)
     e = launch_polygons_traversable(c->geo, c->params.fp_default, n_polygons, d_off, d_xy, c->L.trav + per * map,
@@ -383,7 +392,8 @@ int te_polygon_untraversable_hull(te_ctx* c, int map, int n_vertices, const doub
   HIP_TRY(tmp.once(cv.total));
   std::vector<double> rows5((size_t)5 * c->geo.rows);
   const size_t per = (size_t)c->geo.rows * c->geo.cols;
-  hipError_t e = hipMemcpyAsync(p_xy.in(tmp), vertex_xy, p_xy.bytes(), hipMemcpyHostToDevice, c->stream);
+  hipError_t e = ensure_mask(c);  // (built by polygons_traversable_locked above: nothing to do)
+  if (e == hipSuccess) e = hipMemcpyAsync(p_xy.in(tmp), vertex_xy, p_xy.bytes(), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = launch_polygon_untraversable_rows(c->geo, n_vertices, p_xy.in(tmp), c->L.untrav + per * map, p_rows.in(tmp), c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(rows5.data(), p_rows.in(tmp), p_rows.bytes(), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
